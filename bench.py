@@ -9,23 +9,32 @@ the raw-parameter gradient -- followed by an Adam update of the raw parameters (
 host memoises between evaluations at equal parameters can hit).  X and y are resident in HBM before the timed region (model creation); only
 the O(C^2 Q) parameter table goes host->device per step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5] [--mode replicas|sharded]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5] [--mode replicas|sharded] [--full]
+                    [--dump-outputs DIR]
 
-The default line (cfg2) also carries, outside its timed region:
+A plain run sets up, runs W warm-up steps, times exactly K steps, and prints the line: metric, value, unit, ms_per_step (one timed step),
+the roofline fraction priced on ms_per_step, and how the last step was scheduled.  `--dump-outputs DIR` writes what the timed path returned
+in its last timed step as DIR/<name>.npy (loss and the gradient of every raw parameter; predict_f's mean and variance for cfg4), so that
+two builds can be compared output for output: the inputs are seeded, identical from run to run.
+
+`--full` adds everything else, outside the headline's statistic:
   configs       the other BASELINE.json configurations on this GPU: cfg3 (MOSM C=8 Q=5 N=32768 LML+gradient), cfg4 (CSM C=4 Q=3 N=16384
                 predict_f at 4096 points), cfg5 (Titsias N=100000 M=2048 ELBO+gradient): ms_per_step, roofline fraction, steps
   cpu_baseline  the torch-CPU port of the reference's op sequence (oracle/torch_port.py) timed on this box's host cores AT N = 8192
-  roofline / gram_hbm / moments_hbm / stages_ms_per_eval from HIP events inside the timed region
+  sustained     the same step 200 more times behind the timed region
+  roofline / gram_hbm / moments_hbm / stages_ms_per_eval from HIP events inside the timed region (the first timed step carries them) and
+                from LML-only evaluations behind it
+  sharded       at N > 1, the sharded probes below
 `--config cfgN` makes that configuration the timed step instead (same JSON shape).
 
 N > 1: one rank per GPU.  Under a launcher (torch.distributed.run: WORLD_SIZE / RANK / LOCAL_RANK / MASTER_* in the environment) this process is one
 rank; as a PLAIN process (`python bench.py --gpus N`, WORLD_SIZE unset) it starts the N ranks itself (self_launch: rank r on GPU r, rendezvous on
 127.0.0.1) and exits non-zero with a one-line reason when the node shows fewer than N GPUs -- it never prints a 1-GPU line for an N-GPU request.
-The N > 1 line carries `sharded_cfg3` at top level (ONE N = 32768 evaluation split over the ranks: ms_one_gpu, ms_sharded, speedup, rccl_ranks,
+The N > 1 line with --full carries `sharded_cfg3` at top level (ONE N = 32768 evaluation split over the ranks: ms_one_gpu, ms_sharded, speedup, rccl_ranks,
 rel_loss / rel_grad) next to the replicas `value`.
   replicas (default)  `value` = aggregate evals/s of N independent replicas of the workload (one 13 ms evaluation does not pay for an
-                      exchange per pivot block; N GPUs are best used as N evaluations: restarts, models); scaling "weak".  BEFORE the timed
-                      region every rank runs the `sharded` probes -- the north_star's split of ONE evaluation over the GPUs
+                      exchange per pivot block; N GPUs are best used as N evaluations: restarts, models); scaling "weak".  With --full,
+                      BEFORE the timed region every rank runs the `sharded` probes -- the north_star's split of ONE evaluation over the GPUs
                       (mogp_exact_eval_sharded: owned Gram / moment tiles, one RCCL all-gather per 512-wide pivot block issued by the
                       library on its own stream): cfg3 first, then cfg2 and the data-parallel sparse bound (cfg5).  Each probe is a child
                       process group of its own under its own watchdog, so a stuck collective costs that probe, not the line.
@@ -132,6 +141,21 @@ def training_step(m, run_step, kind):
         run_step()
         opt.step()
     return step
+
+
+def dump_outputs(path, kind, result, m):
+    """what the last timed step returned to its caller, as path/<name>.npy in float64: predict_f's mean and variance, or the loss and the
+    gradient of every raw parameter (what the Adam update then reads; it does not change them).  A few hundred kB at most."""
+    os.makedirs(path, exist_ok=True)
+    if kind == "predict":
+        arrays = {"mean": result[0], "variance": result[1]}
+    else:
+        arrays = {"loss": result}
+        for i, p in enumerate(m.parameters()):
+            if p.grad is not None:
+                arrays["grad_%02d_%s" % (i, "".join(ch if ch.isalnum() else "_" for ch in (p._name or "param")))] = p.grad
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(v, dtype=np.float64))
 
 
 def cpu_baseline(N, C, Q, budget_s=240.0):
@@ -544,13 +568,14 @@ def sharded_headline(sharded, world):
 
 def selftest_main(a, rank, world):
     """the orchestration of an N > 1 run without a GPU or a native call (tests/test_bench_dist_cpu.py): gloo ranks, the probe mechanism with its
-    `dummy` probe (one all-reduce of (1, rank + 1) in a child process group), the timed region around a sleeping step, the line's top level"""
+    `dummy` probe (one all-reduce of (1, rank + 1) in a child process group; --full, as the probes of a real run), the timed region around a sleeping step, the line's top level"""
     dist = None
     sharded = None
     if world > 1:
-        base_port = int(os.environ.get("MASTER_PORT", "29655")) + 20
-        sharded = run_probes(["dummy"], base_port, a.probe_timeout)
-        sharded["ranks"] = world
+        if a.full:
+            base_port = int(os.environ.get("MASTER_PORT", "29655")) + 20
+            sharded = run_probes(["dummy"], base_port, a.probe_timeout)
+            sharded["ranks"] = world
         import torch.distributed as dist
         dist.init_process_group("gloo")
     steps = a.steps if a.steps is not None else 5
@@ -577,8 +602,12 @@ def main():
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
     ap.add_argument("--mode", default="replicas", choices=["replicas", "sharded"])
     ap.add_argument("--n", type=int, default=None, help="override the configuration's N (development)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: configs, cpu_baseline, sustained, per-stage "
+                                                         "HIP-event figures, the Gram kernel alone, the sharded probes at N > 1")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--sustained", type=int, default=200, help="steps of the longer sample taken behind the timed region of the headline configuration (0: none)")
+    ap.add_argument("--sustained", type=int, default=None, help="steps of the longer sample taken behind the timed region of the headline configuration "
+                                                                "(0: none; default 200 with --full, 0 without)")
     ap.add_argument("--no-configs", action="store_true", help="skip the `configs` object (cfg3 / cfg4 / cfg5 on this GPU)")
     ap.add_argument("--shard-probe", action="store_true", help="also run the sharded probes at --gpus 1 (1-rank RCCL group)")
     ap.add_argument("--no-shard-probe", action="store_true")
@@ -602,6 +631,9 @@ def main():
     big = a.config != "cfg2"
     steps = a.steps if a.steps is not None else (5 if big else 20)
     warmup = a.warmup if a.warmup is not None else (1 if big else 3)
+    if steps < 1 or warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    sustained_steps = a.sustained if a.sustained is not None else (200 if a.full else 0)
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -619,10 +651,10 @@ def main():
             sys.exit(2)
     sharded_mode = a.mode == "sharded"       # exact / predict: one evaluation's tiles over the ranks; titsias: its data points over the ranks
 
-    # ---- the sharded probes FIRST (N > 1, replicas mode): nothing of this process is on the GPU yet, every probe is a group of child
+    # ---- the sharded probes FIRST (N > 1 with --full, replicas mode): nothing of this process is on the GPU yet, every probe is a group of child
     # ---- processes with a watchdog of its own; a probe that hangs is killed and the line goes on
     sharded = None
-    want_probe = (world > 1 or a.shard_probe) and not a.no_shard_probe and kind == "exact" and not sharded_mode
+    want_probe = ((world > 1 and a.full) or a.shard_probe) and not a.no_shard_probe and kind == "exact" and not sharded_mode
     if want_probe:
         base_port = int(os.environ.get("MASTER_PORT", "29655")) + 20
         names = [n for n in a.probes.split(",") if n and not (n == "cfg5_weak" and world == 1)]
@@ -640,7 +672,12 @@ def main():
     from mogptk_amd import _lib
 
     m, run_step, algo_flops = build_model(a.config, local_rank, a.n)
-    train_step = training_step(m, run_step, kind)
+    last = {}
+
+    def run_and_keep():
+        last["out"] = run_step()
+
+    train_step = training_step(m, run_and_keep, kind)
 
     def sync():
         if torch.cuda.is_available():
@@ -663,10 +700,10 @@ def main():
         run_step()
     stage = np.zeros(_lib.ST_COUNT)
     acc = dict(flops=0.0, launches=0, nprof=0)
-    PROFILE_EVERY = max(20, steps)          # HIP events around every GEMM launch cost ~5 % of a step: ONE timed step (the first) carries them
+    PROFILE_EVERY = max(20, steps)          # HIP events around every GEMM launch cost ~5 % of a step: with --full ONE timed step (the first) carries them
 
     def step(i):
-        prof = i >= 0 and (i % PROFILE_EVERY) == 0 and kind == "exact" and not sharded_mode
+        prof = a.full and i >= 0 and (i % PROFILE_EVERY) == 0 and kind == "exact" and not sharded_mode
         h.set_profiling(prof)
         train_step()
         if prof:
@@ -680,22 +717,24 @@ def main():
     dt = timed_region(step, steps, warmup, dist, sync, "cuda" if dist is not None else "cpu", per_step=step_times)
     gemm_flops, gemm_launches, nprof = acc["flops"], acc["launches"], max(acc["nprof"], 1)
     h.set_profiling(False)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, kind, last["out"], m)
     # a longer sample of the same step right behind the timed region (the chip's clocks take tens of ms of load to settle, and K = 20 steps of
     # configs[1] are 0.2 s): reported beside `value`, never instead of it
     sustained = None
-    if a.sustained > 0 and not big and not sharded_mode:
+    if sustained_steps > 0 and not big and not sharded_mode:
         sus_times = []
-        dts = timed_region(lambda i: train_step(), a.sustained, 0, dist, sync, "cuda" if dist is not None else "cpu", per_step=sus_times)
-        sustained = {"steps": a.sustained, "ms_per_step": 1e3 * dts / a.sustained, "value": aggregate_value(world, a.sustained, dts),
+        dts = timed_region(lambda i: train_step(), sustained_steps, 0, dist, sync, "cuda" if dist is not None else "cpu", per_step=sus_times)
+        sustained = {"steps": sustained_steps, "ms_per_step": 1e3 * dts / sustained_steps, "value": aggregate_value(world, sustained_steps, dts),
                      "median_ms_per_step": 1e3 * float(np.median(sus_times)), "max_ms_per_step": 1e3 * float(np.max(sus_times)),
-                     "note": "the same step, %d more times behind the timed region" % a.sustained}
+                     "note": "the same step, %d more times behind the timed region" % sustained_steps}
     # the Gram tile kernel BY ITSELF: inside the gradient evaluation's dataflow schedule it is two launches, the larger one on the bulk stream underneath the first
     # chain kernel and next to the resident dataflow kernel's polling workgroups (which is where it is hidden, and why its duration there -- gram_kernel in
     # stages_ms_per_eval -- says little about the kernel); an LML-only evaluation builds the same matrix in ONE launch with nothing beside it
     gram_alone_ms = None
     # (how the LAST evaluation was scheduled is read here, behind the timed steps: the LML-only evaluations below are not gradient evaluations)
     sched_timed = h.schedule() if (kind in ("exact", "predict") and not sharded_mode and hasattr(h, "schedule")) else None
-    if rank == 0 and kind == "exact" and not sharded_mode and hasattr(m, "log_marginal_likelihood"):
+    if a.full and rank == 0 and kind == "exact" and not sharded_mode and hasattr(m, "log_marginal_likelihood"):
         try:
             h.set_profiling(True)
             ts = []
@@ -849,8 +888,8 @@ def main():
             out["sharded"] = sharded
             out["sharded_cfg3"] = sharded_headline(sharded, world)
 
-    # ---- the other configurations on this GPU, then the CPU baseline: outside the timed region, rank 0 at N = 1 only -----------------------
-    if rank == 0 and world == 1 and not sharded_mode and a.config == "cfg2" and not a.n:
+    # ---- --full: the other configurations on this GPU, then the CPU baseline: outside the timed region, rank 0 at N = 1 only --------------
+    if a.full and rank == 0 and world == 1 and not sharded_mode and a.config == "cfg2" and not a.n:
         if not a.no_configs:
             h.close()                   # the headline model's 1.5 GB of workspaces are not needed any more
             out["configs"] = extra_configs(local_rank)
@@ -860,7 +899,7 @@ def main():
                 out["cpu_baseline"].update(cpu_identity())
             except Exception as e:      # the baseline is a report, never a reason to lose the GPU measurement
                 out["cpu_baseline"] = {"value": None, "error": repr(e)}
-    elif rank == 0 and world == 1 and not a.no_cpu_baseline and not sharded_mode:
+    elif a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not sharded_mode:
         out["cpu_baseline"] = {"value": None, "note": "cpu_baseline is timed on the headline configuration (cfg2) only; reference CPU timings of the "
                                                       "other configurations are in BASELINE.md / DESIGN.md section 5"}
 

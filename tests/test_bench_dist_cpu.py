@@ -93,7 +93,7 @@ def test_plain_process_launches_its_own_ranks():
     print n_gpus 1: it starts the two ranks itself.  --selftest keeps the GPU out of it (gloo ranks, a sleeping step, the `dummy` probe)."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--selftest", "--steps", "3", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--selftest", "--full", "--steps", "3", "--warmup", "1"],
                          capture_output=True, text=True, timeout=300, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -102,6 +102,20 @@ def test_plain_process_launches_its_own_ranks():
     assert r["n_gpus"] == 2 and r["steps"] == 3 and r["config"]["self_launched"] is True
     assert r["rccl_ranks"] == 2 and r["sharded"]["dummy"]["rank_sum_ok"] is True      # the probe's child group spanned both ranks
     assert abs(r["value"] - 2 * 3 / (r["ms_per_step"] * 3e-3)) < 1e-6 * r["value"]
+
+
+def test_plain_run_starts_no_probe():
+    """without --full the N > 1 line is the timed steps alone: no sharded probe runs before them"""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--selftest", "--steps", "4", "--warmup", "0"],
+                         capture_output=True, text=True, timeout=300, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    r = json.loads(lines[0])
+    assert r["n_gpus"] == 2 and r["steps"] == 4 and r["warmup"] == 0
+    assert "sharded" not in r and "rccl_ranks" not in r, r
 
 
 def test_more_gpus_than_the_node_has_is_an_error_with_a_reason():

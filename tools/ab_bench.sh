@@ -2,7 +2,7 @@
 # A/B of the headline bench line under environment variants: usage (gpurun): bash tools/ab_bench.sh "VAR=val VAR2=val" "..." ...   (one quoted string per variant; "" = defaults)
 cd $GRAFT_REPO_ROOT
 for v in "$@"; do
-  out=$(env $v python bench.py --no-cpu-baseline --no-configs --no-shard-probe 2>/dev/null | tail -1)
+  out=$(env $v python bench.py --full --no-cpu-baseline --no-configs --no-shard-probe 2>/dev/null | tail -1)
   python - "$v" <<PY
 import json, sys
 d = json.loads('''$out''')
