@@ -57,8 +57,16 @@ int  mogp_ctx_device_name(mogp_ctx* ctx, char* buf, int buflen);
  * of :435 is NOT materialised).  X: N x (1+D), y: N.  C = number of channels (kernel.output_dims). */
 int  mogp_model_create(mogp_ctx* ctx, int64_t N, int D, int C, const double* X, const double* y, mogp_model** out);
 int  mogp_model_destroy(mogp_model* m);
-/* replace y (e.g. y - mean(X), gpr/model.py:445-448) */
+/* replace y (e.g. y - mean(X), gpr/model.py:445-448).  With a mean table set (below) these are the RAW targets and the residual follows. */
 int  mogp_model_set_y(mogp_model* m, const double* y);
+/* Trainable mean function (reference gpr/mean.py ConstantMean / LinearMean / MultiOutputMean, subtracted at gpr/model.py:445-448, :518-519,
+ * :701-702): coef is a C x (1 + D) table, row c = [b_c, s_c,1 .. s_c,D], and m(x) = b_c + sum_d s_c,d x_d for a point x of channel c.  The
+ * exact, Titsias and Snelson evaluations and predictions then see y - m(X) in place of y (computed on the device, again only when the table or
+ * the targets change); y stays what mogp_model_create / mogp_model_set_y gave.  NULL: no mean, no extra launch and no extra memory. */
+int  mogp_model_set_mean(mogp_model* m, const double* coef);
+/* g (C x (1 + D)) of the last MOGP_EVAL_GRAD evaluation (exact, Titsias, Snelson) under the table: g[c][j] = sum_{k in c} dp/dr_k [1, x_k][j],
+ * r = y - m(X), p the LML or ELBO -- which is d(-p)/d coef, the table's share of the autograd backward of gpr.Model.loss() (gpr/model.py:279-292). */
+int  mogp_model_mean_grad(mogp_model* m, double* g);
 
 /* Unified spectral term table: every MOSM / SM / CSM channel-pair block is
  *   K_ab = sum_t A exp(-1/2 sum_d V_d u_d^2) cos(2 pi (sum_d M_d u_d + Psi)),  u_d = x_a,d - x_b,d + Delta_d.
@@ -301,7 +309,10 @@ int  mogp_flow_trace(mogp_model* m, int64_t* out, int64_t cap, int64_t* count);
 
 /* copy device-resident matrices of the last eval back (tests / CholeskyException payload):
  * which: 0 = W = L^-1, inverse of the lower Cholesky factor of Kj, in CHANNEL-SORTED row order (after any eval), 1 = Kj^-1 (after MOGP_EVAL_GRAD),
- *        2 = alpha (N).  Output in the caller's original row order, full N x N (symmetrised / lower-filled). */
+ *        2 = alpha (N), 3 = dp/dr (N), r = y - m(X), of a MOGP_EVAL_GRAD evaluation of the exact, Titsias or Snelson model when it was the
+ *        LAST evaluation or prediction on the handle (any later one ends it: EINVAL) -- the vector a mean function's own backward needs (it
+ *        replaces autograd through mean(self.X), gpr/model.py:445-448).
+ *        Output in the caller's original row order, full N x N (symmetrised / lower-filled). */
 int  mogp_model_fetch(mogp_model* m, int which, double* out);
 
 /* The pseudo-input sparse GP of Snelson & Ghahramani (FITC) on the model's data: reference gpr/model.py:516-541

@@ -40,6 +40,8 @@ SIGNATURES = {
                                          ctypes.POINTER(ctypes.c_void_p)]),
     "mogp_model_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "mogp_model_set_y": (ctypes.c_int, [ctypes.c_void_p, c_dp]),
+    "mogp_model_set_mean": (ctypes.c_int, [ctypes.c_void_p, c_dp]),
+    "mogp_model_mean_grad": (ctypes.c_int, [ctypes.c_void_p, c_dp]),
     "mogp_model_set_terms": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_dp]),
     "mogp_model_set_terms_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_dp]),
     "mogp_model_set_point_diag": (ctypes.c_int, [ctypes.c_void_p, c_dp]),
@@ -243,6 +245,21 @@ class ExactHandle:
     def set_y(self, y):
         y = _f64(np.asarray(y).reshape(-1))
         check(lib().mogp_model_set_y(self._h, _dp(y)))
+
+    def set_mean(self, coef):
+        """the affine mean table (C x (1 + D)), or None for no mean; the device recomputes the residual only when the table changed"""
+        if coef is None:
+            check(lib().mogp_model_set_mean(self._h, None))
+            return
+        coef = _f64(coef)
+        assert coef.shape == (self.C, 1 + self.D)
+        check(lib().mogp_model_set_mean(self._h, _dp(coef)))
+
+    def mean_grad(self):
+        """g = d loss / d table of the last gradient evaluation, (C, 1 + D)"""
+        g = np.empty((self.C, 1 + self.D))
+        check(lib().mogp_model_mean_grad(self._h, _dp(g)))
+        return g
 
     def set_terms(self, table):
         table = _f64(table)
@@ -554,6 +571,6 @@ class ExactHandle:
         return float(f[0])
 
     def fetch(self, which):
-        out = np.empty(self.N if which == 2 else (self.N, self.N))
+        out = np.empty(self.N if which in (2, 3) else (self.N, self.N))
         check(lib().mogp_model_fetch(self._h, which, _dp(out)))
         return out

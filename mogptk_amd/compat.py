@@ -315,6 +315,23 @@ def _convert_likelihood(bag, variational=False):
     return lik
 
 
+# ---- mean functions (reference gpr/mean.py) -----------------------------------------------------------------------------------------
+def _convert_mean(bag):
+    """the built-in means; a MultiOutputMean's sub-means sit in a plain list attribute, not among its modules (quirk Q8): they are rebuilt
+    and given their values here, outside the model's parameter list"""
+    name, st = bag.cls(), bag.state()
+    if name == "ConstantMean":
+        return _gpr.ConstantMean()
+    if name == "LinearMean":
+        return _gpr.LinearMean(int(st["_parameters"]["slope"].data.shape[0]))
+    if name == "MultiOutputMean":
+        subs = [_convert_mean(b) for b in st["means"]]
+        for ours, b in zip(subs, st["means"]):
+            _assign_parameters(list(ours.parameters()), _module_parameters(b))
+        return _gpr.MultiOutputMean(*subs)
+    raise NotImplementedError("checkpoint uses the mean function %s; only ConstantMean, LinearMean and MultiOutputMean are converted" % name)
+
+
 # ---- the model -----------------------------------------------------------------------------------------------------------------------
 def _convert_model(bag):
     from . import model as _model
@@ -322,8 +339,10 @@ def _convert_model(bag):
     st = bag.state()
     dataset = _convert_dataset(st["dataset"])
     g = st["gpr"].state()
-    if g.get("mean") is not None:
+    if g.get("mean") is not None:                       # (a torch.nn.Module assigned to the model lives in _modules, below; this is anything else)
         raise NotImplementedError("the checkpoint's model has a mean function object of the reference; not converted")
+    mean_bag = g.get("_modules", {}).get("mean")
+    mean = None if mean_bag is None else _convert_mean(mean_bag)
     inference_name = st["gpr"].cls()
     lik = g["_modules"]["likelihood"]
     if lik.cls() != "GaussianLikelihood" and inference_name not in ("SparseHensman", "Hensman", "OpperArchambeau"):
@@ -351,7 +370,7 @@ def _convert_model(bag):
         raise NotImplementedError("inference %s is not part of this package" % inference_name)
     kernel = _convert_kernel(g["_modules"]["kernel"])
     wrapper = getattr(_wrappers, bag.cls(), None)
-    m = _model.Model(dataset, kernel, inference=inference, name=st.get("name"))
+    m = _model.Model(dataset, kernel, inference=inference, mean=mean, name=st.get("name"))
     if wrapper is not None:                                  # MOSM / SM / CSM / SM_LMC / CONV / MOHSM: same class, same extra attributes
         m.__class__ = wrapper
         for key in ("Q", "Rq", "P"):
@@ -388,7 +407,8 @@ def load_reference_model(source):
 # their methods expect after `pickle.load` (no __init__ runs on that side: everything an __init__ would have set has to be in the state --
 # the dense identity `eye`, the quadrature nodes of the likelihood, torch.nn.Module's registries).  A small pickler writes the global
 # references and object states directly, so nothing is registered in sys.modules and no class of the reference is needed here; tensors are
-# written by torch itself.  Scope: Exact and Titsias inference with a Gaussian likelihood and no mean function, the kernels of the six model
+# written by torch itself.  Scope: Exact and Titsias inference with a Gaussian likelihood and no mean function or a built-in one (ConstantMean,
+# LinearMean, MultiOutputMean), the kernels of the six model
 # wrappers (and sums / products of them), the Y transformers.  Anything else raises NotImplementedError naming the object.
 # ======================================================================================================================================
 class _Global:
@@ -513,6 +533,17 @@ class _Exporter:
             mods.append(("kernels", self.module_list([self.kernel(s) for s in k.kernels])))
         return _Obj(_Global("mogptk.gpr." + where, name), _module_state(own, self.own_parameters(k), mods))
 
+    def mean(self, m):
+        """reference gpr/mean.py: torch.nn.Module state with the parameters; a MultiOutputMean keeps `output_dims` and its sub-means in a plain
+        list (quirk Q8)"""
+        name = type(m).__name__
+        if type(m) not in (_gpr.ConstantMean, _gpr.LinearMean, _gpr.MultiOutputMean):
+            raise NotImplementedError("the checkpoint writer covers ConstantMean, LinearMean and MultiOutputMean, not %s" % name)
+        own = {}
+        if name == "MultiOutputMean":
+            own = {"output_dims": int(m.output_dims), "means": [self.mean(s) for s in m.means]}
+        return _Obj(_Global("mogptk.gpr.mean", name), _module_state(own, self.own_parameters(m)))
+
     def likelihood(self, lik):
         if type(lik) is not _gpr.GaussianLikelihood:
             raise NotImplementedError("the checkpoint writer covers the Gaussian likelihood only, not %s" % type(lik).__name__)
@@ -526,8 +557,12 @@ class _Exporter:
         name = type(g).__name__
         if type(g) not in (_gpr.Exact, _gpr.Titsias):
             raise NotImplementedError("the checkpoint writer covers Exact and Titsias inference, not %s" % name)
-        if g.mean is not None:
-            raise NotImplementedError("mean functions are not written")
+        mods = [("kernel", self.kernel(g.kernel))]
+        if g.mean is not None:                                   # reference gpr/model.py:115: a Mean is a module, registered between kernel and likelihood
+            if not isinstance(g.mean, _gpr.Mean):
+                raise NotImplementedError("a mean function that is not a gpr.Mean is not written")
+            mods.append(("mean", self.mean(g.mean)))
+        mods.append(("likelihood", self.likelihood(g.likelihood)))
         X = np.asarray(g.X, dtype=np.float64)
         own, first = {}, {}
         if name == "Exact":
@@ -537,6 +572,8 @@ class _Exporter:
             first["data_variance"] = None if dv is None else self.torch.diagflat(self.tensor(np.reshape(dv, -1)))
         own.update({"X": self.tensor(X), "y": self.tensor(np.reshape(g.y, (-1, 1))), "mean": None, "jitter": float(g.jitter),
                     "input_dims": int(X.shape[1]), "_compiled_forward": None})
+        if g.mean is not None:
+            del own["mean"]
         pars = []
         if name == "Titsias":
             own["eye"] = self.torch.eye(g.Z.data.shape[0], dtype=self.torch.float64)
@@ -545,7 +582,7 @@ class _Exporter:
             own["eye"] = self.torch.eye(X.shape[0], dtype=self.torch.float64)
         own["log_marginal_likelihood_constant"] = np.float64(0.5 * X.shape[0] * np.log(2.0 * np.pi))
         return _Obj(_Global("mogptk.gpr.model", name),
-                    _module_state(own, pars, [("kernel", self.kernel(g.kernel)), ("likelihood", self.likelihood(g.likelihood))], first))
+                    _module_state(own, pars, mods, first))
 
     def transformer(self, t):
         name = type(t).__name__

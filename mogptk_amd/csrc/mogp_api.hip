@@ -1258,6 +1258,7 @@ static int moment_pass_device(mogp_model* m, const double* kinv, double ksign) {
     if ((rc = launch_moments(ma, m->st))) return rc;
     if ((rc = launch_moment_reduce(m->d_partial.p, own ? m->d_pair_start_own.p : m->d_pair_start.p, P, T, W, D, m->d_moments.p, m->st))) return rc;
     if ((rc = launch_diagG(kinv, Npad, m->d_alpha.p, m->d_chan_off.p, C, m->d_diagG.p, m->st, ksign, rm, m->sh_rank))) return rc;
+    if ((rc = mean_grad_enqueue(m, m->d_alpha.p, -1.0))) return rc;            // dp/dr = -alpha (nothing is launched without a mean table)
     return mark(m, 6);
 }
 
@@ -1395,6 +1396,7 @@ int mogp_model_destroy(mogp_model* m) {
     m->d_Kss.release(); m->d_ptiles.release(); m->d_pred_tasks.release();
     m->ph_xx.release(); m->ph_sx.release(); m->ph_ss.release();
     if (m->h_pin) { hipError_t e = hipHostFree(m->h_pin); (void)e; m->h_pin = nullptr; }
+    mean_release(m);
 
     delete m;
     return MOGP_OK;
@@ -1406,6 +1408,12 @@ int mogp_model_set_y(mogp_model* m, const double* y) {
     if ((rc = use_device(m->ctx))) return rc;
     std::vector<double> ys(m->Npad, 0.0);
     for (int64_t pos = 0; pos < m->N; ++pos) ys[pos] = y[m->sx.perm[pos]];
+    if (m->mean_on) {                           // the raw targets change under a mean table: the residual follows (mean.hip)
+        HIP_TRY(dev_upload(m->d_y0.p, ys.data(), m->Npad * sizeof(double)));
+        m->hy0 = ys;
+        m->mean_g_valid = m->mean_g_pending = false;
+        return mean_apply(m);
+    }
     HIP_TRY(dev_upload(m->d_y.p, ys.data(), m->Npad * sizeof(double)));
     m->hy = ys;
     return MOGP_OK;
@@ -1447,6 +1455,7 @@ int mogp_model_set_point_diag(mogp_model* m, const double* kdiag) {
 
 int mogp_exact_eval(mogp_model* m, const double* noise_var, const double* data_var, double jitter, int flags,
                     double* lml, double* moments, double* diagG, double* trG, double* jitter_abs, int64_t* info) {
+    if (m) m->mean_w = nullptr;                 // dp/dr of an earlier gradient evaluation: this call may overwrite or regrow its buffer (mogp_model_fetch 3)
     if (!m) return fail(MOGP_EINVAL, "mogp_exact_eval: model is null");
     int rc;
     if ((rc = use_device(m->ctx))) return rc;
@@ -1515,6 +1524,7 @@ int mogp_exact_eval(mogp_model* m, const double* noise_var, const double* data_v
     *trG = tr;
     m->have_Kinv = true;
     m->kinv_in_A = sweep;
+    mean_grad_collect(m);
     collect_timing(m, 6);
     return MOGP_OK;
 }
@@ -1524,6 +1534,7 @@ int mogp_exact_eval(mogp_model* m, const double* noise_var, const double* data_v
 static int predict_core(mogp_model* m, const double* noise_var, const double* data_var, double jitter,
                         const double* kss_diag, int64_t S, const double* Xs, int full,
                         double* mu, double* var, int64_t* info, const double* mean_w) {
+    if (m) m->mean_w = nullptr;                 // dp/dr of an earlier gradient evaluation: this call may overwrite or regrow its buffer (mogp_model_fetch 3)
     int rc;
     if ((rc = use_device(m->ctx))) return rc;
     if (info) *info = 0;
@@ -1840,6 +1851,7 @@ int mogp_model_work_bytes(mogp_model* m, int64_t* backed, int64_t* whole) {
 }
 
 int mogp_shard_begin(mogp_model* m, const double* noise_var, const double* data_var, double jitter, double* jitter_abs, int* nblocks) {
+    if (m) m->mean_w = nullptr;                 // dp/dr of an earlier gradient evaluation: this call may overwrite or regrow its buffer (mogp_model_fetch 3)
     if (!m || !nblocks) return fail(MOGP_EINVAL, "mogp_shard_begin: bad argument");
     int rc;
     if ((rc = use_device(m->ctx))) return rc;
@@ -1960,6 +1972,7 @@ static int sharded_inverse(mogp_model* m, const double* noise_var, const double*
 
 int mogp_exact_eval_sharded(mogp_model* m, const double* noise_var, const double* data_var, double jitter,
                             double* lml, double* moments, double* diagG, double* trG, double* jitter_abs, int64_t* info) {
+    if (m) m->mean_w = nullptr;                 // dp/dr of an earlier gradient evaluation: this call may overwrite or regrow its buffer (mogp_model_fetch 3)
     if (!m || !lml || !moments || !diagG || !trG) return fail(MOGP_EINVAL, "mogp_exact_eval_sharded: bad argument");
     int rc;
     if ((rc = use_device(m->ctx))) return rc;
@@ -2219,6 +2232,13 @@ int mogp_model_fetch(mogp_model* m, int which, double* out) {
     int rc;
     if ((rc = use_device(m->ctx))) return rc;
     const int64_t N = m->N, Npad = m->Npad;
+    if (which == 3) {                           // dp/dr of the last gradient evaluation (Exact, Titsias, Snelson): what a user mean's backward needs
+        if (!m->mean_w) return fail(MOGP_EINVAL, "mogp_model_fetch: dp/dr needs a gradient evaluation of the exact, Titsias or Snelson model as the last call on the handle");
+        std::vector<double> h(Npad);
+        HIP_TRY(hipMemcpy(h.data(), m->mean_w, Npad * sizeof(double), hipMemcpyDeviceToHost));
+        for (int64_t pos = 0; pos < N; ++pos) out[m->sx.perm[pos]] = m->mean_w_scale * h[pos];
+        return MOGP_OK;
+    }
     if (which == 2) {
         if (!m->have_W && !m->have_Kinv) return fail(MOGP_EINVAL, "mogp_model_fetch: no evaluation has completed yet");
         std::vector<double> h(Npad);
@@ -2228,7 +2248,7 @@ int mogp_model_fetch(mogp_model* m, int which, double* out) {
     }
     if (which == 0 && !m->have_W) return fail(MOGP_EINVAL, "mogp_model_fetch: no evaluation has completed yet");
     if (which == 1 && !m->have_Kinv) return fail(MOGP_EINVAL, "mogp_model_fetch: Kj^-1 needs an evaluation with MOGP_EVAL_GRAD");
-    if (which != 0 && which != 1) return fail(MOGP_EINVAL, "mogp_model_fetch: which must be 0, 1 or 2");
+    if (which != 0 && which != 1) return fail(MOGP_EINVAL, "mogp_model_fetch: which must be 0, 1, 2 or 3");
     if (m->k.owned_rows) return fail(MOGP_EINVAL, "mogp_model_fetch: this rank of a sharded evaluation holds only its own tile rows of the matrix");
     if (which == 1 && m->kinv_sparse && !m->kinv_in_A) {
         // the evaluation formed only the tiles of Kj^-1 its gradient reads (kinv_plan): form all of them now, W^T W from the W it left

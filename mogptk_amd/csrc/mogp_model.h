@@ -407,6 +407,15 @@ struct mogp_model {
     bool no_chain = false;              // the persistent chain kernel timed out once on this model (another process's chain kernel held the reserved CUs): launch-per-step chain from now on
     TitsiasWork* tw = nullptr;
     OaWork oa;
+
+    // trainable mean (mean.hip, mogp_model_set_mean): with a table set, d_y / hy hold the residual y0 - m(X) and d_y0 / hy0 the raw targets
+    bool mean_on = false, mean_g_valid = false, mean_g_pending = false;
+    std::vector<double> mean_coef, mean_g, hy0;         // C x (1 + D) table; its gradient from the last gradient evaluation; raw targets (host, sorted)
+    DevBuf<double> d_y0, d_mean_coef, d_mean_part, d_mean_g;
+    double* h_mean_pin = nullptr;                       // pinned: the gradient's copy rides behind the evaluation's own on the same stream
+    hipEvent_t mean_ev = nullptr;                       // the residual is in d_y (other streams wait for it)
+    const double* mean_w = nullptr;                     // dp/dr of the last gradient evaluation (device, channel-sorted) is mean_w_scale * mean_w
+    double mean_w_scale = 0.0;
 };
 
 
@@ -416,6 +425,10 @@ int gemm_call(mogp_model* m, const GemmArgs& g, double flops, hipStream_t st = n
 int mark(mogp_model* m, int idx);
 double table_diag(const mogp_model* m, int c);
 double table_diag_points(const mogp_model* m, const SortedX& pts);      // sum of K(x, x) over the points (per point when the terms carry an envelope)
+int mean_apply(mogp_model* m);                                             // mean.hip: residual into d_y / hy after a new table or new targets
+int mean_grad_enqueue(mogp_model* m, const double* w, double scale);       // dp/dr = scale * w (device, sorted): records it, and queues g on m->st
+void mean_grad_collect(mogp_model* m);                                     // after the evaluation's wait: g to the host copy
+void mean_release(mogp_model* m);
 int spd_alloc(Spd& w, int64_t Npad, int owned_rows_device = -1);   // >= 0: the owned-rows form (A reserved on that device, nothing backed yet, no B)
 int spd_make_whole(Spd& w);           // an owned-rows workspace becomes an ordinary one (every granule of A backed, B allocated)
 // helpers shared by the sparse / variational models (titsias.hip)

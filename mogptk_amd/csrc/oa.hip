@@ -86,6 +86,7 @@ int upload_sorted(mogp_model* m, const double* src, double* dst, double pad) {
 extern "C" {
 
 int mogp_oa_forward(mogp_model* m, const double* q_nu, const double* q_lambda, double* mu, double* var, double* kl, int64_t* info) {
+    if (m) m->mean_w = nullptr;                 // dp/dr of an earlier gradient evaluation: this call may overwrite or regrow its buffer (mogp_model_fetch 3)
     if (!m || !q_nu || !q_lambda || !mu || !var || !kl) return fail(MOGP_EINVAL, "mogp_oa_forward: bad argument");
     RC(use_device(m->ctx));
     if (info) *info = 0;
@@ -168,6 +169,7 @@ int mogp_oa_forward(mogp_model* m, const double* q_nu, const double* q_lambda, d
 }
 
 int mogp_oa_backward(mogp_model* m, const double* e, const double* f, double* moments, double* g_nu, double* g_lambda) {
+    if (m) m->mean_w = nullptr;                 // dp/dr of an earlier gradient evaluation: this call may overwrite or regrow its buffer (mogp_model_fetch 3)
     if (!m || !e || !f || !moments || !g_nu || !g_lambda) return fail(MOGP_EINVAL, "mogp_oa_backward: bad argument");
     RC(use_device(m->ctx));
     OaWork& o = m->oa;

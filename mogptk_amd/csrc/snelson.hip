@@ -247,6 +247,7 @@ int snelson_front(mogp_model* m, int64_t M, const double* Z, const double* noise
 int snelson_eval_impl(mogp_model* m, int64_t M, const double* Z, const double* noise_var, double jitter, const double* kff_diag, int flags,
                       double* lml, double* mom_uu, double* mom_uf, double* gZ, double* trGA, double* hsum, double* jitter_abs, int64_t* info,
                       bool sharded) {
+    if (m) m->mean_w = nullptr;                 // dp/dr of an earlier gradient evaluation: this call may overwrite or regrow its buffer (mogp_model_fetch 3)
     if (!m || !Z || !noise_var || !kff_diag || !lml || M <= 0) return fail(MOGP_EINVAL, "mogp_snelson_eval: bad argument");
     RC(use_device(m->ctx));
     if (info) *info = 0;
@@ -354,8 +355,10 @@ int snelson_eval_impl(mogp_model* m, int64_t M, const double* Z, const double* n
     HIP_TRY(hipMemcpyAsync(hb.data(), beta, Mpad * sizeof(double), hipMemcpyDeviceToHost, m->st));
     HIP_TRY(hipMemcpyAsync(hd.data(), dga, Mpad * sizeof(double), hipMemcpyDeviceToHost, m->st));
     HIP_TRY(hipMemcpyAsync(hh.data(), h, Npad * sizeof(double), hipMemcpyDeviceToHost, m->st));
+    RC(mean_grad_enqueue(m, alpha, -1.0));                  // dp/dy = -(Qff + Lambda)^-1 y = -alpha (Woodbury, k_sn_alpha)
     HIP_TRY(hipStreamSynchronize(m->st));
     RC(sparse_timeout_check(m));
+    mean_grad_collect(m);
     for (int64_t pos = 0; pos < M; ++pos)
         for (int d = 0; d < D; ++d) gZ[sz.perm[pos] * D + d] = hgz[(size_t)d * Mpad + pos];
     double tr = 0.0;
@@ -415,6 +418,7 @@ namespace {
 
 int snelson_predict_impl(mogp_model* m, int64_t M, const double* Z, const double* noise_var, double jitter, const double* kff_diag,
                          const double* kss_diag, int64_t S, const double* Xs, double* mu, double* var, int64_t* info, bool sharded) {
+    if (m) m->mean_w = nullptr;                 // dp/dr of an earlier gradient evaluation: this call may overwrite or regrow its buffer (mogp_model_fetch 3)
     if (!m || !Z || !noise_var || !kff_diag || !kss_diag || !Xs || !mu || !var || M <= 0 || S <= 0)
         return fail(MOGP_EINVAL, "mogp_snelson_predict: bad argument");
     RC(use_device(m->ctx));

@@ -115,6 +115,7 @@ extern "C" {
 int mogp_svgp_forward(mogp_model* m, int64_t M, const double* Z, const double* q_mu, const double* q_sqrt, double jitter,
                       const double* kff_diag, int dense, int64_t S, const double* Xs, const double* kss_diag,
                       double* mu, double* var, double* jitter_abs, int64_t* info) {
+    if (m) m->mean_w = nullptr;                 // dp/dr of an earlier gradient evaluation: this call may overwrite or regrow its buffer (mogp_model_fetch 3)
     if (!m || !Z || !q_mu || !q_sqrt || !kff_diag || !mu || !var || M <= 0) return fail(MOGP_EINVAL, "mogp_svgp_forward: bad argument");
     if (S > 0 && (!Xs || !kss_diag)) return fail(MOGP_EINVAL, "mogp_svgp_forward: test inputs without Xs / kss_diag");
     RC(use_device(m->ctx));
@@ -208,6 +209,7 @@ int mogp_svgp_forward(mogp_model* m, int64_t M, const double* Z, const double* q
 // M x M products over N, v e, the (Z, X) moments and their share of d/dZ -- is all-reduced; e, f are those of the local points
 static int svgp_backward_impl(mogp_model* m, const double* e, const double* f, double* mom_uu, double* mom_uf, double* gZ, double* trGA,
                               double* g_qmu, double* g_qsqrt, bool sharded) {
+    if (m) m->mean_w = nullptr;                 // dp/dr of an earlier gradient evaluation: this call may overwrite or regrow its buffer (mogp_model_fetch 3)
     if (!m || !e || !f || !mom_uu || !mom_uf || !gZ || !trGA || !g_qmu || !g_qsqrt) return fail(MOGP_EINVAL, "mogp_svgp_backward: bad argument");
     RC(use_device(m->ctx));
     if (!m->tw || !m->tw->sv_valid) return fail(MOGP_EINVAL, "mogp_svgp_backward: no forward pass at the training inputs precedes it");

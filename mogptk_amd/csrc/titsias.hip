@@ -332,6 +332,7 @@ static int titsias_front(mogp_model* m, int64_t M, const double* Z, double sigma
 static int titsias_eval_impl(mogp_model* m, int64_t M, const double* Z, double sigma, double jitter, const double* kff_diag, int flags,
                              double* elbo, double* mom_uu, double* mom_uf, double* gZ, double* trGA, double* dsigma,
                              double* jitter_abs, int64_t* info, bool sharded) {
+    if (m) m->mean_w = nullptr;                 // dp/dr of an earlier gradient evaluation: this call may overwrite or regrow its buffer (mogp_model_fetch 3)
     if (!m || !Z || !kff_diag || !elbo || M <= 0) return fail(MOGP_EINVAL, "mogp_titsias_eval: bad argument");
     RC(use_device(m->ctx));
     if (info) *info = 0;
@@ -467,8 +468,11 @@ static int titsias_eval_impl(mogp_model* m, int64_t M, const double* Z, double s
     HIP_TRY(hipMemcpyAsync(hgz.data(), t.gz.p, hgz.size() * sizeof(double), hipMemcpyDeviceToHost, m->st));
     HIP_TRY(hipMemcpyAsync(hb.data(), beta, Mpad * sizeof(double), hipMemcpyDeviceToHost, m->st));
     HIP_TRY(hipMemcpyAsync(hd.data(), dga, Mpad * sizeof(double), hipMemcpyDeviceToHost, m->st));
+    // dELBO/dy = -(Qff + s2 I)^-1 y = -s2^-1 (y - s2^-1 v^T t1) = -s2 r  (Woodbury; r = s2^-2 y - s2^-3 B^T beta above, B^T beta = v^T t1)
+    RC(mean_grad_enqueue(m, r, -s2));
     HIP_TRY(hipStreamSynchronize(m->st));
     RC(sparse_timeout_check(m));
+    mean_grad_collect(m);
     for (int64_t pos = 0; pos < M; ++pos)
         for (int d = 0; d < D; ++d) gZ[sz.perm[pos] * D + d] = hgz[(size_t)d * Mpad + pos];
     double tr = 0.0;
@@ -533,6 +537,7 @@ int mogp_titsias_predict_sharded(mogp_model* m, int64_t M, const double* Z, doub
 
 static int titsias_predict_impl(mogp_model* m, int64_t M, const double* Z, double sigma, double jitter, const double* kss_diag,
                                 int64_t S, const double* Xs, double* mu, double* var, int64_t* info, bool sharded) {
+    if (m) m->mean_w = nullptr;                 // dp/dr of an earlier gradient evaluation: this call may overwrite or regrow its buffer (mogp_model_fetch 3)
     if (!m || !Z || !kss_diag || !Xs || !mu || !var || M <= 0 || S <= 0) return fail(MOGP_EINVAL, "mogp_titsias_predict: bad argument");
     RC(use_device(m->ctx));
     if (info) *info = 0;

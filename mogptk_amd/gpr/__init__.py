@@ -3,6 +3,7 @@ from .config import *
 from .config import config
 from .parameter import *
 from .likelihood import *
+from .mean import *
 from .kernel import *
 from .singleoutput import *
 from .multioutput import *

@@ -496,7 +496,7 @@ class Model:
             dataset (DataSet, Data): data of all channels.
             kernel (mogptk_amd.gpr.Kernel): the kernel.
             inference: inference model factory, e.g. `mogptk_amd.Exact()`.
-            mean: mean function hook (fixed functions only).
+            mean: a gpr.Mean (trained with the model: Exact, Titsias, Snelson) or a fixed callable.
             name (str): name of the model.
 
         Attributes:
@@ -534,6 +534,8 @@ class Model:
         s = "Model: %s\n" % self.gpr._get_name()
         s += "‣ Kernel: %s\n" % self.gpr.kernel.name()
         s += "‣ Likelihood: %s\n" % self.gpr.likelihood.name()
+        if isinstance(self.gpr.mean, gpr.Mean):
+            s += "‣ Mean: %s\n" % self.gpr.mean._get_name()
         s += "‣ Parameters: %d\n" % self.num_parameters()
         for p in self.gpr.parameters():
             s += "  - %s %s\n" % (p._name, p.shape)
@@ -657,6 +659,8 @@ class Model:
             print("‣ Model: %s" % self.gpr.name())
             print("  ‣ Kernel: %s" % self.gpr.kernel.name())
             print("  ‣ Likelihood: %s" % self.gpr.likelihood.name())
+            if isinstance(self.gpr.mean, gpr.Mean):
+                print("  ‣ Mean: %s" % self.gpr.mean.name())
             print("‣ Channels: %d" % len(self.dataset))
             print("‣ Parameters: %d" % self.num_parameters())
             print("‣ Training points: %d" % self.num_training_points())
