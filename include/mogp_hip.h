@@ -99,6 +99,23 @@ int  mogp_gram(mogp_ctx* ctx, int C, int D, int T, const double* table,
 int  mogp_gram_ex(mogp_ctx* ctx, int C, int D, int T, int width, const double* table,
                   int64_t M1, const double* X1, int64_t M2, const double* X2, double* K_out);
 
+/* Radial profiles of the stationary kernels (reference gpr/singleoutput.py: ExponentialKernel.K :206-211, SquaredExponentialKernel.K
+ * :252-263, RationalQuadraticKernel.K :307-318, MaternKernel.K :637-650): the Gaussian of a term generalised to
+ *   K_ab = sum_t A phi_kind(s) cos(2 pi (sum_d M_d u_d + Psi)),   s = sum_d V_d u_d^2,  r = sqrt(s),
+ *   kind 0  exp(-s/2)  (what mogp_model_set_terms alone means)      kind 1  (1 + s / (2 shape))^-shape   (rational quadratic)
+ *   kind 2  exp(-r)                                                  kind 3  (1 + sqrt(3) r) exp(-sqrt(3) r)
+ *   kind 4  (1 + sqrt(5) r + 5 r^2 / 3) exp(-sqrt(5) r)               (Matern 1/2, 3/2, 5/2; the reference's exponential kernel is kind 2)
+ * kind / shape: C x C x T each, entry [i][j][t] beside the table's; valid until the next mogp_model_set_terms of a DIFFERENT T.  NULL or all
+ * zero: Gaussian, and nothing of an evaluation changes.  With a non-zero kind the exact evaluation and prediction (mogp_exact_eval,
+ * mogp_exact_predict) build every Gram tile entry by entry and form the whole of Kj^-1; the gradient moments keep their layout and host
+ * formulas, with psi = -2 dphi/ds in place of phi in m1_d and m2_d (u_d^2 psi = u_d psi = 0 where kind 2 has r = 0).  Rows of width 2 + 3 D
+ * only.  The sparse, variational and sharded entry points do not take kinds: gpr/ refuses them before any call. */
+int  mogp_model_set_kinds(mogp_model* m, int T, const int* kind, const double* shape);
+/* mogp_gram_ex with kinds (NULL: mogp_gram_ex itself): replaces Kernel.K of the kernels above, and of their sums, IndependentMultiOutputKernel
+ * and LinearModelOfCoregionalizationKernel compositions (gpr/kernel.py:138-150, :232-246, gpr/multioutput.py:5-39, :456-502) */
+int  mogp_gram_kinds(mogp_ctx* ctx, int C, int D, int T, int width, const double* table, const int* kind, const double* shape,
+                     int64_t M1, const double* X1, int64_t M2, const double* X2, double* K_out);
+
 /* flags for mogp_exact_eval */
 #define MOGP_EVAL_GRAD   1   /* also compute the gradient moments */
 

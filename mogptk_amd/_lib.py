@@ -27,6 +27,7 @@ _live = weakref.WeakSet()             # open ExactHandles (shutdown() closes the
 
 c_dp = ctypes.POINTER(ctypes.c_double)
 c_i64p = ctypes.POINTER(ctypes.c_int64)
+c_ip = ctypes.POINTER(ctypes.c_int)
 
 # name -> (restype, argtypes); mirrors include/mogp_hip.h one to one (tests check every symbol is exported)
 SIGNATURES = {
@@ -49,6 +50,9 @@ SIGNATURES = {
                                     ctypes.c_int64, c_dp, ctypes.c_int64, c_dp, c_dp]),
     "mogp_gram": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_dp,
                                  ctypes.c_int64, c_dp, ctypes.c_int64, c_dp, c_dp]),
+    "mogp_model_set_kinds": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_ip, c_dp]),
+    "mogp_gram_kinds": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_dp, c_ip, c_dp,
+                                       ctypes.c_int64, c_dp, ctypes.c_int64, c_dp, c_dp]),
     "mogp_exact_eval": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.c_double, ctypes.c_int,
                                        c_dp, c_dp, c_dp, c_dp, c_dp, c_i64p]),
     "mogp_exact_predict": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.c_double, c_dp, ctypes.c_int64, c_dp,
@@ -179,8 +183,12 @@ def device_name(device=0):
     return buf.value.decode()
 
 
-def gram(device, C, D, table, X1, X2=None):
-    """K(X1[,X2]) through mogp_gram."""
+def _ip(a):
+    return None if a is None else a.ctypes.data_as(c_ip)
+
+
+def gram(device, C, D, table, X1, X2=None, kind=None, shape=None):
+    """K(X1[,X2]) through mogp_gram; with radial kinds (gpr/kernel.py: _spectral_kinds) through mogp_gram_kinds."""
     table = _f64(table)
     X1 = _f64(X1)
     X2 = _f64(X2)
@@ -188,6 +196,13 @@ def gram(device, C, D, table, X1, X2=None):
     M1 = X1.shape[0]
     M2 = M1 if X2 is None else X2.shape[0]
     out = np.empty((M1, M2), dtype=np.float64)
+    if kind is not None:
+        kind = np.ascontiguousarray(kind, dtype=np.int32)
+        shape = _f64(shape)
+        assert kind.shape == table.shape[:3] and shape.shape == table.shape[:3]
+        check(lib().mogp_gram_kinds(context(device), C, D, T, int(table.shape[3]), _dp(table), _ip(kind), _dp(shape), M1, _dp(X1),
+                                    0 if X2 is None else M2, _dp(X2), _dp(out)))
+        return out
     check(lib().mogp_gram_ex(context(device), C, D, T, int(table.shape[3]), _dp(table), M1, _dp(X1),
                              0 if X2 is None else M2, _dp(X2), _dp(out)))
     return out
@@ -267,6 +282,16 @@ class ExactHandle:
         self.T = table.shape[2]
         self.W = int(table.shape[3])                 # 2 + 3 D, or 2 + 5 D for terms with an envelope (MOHSM)
         check(lib().mogp_model_set_terms_ex(self._h, self.T, self.W, _dp(table)))
+
+    def set_kinds(self, kind, shape):
+        """radial profile and shape of every (pair, term) of the table just set (mogp_model_set_kinds); None: all Gaussian"""
+        if kind is None:
+            check(lib().mogp_model_set_kinds(self._h, self.T, None, None))
+            return
+        kind = np.ascontiguousarray(kind, dtype=np.int32)
+        shape = _f64(shape)
+        assert kind.shape == (self.C, self.C, self.T) and shape.shape == kind.shape
+        check(lib().mogp_model_set_kinds(self._h, self.T, _ip(kind), _dp(shape)))
 
     def set_point_diag(self, kdiag):
         """K_diag per training point for kernels whose diagonal is not constant per channel (None: back to the table's constant)"""

@@ -252,8 +252,14 @@ def _convert_kernel(bag):
         return cls(*subs, output_dims=odims, input_dims=idims, Rq=params["weight"].data.shape[2])
     if name == "SpectralMixtureKernel":
         return cls(Q=params["magnitude"].data.shape[0], input_dims=idims)
+    if name == "SquaredExponentialKernel":
+        return cls(order=st.get("order", 0), input_dims=idims)
+    if name == "RationalQuadraticKernel":
+        return cls(alpha=float(st.get("alpha", 1.0)), order=st.get("order", 0), input_dims=idims)
+    if name == "MaternKernel":
+        return cls(nu=float(st.get("nu", 0.5)), input_dims=idims)
     try:
-        return cls(input_dims=idims)                       # single-output kernels: SquaredExponential, Spectral, Matern, ...
+        return cls(input_dims=idims)                       # the other single-output kernels: Spectral, Exponential, ...
     except TypeError:
         raise NotImplementedError("the checkpoint loader does not know how to construct the kernel %s" % name)
 
@@ -464,6 +470,7 @@ _PARAMETER_REBUILD = _Global("mogptk.gpr.parameter", "Parameter._rebuild")
 _REF_KERNEL_MODULE = {
     "AddKernel": "kernel", "MulKernel": "kernel", "MixtureKernel": "kernel",
     "SpectralKernel": "singleoutput", "SpectralMixtureKernel": "singleoutput", "SquaredExponentialKernel": "singleoutput",
+    "RationalQuadraticKernel": "singleoutput", "MaternKernel": "singleoutput", "ExponentialKernel": "singleoutput",
     "IndependentMultiOutputKernel": "multioutput", "MultiOutputSpectralMixtureKernel": "multioutput", "CrossSpectralKernel": "multioutput",
     "LinearModelOfCoregionalizationKernel": "multioutput", "GaussianConvolutionProcessKernel": "multioutput",
     "MultiOutputHarmonizableSpectralKernel": "multioutput", "MultiOutputSpectralKernel": "multioutput",
@@ -528,6 +535,9 @@ class _Exporter:
         own = {"input_dims": None if name == "IndependentMultiOutputKernel" else k.input_dims, "_active_dims": None, "output_dims": k.output_dims}
         if "twopi" in k.__dict__:
             own["twopi"] = np.float64(k.twopi)
+        for attr in ("alpha", "nu", "order"):                     # plain attributes of the stationary kernels, in the reference constructors' order
+            if attr in k.__dict__:
+                own[attr] = k.__dict__[attr]
         mods = []
         if isinstance(k.__dict__.get("kernels"), (list, tuple)):
             mods.append(("kernels", self.module_list([self.kernel(s) for s in k.kernels])))

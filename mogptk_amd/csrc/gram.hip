@@ -225,11 +225,28 @@ __device__ __forceinline__ void stage_item_load(StageItem<DM>& I, int which, int
 
 // AMP: fold the amplitude A_t into the row factors (Gram); otherwise unit amplitude (moments).  `tab`: the pair's term rows (LDS copy or
 // global memory -- a generic pointer), W doubles each.
-template <int DM, bool AMP>
+// RAD: a launch with radial profiles (below): no Gaussian factor is split off, every term runs entry by entry (GT_GENERAL) and the staged
+// factors are the plain phase factors (times the amplitude)
+template <int DM, bool AMP, bool RAD = false>
 __device__ __forceinline__ void stage_item_compute(TileLds<DM>& L, const StageItem<DM>& I, const TileCtx<DM>& X, const double* tab, int W,
                                                    int which, int t, int pnt, int D, int t0) {
     const double* row = tab + (size_t)(t0 + t) * W;
     const double A = row[0];
+    if constexpr (RAD) {
+        const int deg = (AMP && A == 0.0) ? GT_SKIP : GT_GENERAL;
+        if (pnt == 0 && which == 0) {
+            L.deg[t] = deg; L.A[t] = A;
+            for (int d = 0; d < D; ++d) {
+                L.V[t][d] = row[2 + d]; L.M[t][d] = row[2 + D + d];
+                L.s[t][d] = (X.cr[d] - X.cc[d]) + row[2 + 2 * D + d];
+            }
+        }
+        if (deg == GT_SKIP) return;
+        const double f = AMP ? A : 1.0;
+        if (which == 0) { L.cu[t][pnt] = f * I.cs; L.su[t][pnt] = f * I.sn; }
+        else { L.cw[t][pnt] = I.cs; L.sw[t][pnt] = I.sn; }
+        return;
+    }
     const bool env = W > 2 + 3 * D;
     double zmax = 0.0, es = 0.0, emin = 0.0, efac = 0.0, s[DM], V[DM], Lv[DM], er[DM], ec[DM];
     for (int d = 0; d < D; ++d) {
@@ -292,7 +309,7 @@ __device__ __forceinline__ void stage_item_compute(TileLds<DM>& L, const StageIt
 #define STAGE_MAP(tid) const int st_wave = __builtin_amdgcn_readfirstlane((tid) >> 6), st_which = st_wave & 1, st_tb = st_wave >> 1, st_pnt = (tid) & 63
 
 // one chunk of terms into LDS; BATCH: all items' loads first (one memory round trip), else item by item (large D: registers)
-template <int DM, bool AMP, bool BATCH>
+template <int DM, bool AMP, bool BATCH, bool RAD = false>
 __device__ __forceinline__ void stage_chunk(TileLds<DM>& L, const TileCtx<DM>& X, const GTile& tl, const double* tab, int W, int D,
                                             int C, int T, int t0, int nt, const PhaseView& v, const double* __restrict__ xr, int64_t ldxr,
                                             const double* __restrict__ xc, int64_t ldxc, int tid) {
@@ -304,12 +321,12 @@ __device__ __forceinline__ void stage_chunk(TileLds<DM>& L, const TileCtx<DM>& X
             if (st_tb + 2 * k < nt) stage_item_load<DM>(I[k], st_which, st_tb + 2 * k, st_pnt, tl, D, C, T, t0, v, xr, ldxr, xc, ldxc);
 #pragma unroll
         for (int k = 0; k < STAGE_ITEMS; ++k)
-            if (st_tb + 2 * k < nt) stage_item_compute<DM, AMP>(L, I[k], X, tab, W, st_which, st_tb + 2 * k, st_pnt, D, t0);
+            if (st_tb + 2 * k < nt) stage_item_compute<DM, AMP, RAD>(L, I[k], X, tab, W, st_which, st_tb + 2 * k, st_pnt, D, t0);
     } else {
         for (int t = st_tb; t < nt; t += 2) {
             StageItem<DM> I;
             stage_item_load<DM>(I, st_which, t, st_pnt, tl, D, C, T, t0, v, xr, ldxr, xc, ldxc);
-            stage_item_compute<DM, AMP>(L, I, X, tab, W, st_which, t, st_pnt, D, t0);
+            stage_item_compute<DM, AMP, RAD>(L, I, X, tab, W, st_which, t, st_pnt, D, t0);
         }
     }
 }
@@ -352,6 +369,70 @@ __device__ __forceinline__ void gram_term(double (&acc)[4][4], const double (&p)
                 e = gauss_general<DM>(p[m], q[n], L.V[t], L.s[t], L.L[t], L.e[t], D);
             }
             acc[m][n] = fma(e, fma(cu[m], cw[n], su[m] * sw[n]), acc[m][n]);
+        }
+    }
+}
+
+// ---- radial profiles --------------------------------------------------------------------------------------------------
+// A term's Gaussian exp(-s/2), s = sum_d V_d u_d^2, generalised to a profile phi_kind(s) per (channel pair, term): rational quadratic and
+// Matern 1/2, 3/2, 5/2 (reference gpr/singleoutput.py: RationalQuadraticKernel, MaternKernel, ExponentialKernel).  None of them factorises
+// over rows and columns, so there is no tile-centred split: one library exp (and a square root) per entry and term.  The kind is uniform
+// over a tile's term -- a tile never straddles a channel pair -- so the switch below does not diverge.
+// PSI: also psi = -2 dphi/ds, the weight of the moments m1_d, m2_d (d/dV_d).  The only singular one is Matern 1/2 at s = 0 (exp(-r) / r):
+// there psi is RETURNED as 0, which makes the products u_d^2 psi and u_d psi the limit they have (0) without ever forming 0 * inf.
+template <bool PSI>
+__device__ __forceinline__ void radial_profile(int kind, double shape, double s, double& phi, double& psi) {
+    s = fmax(s, 0.0);
+    switch (kind) {
+        case MOGP_KIND_RQ: {
+            const double b = fma(s, 0.5 / shape, 1.0);
+            phi = exp(-shape * log(b));
+            if (PSI) psi = phi / b;
+        } break;
+        case MOGP_KIND_MATERN12: {
+            const double r = sqrt(s);
+            phi = exp(-r);
+            if (PSI) psi = s > 0.0 ? phi / r : 0.0;
+        } break;
+        case MOGP_KIND_MATERN32: {
+            const double r = sqrt(3.0 * s), e = exp(-r);
+            phi = fma(r, e, e);
+            if (PSI) psi = 3.0 * e;
+        } break;
+        case MOGP_KIND_MATERN52: {
+            const double r = sqrt(5.0 * s), e = exp(-r);
+            phi = fma(r, r, 3.0 * (1.0 + r)) * (e * (1.0 / 3.0));
+            if (PSI) psi = (5.0 / 3.0) * fma(r, e, e);
+        } break;
+        default:
+            phi = exp(-0.5 * s);
+            if (PSI) psi = phi;
+            break;
+    }
+}
+
+template <int DM>
+__device__ __forceinline__ double radial_s(const double (&p)[DM], const double (&q)[DM], const double* V, const double* s, int D) {
+    double arg = 0.0;
+    for (int d = 0; d < D; ++d) {
+        const double u = (p[d] - q[d]) + s[d];
+        arg = fma(V[d] * u, u, arg);
+    }
+    return arg;
+}
+
+template <int DM>
+__device__ __forceinline__ void gram_term_radial(double (&acc)[4][4], const double (&p)[4][DM], const double (&q)[4][DM], const TileLds<DM>& L, int t,
+                                                 int D, int kind, double shape, const double (&cu)[4], const double (&su)[4],
+                                                 const double (&cw)[4], const double (&sw)[4]) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        __builtin_amdgcn_sched_barrier(0);                  // one row of four library exps at a time: interleaving all sixteen is what spills
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            double phi, psi;
+            radial_profile<false>(kind, shape, radial_s<DM>(p[m], q[n], L.V[t], L.s[t], D), phi, psi);
+            acc[m][n] = fma(phi, fma(cu[m], cw[n], su[m] * sw[n]), acc[m][n]);
         }
     }
 }
@@ -406,7 +487,9 @@ __device__ __forceinline__ void gram_store(const GramArgs& a, const GTile& tl, c
 // inputs and staging items, all functions of the descriptor alone) are issued one tile ahead, before the previous tile's main loop, and
 // the descriptor itself two tiles ahead -- a tile-per-workgroup launch spends more time in these two dependent memory round trips than
 // in its arithmetic (measured: 66 of 126 us).  The staged factors are double buffered in LDS: one barrier per tile.
-template <int DT>
+// RAD: the radial instantiation (a.kind / a.shape are set): same pipeline, entry-by-entry profiles.  The Gaussian instantiations (RAD = false)
+// contain nothing of it.
+template <int DT, bool RAD = false>
 __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a, int ntiles) {
     constexpr int DM = DT > 0 ? DT : MOGP_MAXD;
     constexpr bool BATCH = DT == 1;
@@ -447,9 +530,9 @@ __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a, int ntiles) {
         if (BATCH) {
 #pragma unroll
             for (int k = 0; k < STAGE_ITEMS; ++k)
-                if (st_tb + 2 * k < nt0) stage_item_compute<DM, true>(L, I[k], X, tab, W, st_which, st_tb + 2 * k, st_pnt, D, 0);
+                if (st_tb + 2 * k < nt0) stage_item_compute<DM, true, RAD>(L, I[k], X, tab, W, st_which, st_tb + 2 * k, st_pnt, D, 0);
         } else {
-            stage_chunk<DM, true, false>(L, X, cur, tab, W, D, a.C, a.T, 0, nt0, v, a.xr, a.ldxr, a.xc, a.ldxc, tid);
+            stage_chunk<DM, true, false, RAD>(L, X, cur, tab, W, D, a.C, a.T, 0, nt0, v, a.xr, a.ldxr, a.xc, a.ldxc, tid);
         }
         double pc[4][DM], qc[4][DM];
 #pragma unroll
@@ -481,7 +564,7 @@ __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a, int ntiles) {
                 __syncthreads();
                 TileCtx<DM> Xc;
                 tile_centres<DM>(Xc, cur, D, v, a.ldxr, a.ldxc);
-                stage_chunk<DM, true, false>(L, Xc, cur, tab, W, D, a.C, a.T, t0, nt, v, a.xr, a.ldxr, a.xc, a.ldxc, tid);
+                stage_chunk<DM, true, false, RAD>(L, Xc, cur, tab, W, D, a.C, a.T, t0, nt, v, a.xr, a.ldxr, a.xc, a.ldxc, tid);
                 __syncthreads();
             }
             for (int t = 0; t < nt; ++t) {
@@ -492,6 +575,12 @@ __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a, int ntiles) {
                 for (int m = 0; m < 4; ++m) {
                     cu[m] = L.cu[t][rg * 4 + m]; su[m] = L.su[t][rg * 4 + m];
                     cw[m] = L.cw[t][cg * 4 + m]; sw[m] = L.sw[t][cg * 4 + m];
+                }
+                if constexpr (RAD) {
+                    const size_t kt = (size_t)cur.pair * a.T + t0 + t;
+                    const int kind = __builtin_amdgcn_readfirstlane(a.kind[kt]);
+                    gram_term_radial<DM>(acc, pc, qc, L, t, D, kind, a.shape[kt], cu, su, cw, sw);
+                    continue;
                 }
                 switch (deg) {
                     #define GT_CASE(N) case N: gram_term<DM, N>(acc, pc, qc, L, t, D, cu, su, cw, sw); break;
@@ -968,6 +1057,19 @@ int launch_gram(const GramArgs& a0, int ntiles, hipStream_t s) {
     a.tab_lds = tab_bytes <= 24 * 1024;                      // the term table rides in LDS when small (it is read by every staging item)
     const size_t dyn = a.tab_lds ? tab_bytes : 0;
     if (a.ev0) HIP_TRY(hipEventRecord(a.ev0, s));
+    if (a.kind) {                                            // radial profiles: every tile of the list through the radial general kernel
+        if (!a.shape) { set_error("launch_gram: kinds without shapes"); return -1; }
+        if (a.W != 2 + 3 * a.D) { set_error("launch_gram: radial profiles do not combine with enveloped term rows"); return -1; }
+        switch (a.D) {
+            case 1: hipLaunchKernelGGL((k_gram<1, true>), dim3(grid), dim3(256), dyn, s, a, ntiles); break;
+            case 2: hipLaunchKernelGGL((k_gram<2, true>), dim3(grid), dim3(256), dyn, s, a, ntiles); break;
+            case 3: hipLaunchKernelGGL((k_gram<3, true>), dim3(grid), dim3(256), dyn, s, a, ntiles); break;
+            default: hipLaunchKernelGGL((k_gram<0, true>), dim3(grid), dim3(256), dyn, s, a, ntiles); break;
+        }
+        if (a.ev1) HIP_TRY(hipEventRecord(a.ev1, s));
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     static const bool strip_on = !(std::getenv("MOGP_GRAM_STRIP") && std::atoi(std::getenv("MOGP_GRAM_STRIP")) == 0);
     if (strip_on && a.segs && a.nsegs > 0 && a.D == 1 && a.W == 5 && a.T <= GS_TC_MAX && !a.mirror && (a.ldo & 1) == 0) {
         static const int strip_nc = []() { const char* e = std::getenv("MOGP_GRAM_NC"); const int v = e ? std::atoi(e) : 4; return v == 2 ? 2 : 4; }();      // MOGP_GRAM_NC=2: 4 x 2 entries per thread on 512 threads (four waves per SIMD; round 6: 148 vs 159 us on one box, 154 vs 146 on another -- not kept as the default)
@@ -1071,12 +1173,49 @@ __device__ __forceinline__ void moment_term(double* mom, const double (&g)[4][4]
         }
 }
 
+// the radial form of moment_term (exact mode, no envelope, no input gradients): phi weighs m0, m4, m3_d; psi = -2 dphi/ds weighs m1_d, m2_d
+template <int DM>
+__device__ __forceinline__ void moment_term_radial(double* mom, const double (&g)[4][4], const double (&p)[4][DM], const double (&q)[4][DM],
+                                                   const TileLds<DM>& L, int t, int D, int kind, double shape,
+                                                   const double (&cu)[4], const double (&su)[4], const double (&cw)[4], const double (&sw)[4]) {
+    const double* V = L.V[t];
+    const double* s = L.s[t];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            if ((n & 1) == 0) __builtin_amdgcn_sched_barrier(0);      // two entries' profiles at a time (see gram_term_radial; a whole row spills here)
+            double u[DM], arg = 0.0;
+            for (int d = 0; d < D; ++d) {
+                u[d] = (p[m][d] - q[n][d]) + s[d];
+                arg = fma(V[d] * u[d], u[d], arg);
+            }
+            double phi, psi;
+            radial_profile<true>(kind, shape, arg, phi, psi);
+            const double cc = fma(cu[m], cw[n], su[m] * sw[n]), sn = fma(su[m], cw[n], -cu[m] * sw[n]);
+            const double kc = g[m][n] * phi * cc;
+            const double ks = g[m][n] * phi * sn;
+            const double kp = g[m][n] * psi * cc;
+            mom[0] += kc;
+            mom[1] += ks;
+            for (int d = 0; d < D; ++d) {
+                const double uk = u[d] * kp;
+                mom[2 + d] = fma(u[d], uk, mom[2 + d]);
+                mom[2 + D + d] += uk;
+                mom[2 + 2 * D + d] = fma(u[d], ks, mom[2 + 2 * D + d]);
+            }
+        }
+    }
+}
+
 // Two workgroups per CU wherever the registers allow it with a handful of spills (D = 1: the input-gradient variant needs 268 VGPRs
 // unconstrained, i.e. ONE wave per SIMD and nothing to hide its loads behind).
 // (round 4: cutting the registers to three or four waves per SIMD -- __launch_bounds__(256, 3 / 4) -- costs 81 / 92 spilled VGPRs; the pressure is
 // the tile's adjoint block (g: 32 VGPRs), the staged factors and the staging prefetch, not the Horner chains)
-template <int DT, bool DENSE, bool ZG, bool ENV>
-__global__ __launch_bounds__(256, (DT == 1 ? 2 : 1)) void k_moments(MomentArgs a) {
+// RAD: the radial instantiation (a.kind / a.shape are set; DENSE, ZG and ENV are false); the others contain nothing of it.
+template <int DT, bool DENSE, bool ZG, bool ENV, bool RAD = false>
+__global__ __launch_bounds__(256, (DT == 1 && !RAD ? 2 : 1)) void k_moments(MomentArgs a) {      // (RAD, D = 1: the library exps push two workgroups per CU into scratch)
+    static_assert(!RAD || (!DENSE && !ZG && !ENV), "radial moments: exact mode only");
     constexpr int DM = DT > 0 ? DT : MOGP_MAXD;
     constexpr int WM = 2 + (ENV ? 5 : 3) * DM;
     constexpr int RSTRIDE = 256 + 16;                        // one moment of all threads, +1 per 16 (the slice reads hit distinct banks)
@@ -1150,7 +1289,7 @@ __global__ __launch_bounds__(256, (DT == 1 ? 2 : 1)) void k_moments(MomentArgs a
     for (int t0 = 0; t0 < a.T; t0 += MOGP_TC) {
         const int nt = min(MOGP_TC, a.T - t0);
         if (t0 > 0) __syncthreads();                         // the first chunk has nothing to wait for
-        stage_chunk<DM, false, (DT == 1)>(L, X, tl, tab, W, D, a.C, a.T, t0, nt, v, a.x, a.ldx, xcol, ldxc, tid);
+        stage_chunk<DM, false, (DT == 1 && !RAD), RAD>(L, X, tl, tab, W, D, a.C, a.T, t0, nt, v, a.x, a.ldx, xcol, ldxc, tid);
         __syncthreads();
         for (int t = 0; t < nt; ++t) {
             const int deg = L.deg[t];
@@ -1167,6 +1306,11 @@ __global__ __launch_bounds__(256, (DT == 1 ? 2 : 1)) void k_moments(MomentArgs a
                 cu[m] = L.cu[t][rg * 4 + m]; su[m] = L.su[t][rg * 4 + m];
                 cw[m] = L.cw[t][cg * 4 + m]; sw[m] = L.sw[t][cg * 4 + m];
             }
+            if constexpr (RAD) {
+                const size_t kt = (size_t)tl.pair * a.T + t0 + t;
+                const int kind = __builtin_amdgcn_readfirstlane(a.kind[kt]);
+                moment_term_radial<DM>(mom, g, p, q, L, t, D, kind, a.shape[kt], cu, su, cw, sw);
+            } else
             switch (deg) {
                 #define GT_CASE(N) case N: moment_term<DM, N, ZG, ENV>(mom, g, p, q, L, t, D, cu, su, cw, sw, zr, zc); break;
                 GT_DEGREE_CASES(GT_CASE)
@@ -1469,6 +1613,20 @@ int launch_moments(const MomentArgs& a0, hipStream_t s) {
     const int64_t ldxc = a.xc ? a.ldxc : a.ldx;
     int rc = a.phases_ready ? 0 : launch_phase_tables(a.ph, a.x, a.ldx, a.nrows, xc, ldxc, a.xc ? a.ncols : a.nrows, a.table, a.T, a.D, a.C, a.W, s);
     if (rc) return rc;
+    if (a.kind) {                                            // radial profiles: every tile through the radial form of the staged kernel
+        if (!a.shape) { set_error("launch_moments: kinds without shapes"); return -1; }
+        if (a.G != nullptr || env) { set_error("launch_moments: radial profiles run in exact mode without an envelope only"); return -1; }
+        if (a.ev0) HIP_TRY(hipEventRecord(a.ev0, s));
+        switch (a.D) {
+            case 1: hipLaunchKernelGGL((k_moments<1, false, false, false, true>), dim3(a.ntiles), dim3(256), 0, s, a); break;
+            case 2: hipLaunchKernelGGL((k_moments<2, false, false, false, true>), dim3(a.ntiles), dim3(256), 0, s, a); break;
+            case 3: hipLaunchKernelGGL((k_moments<3, false, false, false, true>), dim3(a.ntiles), dim3(256), 0, s, a); break;
+            default: hipLaunchKernelGGL((k_moments<0, false, false, false, true>), dim3(a.ntiles), dim3(256), 0, s, a); break;
+        }
+        HIP_TRY(hipGetLastError());
+        if (a.ev1) HIP_TRY(hipEventRecord(a.ev1, s));
+        return 0;
+    }
     if (a.G == nullptr) {
         if (a.ev0) HIP_TRY(hipEventRecord(a.ev0, s));
         // D = 1 without an envelope, every row this rank's own: the persistent pipelined kernel (MOGP_MOM_X=0: the tile-per-workgroup one)

@@ -644,7 +644,7 @@ static void kinv_block_ranges(mogp_model* m) {
 static int kinv_plan(mogp_model* m, bool want) {
     static const bool full = std::getenv("MOGP_FULL_INVERSE") && std::atoi(std::getenv("MOGP_FULL_INVERSE")) != 0;
     m->kinv_sparse = false; m->kinv_fraction = 1.0;
-    if (!want || full || m->sh_n > 1 || m->tiles.empty()) return 0;
+    if (!want || full || m->sh_n > 1 || m->tiles.empty() || m->radial) return 0;      // (the e^-50 rule is the Gaussian's: other profiles decay more slowly)
     const int nb = m->nb, D = m->D, T = m->T, W = m->Wt;
     const int64_t ld = m->Npad;
     if (m->blk_cen.empty()) kinv_block_ranges(m);
@@ -959,6 +959,7 @@ static int factorize(mogp_model* m, const double* noise_var, const double* data_
     ga.table = m->d_table.p; ga.T = m->T; ga.D = D; ga.C = C; ga.W = m->Wt;
     ga.out = m->k.A.p; ga.ldo = Npad; ga.noise = m->d_noise.p; ga.dvar = data_var ? m->d_dvar.p : nullptr;
     ga.jitter_abs = jabs; ga.mirror = 0;
+    if (m->radial) { ga.kind = m->d_kind.p; ga.shape = m->d_shape.p; }
     ga.ev0 = prof_event(m, 7); ga.ev1 = prof_event(m, 8);
     m->strip.attach(ga);
     // Dataflow schedule: the first chain kernel and the first panel read the first 512 columns only, so the Gram matrix is built in two
@@ -1190,6 +1191,7 @@ static int sweep_eval_begin(mogp_model* m, const double* noise_var, const double
     ga.table = m->d_table.p; ga.T = m->T; ga.D = D; ga.C = C; ga.W = m->Wt;
     ga.out = m->k.A.p; ga.ldo = Npad; ga.noise = m->d_noise.p; ga.dvar = data_var ? m->d_dvar.p : nullptr;
     ga.jitter_abs = m->sh_jabs; ga.mirror = 0;
+    if (m->radial) return fail(MOGP_EINVAL, "the sweep / sharded evaluation does not take radial kinds (mogp_model_set_kinds)");
     const bool own = m->sh_n > 1 && m->own_n == m->sh_n && m->own_rank == m->sh_rank;
     if (own) ga.tiles = m->d_tiles_own.p;
     (own ? m->strip_own : m->strip).attach(ga);
@@ -1252,6 +1254,7 @@ static int moment_pass_device(mogp_model* m, const double* kinv, double ksign) {
     if ((rc = m->ph_xx.prepare(m->sx.off, m->sx.off, C, T, Npad, Npad, m->st, ma.ph))) return rc;
     ma.table = m->d_table.p; ma.T = T; ma.D = D; ma.C = C; ma.W = W; ma.kinv = kinv; ma.kinv_sign = ksign; ma.ld = Npad; ma.alpha = m->d_alpha.p;
     ma.row_mod = rm; ma.row_rem = m->sh_rank;
+    if (m->radial) { ma.kind = m->d_kind.p; ma.shape = m->d_shape.p; }
     ma.partial = m->d_partial.p;
     ma.phases_ready = 1;                       // ph_xx was filled by this evaluation's Gram launch: same inputs, same table
     ma.ev0 = prof_event(m, 9); ma.ev1 = prof_event(m, 10);
@@ -1385,7 +1388,7 @@ int mogp_model_destroy(mogp_model* m) {
     for (auto e : m->sh_ev) { hipError_t r = hipEventDestroy(e); (void)r; }
     if (m->tw) { m->tw->release(); delete m->tw; m->tw = nullptr; }
     m->oa.release();
-    m->d_x.release(); m->d_y.release(); m->d_table.release();
+    m->d_x.release(); m->d_y.release(); m->d_table.release(); m->d_kind.release(); m->d_shape.release();
     m->d_noise.release(); m->d_dvar.release(); m->d_z.release(); m->d_alpha.release(); m->d_zz.release();
     m->d_partial.release(); m->d_moments.release(); m->d_diagG.release(); m->d_tiles.release(); m->d_pair_start.release(); m->strip.release(); m->strip_own.release();
     m->d_tiles_head.release(); m->d_tiles_tail.release(); m->strip_head.release(); m->strip_tail.release();
@@ -1428,6 +1431,7 @@ int mogp_model_set_terms_ex(mogp_model* m, int T, int width, const double* table
     const size_t n = (size_t)m->C * m->C * T * W;
     for (size_t i = 0; i < n; ++i)
         if (!std::isfinite(table[i])) return fail(MOGP_ENONFINITE, "spectral term table has non-finite entries (kernel parameters diverged)");
+    if (T != m->T) m->radial = false;           // kinds belong to a table shape (mogp_model_set_kinds)
     m->T = T;
     m->Wt = W;
     if (m->tw) m->tw->pred_valid = false;       // mogp_sparse_predict_cov combines the last prediction's panels with the CURRENT table: a new table ends that
@@ -1441,6 +1445,33 @@ int mogp_model_set_terms_ex(mogp_model* m, int T, int width, const double* table
 int mogp_model_set_terms(mogp_model* m, int T, const double* table) {
     if (!m) return fail(MOGP_EINVAL, "mogp_model_set_terms: bad argument");
     return mogp_model_set_terms_ex(m, T, 2 + 3 * m->D, table);
+}
+
+int mogp_model_set_kinds(mogp_model* m, int T, const int* kind, const double* shape) {
+    if (!m) return fail(MOGP_EINVAL, "mogp_model_set_kinds: model is null");
+    if (T != m->T || T <= 0) return fail(MOGP_EINVAL, "mogp_model_set_kinds: T must be that of the last mogp_model_set_terms");
+    const size_t n = (size_t)m->C * m->C * T;
+    bool any = false;
+    if (kind)
+        for (size_t i = 0; i < n; ++i) {
+            if (kind[i] < MOGP_KIND_GAUSS || kind[i] > MOGP_KIND_MATERN52) return fail(MOGP_EINVAL, "mogp_model_set_kinds: unknown kind");
+            any |= kind[i] != MOGP_KIND_GAUSS;
+        }
+    m->radial = false;
+    if (!any) return MOGP_OK;                   // all Gaussian: as if never called
+    if (!shape) return fail(MOGP_EINVAL, "mogp_model_set_kinds: shape is null");
+    if (m->Wt != 2 + 3 * m->D) return fail(MOGP_EINVAL, "mogp_model_set_kinds: radial profiles do not combine with enveloped term rows");
+    for (size_t i = 0; i < n; ++i)
+        if (kind[i] == MOGP_KIND_RQ && !(shape[i] > 0.0 && std::isfinite(shape[i]))) return fail(MOGP_EINVAL, "mogp_model_set_kinds: the rational quadratic shape must be positive");
+    int rc;
+    if ((rc = use_device(m->ctx))) return rc;
+    if ((rc = m->d_kind.ensure(n))) return rc;
+    if ((rc = m->d_shape.ensure(n))) return rc;
+    // (pageable sources: the copies are staged before the calls return)
+    HIP_TRY(hipMemcpyAsync(m->d_kind.p, kind, n * sizeof(int), hipMemcpyHostToDevice, m->st));
+    HIP_TRY(hipMemcpyAsync(m->d_shape.p, shape, n * sizeof(double), hipMemcpyHostToDevice, m->st));
+    m->radial = true;
+    return MOGP_OK;
 }
 
 int mogp_model_set_point_diag(mogp_model* m, const double* kdiag) {
@@ -1577,6 +1608,7 @@ static int predict_core(mogp_model* m, const double* noise_var, const double* da
     if ((rc = m->ph_sx.prepare(ss.off, m->sx.off, C, m->T, Spad, Npad, sv, ga.ph))) return rc;
     ga.table = m->d_table.p; ga.T = m->T; ga.D = D; ga.C = C; ga.W = m->Wt; ga.out = m->d_Ksf.p; ga.ldo = Npad;
     ga.noise = nullptr; ga.dvar = nullptr; ga.jitter_abs = 0.0; ga.mirror = 0;
+    if (m->radial) { ga.kind = m->d_kind.p; ga.shape = m->d_shape.p; }
     if ((rc = launch_gram(ga, (int)pt.size(), sv))) return rc;
     if (mean_w) {                                                    // mu = K_sf w, before the substitution consumes K_sf
         std::vector<double> hw(Npad, 0.0);
@@ -1736,8 +1768,20 @@ int mogp_gram(mogp_ctx* ctx, int C, int D, int T, const double* table, int64_t M
 
 int mogp_gram_ex(mogp_ctx* ctx, int C, int D, int T, int width, const double* table, int64_t M1, const double* X1,
                  int64_t M2, const double* X2, double* K_out) {
+    return mogp_gram_kinds(ctx, C, D, T, width, table, nullptr, nullptr, M1, X1, M2, X2, K_out);
+}
+
+int mogp_gram_kinds(mogp_ctx* ctx, int C, int D, int T, int width, const double* table, const int* kind, const double* shape,
+                    int64_t M1, const double* X1, int64_t M2, const double* X2, double* K_out) {
     if (!ctx || !table || !X1 || !K_out || M1 <= 0 || T <= 0 || C <= 0 || D <= 0 || D > MOGP_MAXD || (width != 2 + 3 * D && width != 2 + 5 * D))
         return fail(MOGP_EINVAL, "mogp_gram: bad argument");
+    bool radial = false;
+    if (kind)
+        for (size_t i = 0; i < (size_t)C * C * T; ++i) {
+            if (kind[i] < MOGP_KIND_GAUSS || kind[i] > MOGP_KIND_MATERN52) return fail(MOGP_EINVAL, "mogp_gram_kinds: unknown kind");
+            radial |= kind[i] != MOGP_KIND_GAUSS;
+        }
+    if (radial && (!shape || width != 2 + 3 * D)) return fail(MOGP_EINVAL, "mogp_gram_kinds: kinds need shapes and rows of width 2 + 3 D");
     int rc;
     if ((rc = use_device(ctx))) return rc;
     const bool sym = (X2 == nullptr);
@@ -1752,8 +1796,10 @@ int mogp_gram_ex(mogp_ctx* ctx, int C, int D, int T, int width, const double* ta
     const int W = width;
     DevBuf<double> dx1, dx2, dtab, dout;
     DevBuf<GTile> dt;
+    DevBuf<int> dkind;
+    DevBuf<double> dshape;
     PhaseWs ph;
-    auto cleanup = [&]() { dx1.release(); dx2.release(); dtab.release(); dout.release(); dt.release(); ph.release(); };
+    auto cleanup = [&]() { dx1.release(); dx2.release(); dtab.release(); dout.release(); dt.release(); dkind.release(); dshape.release(); ph.release(); };
 #define G_TRY(x) do { int r__ = (x); if (r__) { cleanup(); return r__; } } while (0)
 #define G_HIP(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { cleanup(); return hip_fail(e__, #x, __FILE__, __LINE__); } } while (0)
     G_TRY(dx1.ensure((size_t)D * s1.Mpad));
@@ -1772,6 +1818,13 @@ int mogp_gram_ex(mogp_ctx* ctx, int C, int D, int T, int width, const double* ta
     G_TRY(ph.prepare(s1.off, sc.off, C, T, s1.Mpad, sc.Mpad, nullptr, ga.ph));
     ga.table = dtab.p; ga.T = T; ga.D = D; ga.C = C; ga.W = W; ga.out = dout.p; ga.ldo = Cc;
     ga.noise = nullptr; ga.dvar = nullptr; ga.jitter_abs = 0.0; ga.mirror = 1;
+    if (radial) {
+        G_TRY(dkind.ensure((size_t)C * C * T));
+        G_TRY(dshape.ensure((size_t)C * C * T));
+        G_HIP(dev_upload(dkind.p, kind, (size_t)C * C * T * sizeof(int)));
+        G_HIP(dev_upload(dshape.p, shape, (size_t)C * C * T * sizeof(double)));
+        ga.kind = dkind.p; ga.shape = dshape.p;
+    }
     G_TRY(launch_gram(ga, (int)tiles.size(), nullptr));
     G_HIP(hipDeviceSynchronize());
     if (s1.identity && sc.identity) {

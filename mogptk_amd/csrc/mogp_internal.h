@@ -11,6 +11,13 @@
 #define MOGP_TC 8              // spectral terms processed per LDS chunk in the Gram / moment kernels
 #define MOGP_MAXD 8            // maximum input dimension
 
+// radial profile phi(s) of a term, s = sum_d V_d u_d^2, r = sqrt(s) (the values of mogp_model_set_kinds)
+#define MOGP_KIND_GAUSS 0      // exp(-s/2)
+#define MOGP_KIND_RQ 1         // (1 + s / (2 alpha))^-alpha
+#define MOGP_KIND_MATERN12 2   // exp(-r)
+#define MOGP_KIND_MATERN32 3   // (1 + sqrt(3) r) exp(-sqrt(3) r)
+#define MOGP_KIND_MATERN52 4   // (1 + sqrt(5) r + 5 r^2 / 3) exp(-sqrt(5) r)
+
 namespace mogp {
 
 // ---- error plumbing --------------------------------------------------------------------------------
@@ -83,6 +90,10 @@ struct GramArgs {
     int dbg;               // measurement only (MOGP_GRAM_DBG): 1 = no stores, 2 = no terms (stores only)
     int tab_lds;           // set by the launcher: the term table is copied to LDS
     int phases_ready;      // the phase workspace already holds this table's phases and block centres (an earlier launch of the same evaluation)
+    // radial profile of every (pair, term), [C*C][T] each (MOGP_KIND_*); null -> all Gaussian.  A launch that carries them sends ALL its tiles
+    // to the radial instantiation of the general kernel and ignores segs / rest (the strip runs and the tile-centred split are Gaussian-only)
+    const int* kind;
+    const double* shape;   // shape parameter of the profile (rational quadratic: alpha; unused otherwise)
 };
 
 struct MomentArgs {
@@ -125,6 +136,10 @@ struct MomentArgs {
     hipEvent_t ev0, ev1;   // when non-null: recorded around the tile kernel alone (profiling)
     int tab_lds;           // set by the launcher: the term table is copied to LDS
     int phases_ready;      // the phase workspace still holds this table's phases and block centres (the Gram launch of the same evaluation filled it)
+    // radial profile of every (pair, term), as in GramArgs; null -> all Gaussian.  Exact mode without an envelope only: the moments m1_d, m2_d
+    // then carry psi = -2 dphi/ds where the others carry phi
+    const int* kind;
+    const double* shape;
 };
 
 int launch_gram(const GramArgs& a, int ntiles, hipStream_t s);

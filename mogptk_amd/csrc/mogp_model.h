@@ -318,6 +318,9 @@ struct mogp_model {
     std::vector<GTile> tiles;
     std::vector<int> pair_start;
     std::vector<double> table;          // host copy [C*C*T*W]
+    bool radial = false;                // mogp_model_set_kinds: some (pair, term) has a non-Gaussian profile; d_kind / d_shape [C*C*T] then hold them
+    mogp::DevBuf<int> d_kind;
+    mogp::DevBuf<double> d_shape;
     hipStream_t st = nullptr;           // critical-path stream (high priority)
     hipStream_t st2 = nullptr;          // bulk trailing updates of the fused schedule (CU-masked: everything but the reserved CUs)
     hipStream_t st2u = nullptr;         // bulk trailing updates over ALL CUs, for flop-bound sizes (MOGP_CHAIN_BOUND_TILES)

@@ -4,6 +4,7 @@ Kernel base classes for the HIP path -- host-side mirror of mogptk/gpr/kernel.py
 A kernel on this path does two things on the host (O(C^2 Q) scalars) and nothing else:
   * `_spectral_terms(D)`   : constrained parameters -> unified spectral term table
                               [C, C, T, 2+3D] = [A, Psi, V_d.., M_d.., Delta_d..]   
+  * `_spectral_kinds(D)`   : the radial profile of every (pair, term) -- all Gaussian unless a stationary kernel of gpr/singleoutput.py is inside
   * `_spectral_backward(g)`: d loss / d table  ->  `.grad` on every raw parameter (the chain rule the
                               reference gets from autograd through gpr/multioutput.py:182-199 etc.)
 All O(N^2) / O(N^3) work (Gram build, Cholesky, solves, gradient moments) runs in the HIP library
@@ -55,11 +56,13 @@ class terms_cache:
 
 
 def cached_terms(fn):
+    name = fn.__name__
+
     def wrapper(self, D):
         cache = _TERMS_CACHE
         if cache is None:
             return fn(self, D)
-        key = (id(self), D)
+        key = (id(self), D, name)
         if key not in cache:
             cache[key] = fn(self, D)
         return cache[key]
@@ -153,6 +156,17 @@ class Kernel(ParameterHolder):
     def _spectral_backward(self, gtable):
         raise NotImplementedError("%s is not on the MI355X spectral path" % self.name())
 
+    def _spectral_kinds(self, D):
+        """(kind [C, C, T] int32, shape [C, C, T] float64): the radial profile phi_kind(s), s = sum_d V_d u_d^2, that stands where the Gaussian
+        exp(-s/2) stands in each (channel pair, term) of `_spectral_terms(D)` (the KIND_* values of gpr/singleoutput.py), and its shape
+        parameter.  Default: all Gaussian."""
+        shape = self._spectral_terms(D).shape[:3]
+        return np.zeros(shape, dtype=np.int32), np.zeros(shape)
+
+    def _radial(self, D):
+        """some term has a non-Gaussian profile: only then do kinds travel to the device"""
+        return bool(np.any(self._spectral_kinds(D)[0]))
+
     def _spectral_diag(self, D):
         """K_diag value per channel AS THE REFERENCE RETURNS IT (constant per channel for every spectral kernel).
         Default: the true diagonal sum_t A_cct (Delta = Psi = 0 on i == j blocks); SM overrides (its K_diag
@@ -176,7 +190,14 @@ class Kernel(ParameterHolder):
         X1k = self._kernel_format(np.asarray(X1, dtype=np.float64))
         X2k = None if X2 is None else self._kernel_format(np.asarray(X2, dtype=np.float64))
         D = X1k.shape[1] - 1
-        return gram(config.device, self._channels(), D, self._spectral_terms(D), X1k, X2k)
+        with terms_cache():
+            table = self._spectral_terms(D)
+            kind, shape = self._spectral_kinds(D)
+        if not np.any(kind):
+            return gram(config.device, self._channels(), D, table, X1k, X2k)
+        if table.shape[3] > term_width(D):
+            raise NotImplementedError("a sum of enveloped (harmonizable) terms and non-Gaussian stationary kernels is not on the HIP path")
+        return gram(config.device, self._channels(), D, table, X1k, X2k, kind, shape)
 
     def K_diag(self, X1):
         """reference gpr/kernel.py:152-163, MO :483-495.  Constant per channel for every stationary spectral kernel; with an
@@ -280,6 +301,11 @@ class AddKernel(Kernels):
         tabs = [k._spectral_terms(D) for k in self.kernels]
         width = max(t.shape[3] for t in tabs)                     # a sum with an enveloped kernel: everything in the wide rows
         return np.concatenate([pad_width(t, width) for t in tabs], axis=2)
+
+    @cached_terms
+    def _spectral_kinds(self, D):
+        parts = [k._spectral_kinds(D) for k in self.kernels]       # along T, as the tables
+        return np.concatenate([p[0] for p in parts], axis=2), np.concatenate([p[1] for p in parts], axis=2)
 
     def _spectral_backward(self, gtable):
         t0 = 0

@@ -32,6 +32,14 @@ def _to_array(X):
     return np.array(X, dtype=config.dtype)
 
 
+def _leaf_kernels(kernel):
+    """the kernels of a composition that carry parameters of their own"""
+    subs = getattr(kernel, "kernels", None)
+    if not subs:
+        return [kernel]
+    return [leaf for k in subs for leaf in _leaf_kernels(k)]
+
+
 _PAIR_INDEX = {}
 
 
@@ -92,6 +100,11 @@ class Model(ParameterHolder):
         if likelihood.output_dims is not None and likelihood.output_dims != kernel.output_dims:
             raise ValueError("kernel and likelihood must have matching output dimensions")
         likelihood.validate_y(X, y)
+        if not isinstance(self, Exact):
+            D = X.shape[1] - (0 if kernel.output_dims is None else 1)
+            if any(k._radial(D) for k in _leaf_kernels(kernel)):
+                raise NotImplementedError("%s with a non-Gaussian stationary kernel (rational quadratic, Matern, exponential) is not on the HIP path yet: "
+                                          "its per-point input gradients need the profile's derivative in a third place; gpr.Exact takes them" % self.name())
 
         # limit to number of significant digits (reference gpr/model.py:106-110)
         jitter = max(jitter, 1e-6 if config.dtype == np.float32 else 1e-15)
@@ -329,11 +342,23 @@ class Exact(Model):
         comm = getattr(config, "comm", None)
         if comm is not None and (comm.world > 1 or comm.force):
             self._mean_refuse("the sharded exact evaluation (use_distributed)")
-        h = self._device_handle()
-        self._sync_mean(h)
         D = self.X.shape[1] - (0 if self.kernel.output_dims is None else 1)
         table = self.kernel._spectral_terms(D)
+        kind, shape = self.kernel._spectral_kinds(D)
+        radial = bool(np.any(kind))
+        if radial:                              # refused before any device call
+            if comm is not None and (comm.world > 1 or comm.force):
+                raise NotImplementedError("non-Gaussian stationary kernels are not carried through the sharded exact evaluation (use_distributed)")
+            if table.shape[3] > 2 + 3 * D:
+                raise NotImplementedError("a sum of enveloped (harmonizable) terms and non-Gaussian stationary kernels is not on the HIP path")
+        h = self._device_handle()
+        self._sync_mean(h)
         h.set_terms(table)
+        if radial:
+            h.set_kinds(kind, shape)
+        elif getattr(h, "radial_kinds", False):
+            h.set_kinds(None, None)               # the kernel was replaced by an all-Gaussian one with the same number of terms
+        h.radial_kinds = radial
         if table.shape[3] > 2 + 3 * D:        # envelope: the diagonal varies from point to point and enters the relative jitter (:244)
             h.set_point_diag(self.kernel._point_diag(table, self.kernel._kernel_format(self.X), D))
         return h, table, D

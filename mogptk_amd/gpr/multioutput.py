@@ -50,6 +50,17 @@ class IndependentMultiOutputKernel(MultiOutputKernel):
             table[c, c, :s.shape[0]] = s
         return table
 
+    @cached_terms
+    def _spectral_kinds(self, D):
+        subs = [k._spectral_kinds(D) for k in self.kernels]            # on the block diagonal, as the tables; padding rows are Gaussian
+        T = max(kd.shape[2] for kd, _ in subs)
+        C = self.output_dims
+        kind, shape = np.zeros((C, C, T), dtype=np.int32), np.zeros((C, C, T))
+        for c, (kd, sh) in enumerate(subs):
+            kind[c, c, :kd.shape[2]] = kd[0, 0]
+            shape[c, c, :sh.shape[2]] = sh[0, 0]
+        return kind, shape
+
     def _spectral_diag(self, D):
         return np.array([k._spectral_diag(D)[0] for k in self.kernels])   # reference :36-39
 
@@ -434,6 +445,14 @@ class LinearModelOfCoregionalizationKernel(MultiOutputKernel):
             part[..., 0] = B[:, :, q, None] * sub[None, None, :, 0]
             parts.append(part)
         return np.concatenate(parts, axis=2)
+
+    @cached_terms
+    def _spectral_kinds(self, D):
+        C = self.output_dims
+        subs = [k._spectral_kinds(D) for k in self.kernels]            # every channel pair carries the base kernels' terms, along T
+        kind = np.concatenate([np.broadcast_to(kd[0, 0], (C, C) + kd.shape[2:]) for kd, _ in subs], axis=2)
+        shape = np.concatenate([np.broadcast_to(sh[0, 0], (C, C) + sh.shape[2:]) for _, sh in subs], axis=2)
+        return np.ascontiguousarray(kind, dtype=np.int32), np.ascontiguousarray(shape)
 
     def _spectral_diag(self, D):
         """reference :497-502: sum_q (sum_r w_cqr^2) K_diag_q -- with the base kernel's own K_diag convention"""

@@ -1,7 +1,9 @@
 """
 Single-output spectral kernels on the HIP path -- host-side mirror of mogptk/gpr/singleoutput.py for
-SpectralKernel (:520-561) and SpectralMixtureKernel (:563-605).  The other stationary kernels of the
-reference are not named by the hot path and are not provided.
+SpectralKernel (:520-561) and SpectralMixtureKernel (:563-605), and for the stationary kernels whose distance is a function of
+s = sum_d V_d tau_d^2: SquaredExponentialKernel (:218-268), RationalQuadraticKernel (:270-323), MaternKernel (:607-655) and
+ExponentialKernel (:181-216).  Those are ONE term each, M = Psi = Delta = 0, with a radial profile phi_kind(s) in place of the Gaussian
+(DESIGN 1b); the device evaluates the profile per entry (csrc/gram.hip: radial_profile).
 """
 import numpy as np
 
@@ -91,3 +93,117 @@ class SpectralKernel(Kernel):
         _accumulate(self.magnitude, np.sum(g[:, 0]))
         _accumulate(self.mean, g[idx, 2 + D + idx])
         _accumulate(self.variance, FOUR_PI2 * g[idx, 2 + idx])
+
+
+# radial profile of a term (include/mogp_hip.h: mogp_model_set_kinds)
+KIND_GAUSS, KIND_RQ, KIND_MATERN12, KIND_MATERN32, KIND_MATERN52 = 0, 1, 2, 3, 4
+
+
+class _RadialKernel(Kernel):
+    """One term A phi_kind(sum_d V_d tau_d^2) with V_d = _vscale / l_d^2: magnitude (scalar) and lengthscale ((input_dims,), or a scalar
+    shared by every dimension).  Subclasses set `_kind`, `_shape` and `_vscale`."""
+    _kind = KIND_GAUSS
+    _vscale = 1.0
+
+    def _profile_shape(self):
+        return 0.0
+
+    def _precision(self, D):
+        if D != self.input_dims:
+            raise ValueError("X must have %d input dimensions" % self.input_dims)
+        l = np.asarray(self.lengthscale(), dtype=np.float64)
+        return np.broadcast_to(self._vscale / np.square(l), (D,))
+
+    @cached_terms
+    def _spectral_terms(self, D):
+        table = np.zeros((1, 1, 1, term_width(D)))
+        table[0, 0, 0, 0] = self.magnitude()
+        table[0, 0, 0, 2:2 + D] = self._precision(D)
+        return table
+
+    @cached_terms
+    def _spectral_kinds(self, D):
+        return np.full((1, 1, 1), self._kind, dtype=np.int32), np.full((1, 1, 1), float(self._profile_shape()))
+
+    def _spectral_diag(self, D):
+        return np.array([float(self.magnitude())])                       # K_diag = magnitude (phi(0) = 1)
+
+    def _spectral_diag_backward(self, gc, D):
+        _accumulate(self.magnitude, np.reshape(float(gc[0]), self.magnitude.shape))
+
+    def _spectral_backward(self, gtable):
+        D = self.input_dims
+        g = gtable[0, 0, 0]
+        _accumulate(self.magnitude, np.reshape(g[0], self.magnitude.shape))
+        l = np.asarray(self.lengthscale(), dtype=np.float64)
+        gl = g[2:2 + D] * (-2.0 * self._vscale / np.broadcast_to(l, (D,)) ** 3)      # d V_d / d l_d
+        _accumulate(self.lengthscale, gl if l.ndim else np.reshape(np.sum(gl), l.shape))
+
+
+def _check_order(order, name):
+    if 0 < order:
+        raise NotImplementedError("%s with order > 0 is not on the HIP path: cross lengthscales make the precision a full matrix M = L L^T + "
+                                  "diag(l)^-2, and a term of the device's table carries a diagonal V only" % name)
+
+
+class SquaredExponentialKernel(_RadialKernel):
+    """K = mag exp(-1/2 sum_d tau_d^2 / l_d^2) (reference :218-268): an ordinary Gaussian term (kind 0, no cosine), so it runs wherever term
+    tables run.  order = 0: one lengthscale per dimension; order = -1: one for all."""
+
+    def __init__(self, order=0, input_dims=1, active_dims=None):
+        super().__init__(input_dims, active_dims)
+        _check_order(order, "SquaredExponentialKernel")
+        self.order = order
+        self.magnitude = Parameter(1.0, lower=config.positive_minimum)
+        self.lengthscale = Parameter(np.ones(input_dims) if -1 < order else 1.0, lower=config.positive_minimum)
+
+
+class RationalQuadraticKernel(_RadialKernel):
+    """K = mag (1 + sum_d tau_d^2 / l_d^2 / (2 alpha))^-alpha (reference :270-323); alpha is a plain float, as there."""
+    _kind = KIND_RQ
+
+    def __init__(self, alpha=1.0, order=0, input_dims=1, active_dims=None):
+        super().__init__(input_dims, active_dims)
+        _check_order(order, "RationalQuadraticKernel")
+        self.alpha = alpha
+        self.order = order
+        self.magnitude = Parameter(1.0, lower=config.positive_minimum)
+        self.lengthscale = Parameter(np.ones(input_dims) if -1 < order else 1.0, lower=config.positive_minimum)
+
+    def _profile_shape(self):
+        return self.alpha
+
+
+def _check_one_dim(input_dims, name, distance):
+    if input_dims != 1:
+        raise NotImplementedError("%s with input_dims > 1 is not on the HIP path: the reference measures distance there as %s, which is not a "
+                                  "function of sum_d V_d tau_d^2" % (name, distance))
+
+
+class MaternKernel(_RadialKernel):
+    """K = mag c_nu(r) exp(-sqrt(2 nu) r), r = |tau| / l, nu in {0.5, 1.5, 2.5} (reference :607-655); one input dimension."""
+
+    def __init__(self, nu=0.5, input_dims=1, active_dims=None):
+        super().__init__(input_dims, active_dims)
+        if nu not in [0.5, 1.5, 2.5]:
+            raise ValueError("nu parameter must be 0.5, 1.5, or 2.5")
+        _check_one_dim(input_dims, "MaternKernel", "|sum_d tau_d / l_d|")
+        self.nu = nu
+        self.magnitude = Parameter(1.0, lower=1e-6)
+        self.lengthscale = Parameter(np.ones(input_dims), lower=1e-6)
+
+    @property
+    def _kind(self):
+        return {0.5: KIND_MATERN12, 1.5: KIND_MATERN32, 2.5: KIND_MATERN52}[self.nu]
+
+
+class ExponentialKernel(_RadialKernel):
+    """K = mag exp(-|tau| / (2 l)) (reference :181-216): the Matern 1/2 profile with V = 1 / (4 l^2); one input dimension."""
+    _kind = KIND_MATERN12
+    _vscale = 0.25
+
+    def __init__(self, input_dims=1, active_dims=None):
+        super().__init__(input_dims, active_dims)
+        _check_one_dim(input_dims, "ExponentialKernel", "sum_d |tau_d| / l_d")
+        self.magnitude = Parameter(1.0, lower=config.positive_minimum)
+        self.lengthscale = Parameter(np.ones(input_dims), lower=config.positive_minimum)
