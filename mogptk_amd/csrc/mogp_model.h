@@ -266,13 +266,13 @@ struct TitsiasWork {
     DevBuf<double> vec, scratch, gz, partial_uu, partial_uf, mom_uu, mom_uf, zero_noise;
     DevBuf<GTile> tiles_uu, tiles_uf;
     DevBuf<int> ps_uu, ps_uf;
-    StripTiles strip_uf;                                // (Z, X) tiles as strip-kernel runs + the rest (titsias_front)
-    std::vector<int> tile_key;                          // channel offsets of Z and X the device copies of the four lists above were made for
+    StripTiles strip_uf;                                // (Z, X) tiles as strip-kernel runs + the rest
+    std::vector<int> tile_key;                          // channel offsets of Z and X the device copies of the lists above were made for (sparse_tiles)
     size_t n_tuu = 0, n_tuf = 0;                        // their lengths (the host lists themselves are built only when the key changes)
     DevBuf<double> Kus, Aus, Bus;                       // prediction panels (Mpad x Spad)
     DevBuf<double> zero_col;                            // Mpad zeros
     DevBuf<double> kslices;                             // split-K partial sums of the Qs SYRK (ks x Mpad x Mpad)
-    DevBuf<double> red;                                 // data-sharded evaluation: [v y | y^T y, N, sum K_ff,nn] for the all-reduce
+    DevBuf<double> red;                                 // data-sharded evaluation: [vector | host scalars] for one all-reduce (allreduce_vec_scalars)
     const double* Wq = nullptr;                         // L_q^-1 of the inner M x M system (where spd_invert left it)
     SortedX pred_ss;                                    // the test inputs of the last sparse prediction (a = L^-1 Kus in Aus, b in Bus): what
     bool pred_valid = false;                            // mogp_sparse_predict_cov needs for the full covariance K_ss - a^T a + b^T b
@@ -282,7 +282,7 @@ struct TitsiasWork {
     std::vector<int> hblk_z, hblk_x;                    // the fixed-order reduction of d/dZ (gz_prepare / gz_attach)
     DevBuf<double> gzp;
     // svgp.hip: what the forward pass at the training inputs leaves for the backward pass
-    SortedX sv_sz; std::vector<GTile> sv_tuu, sv_tuf; std::vector<int> sv_psuu, sv_psuf; int64_t sv_M = 0; bool sv_dense = false, sv_valid = false;
+    SortedX sv_sz; bool sv_dense = false, sv_valid = false;
     DevBuf<double> kd_point;                            // Snelson / Hensman with enveloped terms: the kernel diagonal per training point (sorted order)
     DevBuf<double> nvec;                                // Snelson: per-point vectors (g, G, G y, sqrt G, v^T r / w, alpha, h) + per-channel inputs
     PhaseWs ph_zz, ph_zx, ph_zs;                        // phase tables: (Z, Z), (Z, X), (Z, Xs)
@@ -434,7 +434,7 @@ void mean_grad_collect(mogp_model* m);                                     // af
 void mean_release(mogp_model* m);
 int spd_alloc(Spd& w, int64_t Npad, int owned_rows_device = -1);   // >= 0: the owned-rows form (A reserved on that device, nothing backed yet, no B)
 int spd_make_whole(Spd& w);           // an owned-rows workspace becomes an ordinary one (every granule of A backed, B allocated)
-// helpers shared by the sparse / variational models (titsias.hip)
+// helpers shared by the sparse / variational models (sparse.hip)
 inline GemmArgs make_gemm(const double* A, int64_t lda, int akm, const double* B, int64_t ldb, int bkm, double* C, int64_t ldc,
                           double alpha, int mode, int mt, int nt, int64_t K) {
     GemmArgs g{};
@@ -454,7 +454,7 @@ void gz_attach(const TitsiasWork& t, MomentArgs& ma, bool zx);
 int spd_check_info(mogp_model* m, const char* which, int64_t* info);
 int spd_info_verdict(mogp_model* m, const char* which, unsigned long long hinfo, int64_t* info);   // what spd_check_info concludes from the word
 // after the LAST stream sync of a sparse / variational evaluation: did a hand-off between workgroups (stream-K GEMM of a wide triangular solve,
-// chain kernel) time out anywhere?  Then the numbers are not valid: the model drops those forms and the call fails, loudly (titsias.hip)
+// chain kernel) time out anywhere?  Then the numbers are not valid: the model drops those forms and the call fails, loudly
 int sparse_timeout_check(mogp_model* m);
 bool chain_enabled(const mogp_model* m);   // chain.hip
 int chain_fallback(mogp_model* m);     // mogp_api.hip: after MOGP_INFO_CHAIN_TIMEOUT -- drain, switch the model to the launch-per-step chain; the caller repeats the evaluation
@@ -466,6 +466,39 @@ int spd_invert(mogp_model* m, Spd& w, const char* which, int64_t* info, const do
 // out (Mpad x Mpad, lower tiles) = alpha A B^T over K (leading dimension ldk), K cut into slices so that the launch fills the chip
 int mm_lower_splitk(mogp_model* m, TitsiasWork& t, const double* A, const double* B, double* out, int mt, int64_t Mpad, int64_t ldk, int64_t K,
                     double alpha = 1.0);
+// The scaffold of the three inducing-point models (sparse.hip); t is *m->tw, sz the channel-sorted inducing inputs.
+int launch_scale_cols(const double* in, double* out, int64_t ld, int64_t rows, int64_t n, const double* s, hipStream_t st);   // out[r][j] = in[r][j] * s[j]
+int sparse_workspace(mogp_model* m, TitsiasWork& t, int64_t Mpad);         // everything sized by Mpad alone, (re)allocated when Mpad changes
+// device tile lists over (Z, Z) and -- want_uf -- (Z, X) with their pair starts and strip runs, rebuilt only when the channel offsets change
+int sparse_tiles(mogp_model* m, TitsiasWork& t, const SortedX& sz, bool want_uf);
+// Sorts Z (need_grouped: the refusal for inducing inputs that are not grouped by channel, for callers that cannot take them), sizes the
+// workspace (creating m->tw), uploads Z and the tile lists, arms d_info and builds Kuu + *jit I (jitter relative to its mean diagonal) in
+// t.a.A, set up for a factorisation that keeps L.  The caller runs spd_potrf on t.a.
+int sparse_kuu(mogp_model* m, int64_t M, const double* Z, double jitter, bool want_uf, SortedX& sz, double* jit, const char* need_grouped = nullptr);
+// Kuf into t.B on `stream` (use_strips: interior tiles on the strip kernel; out2: a second copy written by the same kernel, or null)
+int sparse_kuf(mogp_model* m, TitsiasWork& t, const SortedX& sz, hipStream_t stream, bool use_strips, double* out2);
+int refined_apply(mogp_model* m, TitsiasWork& t, const double* P, const double* Q, const double* rhs, double* out);   // out = P rhs, refined once against Q = P^-1 (Mpad vectors)
+// vec (device, n) and hs (host, k) summed over the ranks in one all-reduce, in place (vec may be null with n = 0); synchronises m->st
+int allreduce_vec_scalars(mogp_model* m, TitsiasWork& t, double* vec, int64_t n, double* hs, int k);
+// t.GA (lower) = scale * L^-T E L^-1 with E symmetric in t.E (overwritten), its diagonal into t.vec[2 Mpad : 3 Mpad]
+int adjoint_GA(mogp_model* m, TitsiasWork& t, double scale, hipStream_t stream);
+// panel (Mpad x Npad, or null) <- L^-T panel, and beta = L^-T r: when N is not a multiple of 128 r travels through the blocked solve in the panel's
+// first (zero) padding column -- a vector solve of its own is 2 nb dependent, almost empty launches -- otherwise, or without a panel, in t.Hm
+int solve_with_rider(mogp_model* m, TitsiasWork& t, double* panel, const double* r, double* beta);
+// One pass of the dense-mode moment kernel: adjoint G (leading dimension ldg) + rcoef ru rw^T; dz: d/dZ is collected into t.gz
+struct MomentSpec { const double* G; int64_t ldg; const double* ru; const double* rw; double rcoef; bool dz; };
+// The (Z, X) pass (uf null, the dense Hensman model: t.mom_uf = 0 instead), all-reduced when sharded, the join of `side`, then the symmetric
+// (Z, Z) pass: t.mom_uf, t.mom_uu, t.gz
+int sparse_moments(mogp_model* m, TitsiasWork& t, const SortedX& sz, const MomentSpec* uf, const MomentSpec& uu, bool sharded, hipStream_t side);
+// Prediction: sorts Xs into ss, Kus into t.Kus, a = L^-1 Kus into t.Aus; the caller forms b in t.Bus.  The last prediction's state for
+// mogp_sparse_predict_cov is invalid from here until sparse_predict_finish, which sets it.
+int sparse_predict_panels(mogp_model* m, TitsiasWork& t, const SortedX& sz, int64_t S, const double* Xs, SortedX& ss);
+// mu = mu_panel^T mu_vec / mu_div and var = kdiag - colsum a^2 + colsum b^2 (kdiag null: colsum b^2 alone) at the points pts, in the caller's
+// order; kdiag per channel, or per point with enveloped terms.  Ends with the evaluation's stream sync and sparse_timeout_check.
+int sparse_point_stats(mogp_model* m, TitsiasWork& t, const SortedX& pts, const double* a, const double* b, const double* mu_panel,
+                       const double* mu_vec, double mu_div, const double* kdiag, double* mu, double* var);
+int sparse_predict_finish(mogp_model* m, TitsiasWork& t, const SortedX& ss, const double* mu_panel, const double* mu_vec, double mu_div,
+                          const double* kss_diag, double* mu, double* var);   // sparse_point_stats with a, b = t.Aus, t.Bus
 void one_gpu_call(mogp_model* m);   // ownership state of a previous sharded evaluation off (every one-GPU entry point calls this first)
 int ensure_system(mogp_model* m);     // the N x N system of the exact / OA paths and the tile lists over (X, X), on first use (mogp_api.hip)
 int spd_potrf(mogp_model* m, Spd& w, long long info_base = 0);

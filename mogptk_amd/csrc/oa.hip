@@ -53,14 +53,6 @@ __global__ void k_oa_rowstats(const double* __restrict__ Binv, int64_t ld, int64
     if (threadIdx.x == 0) { s_out[i] = rs[0]; r_out[i] = rr[0]; }
 }
 
-// out[i][j] = in[i][j] * w[j]
-__global__ void k_oa_scale_cols(const double* __restrict__ in, double* __restrict__ out, int64_t ld, int64_t n, const double* __restrict__ w) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const int64_t i = blockIdx.y;
-    out[i * ld + j] = in[i * ld + j] * w[j];
-}
-
 // G[i][j] = lam[i] lam[j] (Y[i][j] - Binv[i][j] / 2) + (e[i] nu[j] + nu[i] e[j] - nu[i] nu[j]) / 2      (in place over Y)
 __global__ void k_oa_adjoint(double* __restrict__ Y, const double* __restrict__ Binv, int64_t ld, int64_t n, const double* __restrict__ lam,
                              const double* __restrict__ nu, const double* __restrict__ e) {
@@ -203,8 +195,7 @@ int mogp_oa_backward(mogp_model* m, const double* e, const double* f, double* mo
     RC(launch_symv_lower(o.K.p, Npad, Npad, den, dgnu, m->d_symv.p, 1.0, m->st, 0, 0));
     // Y = B^-1 diag(w) B^-1 (lower tiles, mirrored), then the adjoint of K in place
     const dim3 gnn((unsigned)((Npad + 255) / 256), (unsigned)Npad);
-    hipLaunchKernelGGL(k_oa_scale_cols, gnn, dim3(256), 0, m->st, Binv, o.Sc.p, Npad, Npad, dw);
-    HIP_TRY(hipGetLastError());
+    RC(launch_scale_cols(Binv, o.Sc.p, Npad, Npad, Npad, dw, m->st));
     GemmArgs g = make_gemm(o.Sc.p, Npad, 0, Binv, Npad, 0, o.Y.p, Npad, 1.0, GM_LOWER, nt, nt, Npad);
     RC(gemm_call(m, g, gemm_flops(g, nullptr)));
     RC(launch_symmetrize(o.Y.p, Npad, Npad, m->st));

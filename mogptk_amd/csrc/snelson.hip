@@ -23,8 +23,6 @@ using namespace mogp;
 
 namespace {
 
-
-
 // per point (channel-sorted order): g = Kff_diag[c] - q + s2[c], G = 1/g, Gy = G y, sg = sqrt(G); zero on the padding.  kd_point (terms with
 // an envelope, MOHSM): the kernel diagonal follows the points -- Kff_diag per point instead of per channel
 __global__ void k_sn_point(const double* __restrict__ q, const double* __restrict__ y, const int* __restrict__ off, int C,
@@ -39,13 +37,6 @@ __global__ void k_sn_point(const double* __restrict__ q, const double* __restric
     g[n] = gv;
     const double Gv = 1.0 / gv;
     G[n] = Gv; Gy[n] = Gv * y[n]; sg[n] = sqrt(fabs(Gv));
-}
-// out[m][n] = in[m][n] * s[n]
-__global__ void k_scale_cols(const double* __restrict__ in, double* __restrict__ out, int64_t ld, int64_t n, const double* __restrict__ s) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const int64_t r = blockIdx.y;
-    out[r * ld + j] = in[r * ld + j] * s[j];
 }
 // w[n] = sum_m a[m][n] b[m][n] over `rows` rows (row chunks of 256 into part, then summed in order)
 __global__ __launch_bounds__(256) void k_coldot_part(const double* __restrict__ a, const double* __restrict__ b, int64_t ld, int64_t rows, int64_t n,
@@ -88,74 +79,26 @@ __global__ void k_sn_adjoint(double* __restrict__ T, const double* __restrict__ 
 
 struct SnScalars { double logdet_q, sumlogg, yGy, rvGy, jit, ntot; };
 
-
 // Front end shared by the evaluation and the prediction: everything up to r = Pq (v G y) and the scalars of p.
 // On return: t.a = L (Kuu), t.v = v, t.Wq = Lq^-1, t.q.B = Pq (full), t.Qs = Bq (full), t.nvec = [g | G | Gy | sqrt G | ...],
 // t.vec[0:Mpad] = v G y, t.vec[Mpad:2Mpad] = r.
 // sharded: this handle holds ONE SHARD of the training points (cf. mogp_titsias_eval_sharded): v G v^T, v G y, sum log g, y^T G y and N are
 // all-reduced (and the per-point positivity check with them, so that every rank takes the same exit).
 int snelson_front(mogp_model* m, int64_t M, const double* Z, const double* noise_var, double jitter, const double* kff_diag, SortedX& sz,
-                  std::vector<GTile>& tuu, std::vector<int>& psuu, std::vector<GTile>& tuf, std::vector<int>& psuf, SnScalars& sc,
-                  int64_t* info, bool need_moment_tiles, bool sharded) {
-    const int C = m->C, D = m->D, W = m->Wt;                   // 2 + 3 D, or 2 + 5 D: terms with an envelope on the input midpoint (MOHSM)
-    const bool env = W > 2 + 3 * D;
+                  SnScalars& sc, int64_t* info, bool sharded) {
+    const int C = m->C;
+    const bool env = m->Wt > 2 + 3 * m->D;                     // terms with an envelope on the input midpoint (MOHSM)
     const int64_t N = m->N, Npad = m->Npad;
-    if (m->T <= 0) return fail(MOGP_EINVAL, "mogp_model_set_terms must be called before an evaluation");
     if (env && sharded) return fail(MOGP_EINVAL, "the data-parallel Snelson path does not take terms with an envelope (MOHSM)");
     for (int c = 0; c < C; ++c) if (!(noise_var[c] > 0.0)) return fail(MOGP_EINVAL, "noise variances must be positive");
-    RC(sort_inputs(Z, M, D, C, MOGP_TILE, sz));
-    const int64_t Mpad = sz.Mpad;
-    if (!m->tw) m->tw = new TitsiasWork();
+    RC(sparse_kuu(m, M, Z, jitter, true, sz, &sc.jit));
     TitsiasWork& t = *m->tw;
+    const int64_t Mpad = t.Mpad;
     const int mt = (int)(Mpad / MOGP_TILE);
-    if (t.Mpad != Mpad) {
-        t.Mpad = Mpad;
-        RC(spd_alloc(t.a, Mpad)); RC(spd_alloc(t.q, Mpad));
-        RC(t.zx.ensure((size_t)D * Mpad));
-        RC(t.B.ensure((size_t)Mpad * Npad)); RC(t.v.ensure((size_t)Mpad * Npad));
-        { int r__ = dev_fill_zero(t.v.p, (size_t)Mpad * Npad * sizeof(double)); if (r__) return r__; }      // its padding is zero from here on (titsias.hip relies on it)
-        RC(t.Qs.ensure((size_t)Mpad * Mpad));
-        RC(t.vec.ensure((size_t)8 * Mpad + 4 * Npad));
-        RC(t.scratch.ensure((size_t)(Mpad / 256 + 2) * std::max(Npad, Mpad) + (size_t)(Mpad / 512 + 2) * Mpad));
-        RC(t.zero_noise.ensure(C));
-        { int r__ = dev_fill_zero(t.zero_noise.p, C * sizeof(double)); if (r__) return r__; }
-    }
     RC(t.nvec.ensure((size_t)8 * Npad + 2 * C));
     // Kuf's padding (rows >= M, columns >= N) must be zero and this path overwrites t.B with scaled copies of v: cleared per call
     HIP_TRY(hipMemsetAsync(t.B.p, 0, (size_t)Mpad * Npad * sizeof(double), m->st));
-    m->gemm_ev_used = 0; m->gemm_launches = 0; m->gemm_flops = 0.0;
-    build_sym_tiles(sz.off, C, tuu, psuu);
-    build_rect_tiles(sz.off, m->sx.off, C, tuf, &psuf);
-    t.tile_key.clear();                                     // (the Titsias path keeps its lists in these buffers between evaluations)
-    RC(t.tiles_uu.ensure(tuu.size())); RC(t.tiles_uf.ensure(tuf.size()));
-    HIP_TRY(hipMemcpyAsync(t.zx.p, sz.xs.data(), (size_t)D * Mpad * sizeof(double), hipMemcpyHostToDevice, m->st));
-    HIP_TRY(hipMemcpyAsync(t.tiles_uu.p, tuu.data(), tuu.size() * sizeof(GTile), hipMemcpyHostToDevice, m->st));
-    HIP_TRY(hipMemcpyAsync(t.tiles_uf.p, tuf.data(), tuf.size() * sizeof(GTile), hipMemcpyHostToDevice, m->st));
-    if (need_moment_tiles) {
-        RC(t.ps_uu.ensure(psuu.size())); RC(t.ps_uf.ensure(psuf.size()));
-        HIP_TRY(hipMemcpyAsync(t.ps_uu.p, psuu.data(), psuu.size() * sizeof(int), hipMemcpyHostToDevice, m->st));
-        HIP_TRY(hipMemcpyAsync(t.ps_uf.p, psuf.data(), psuf.size() * sizeof(int), hipMemcpyHostToDevice, m->st));
-        RC(t.partial_uu.ensure(tuu.size() * (size_t)m->T * W)); RC(t.partial_uf.ensure(tuf.size() * (size_t)m->T * W));
-        RC(t.mom_uu.ensure((size_t)(C * (C + 1) / 2) * m->T * W)); RC(t.mom_uf.ensure((size_t)C * C * m->T * W));
-    }
-    const unsigned long long big = std::numeric_limits<unsigned long long>::max();
-    HIP_TRY(hipMemcpyAsync(m->d_info.p, &big, sizeof(big), hipMemcpyHostToDevice, m->st));
-
-    sc.jit = jitter * table_diag_points(m, sz) / (double)M;      // relative jitter on Kuu (reference gpr/model.py:524 -> :244); with an envelope the diagonal follows Z
-
-    GramArgs ga{};
-    ga.tiles = t.tiles_uu.p; ga.xr = t.zx.p; ga.xc = t.zx.p; ga.ldxr = ga.ldxc = Mpad; ga.nrows = ga.ncols = M;
-    RC(t.ph_zz.prepare(sz.off, sz.off, C, m->T, Mpad, Mpad, m->st, ga.ph));
-    ga.table = m->d_table.p; ga.T = m->T; ga.D = D; ga.C = C; ga.W = W; ga.out = t.a.A.p; ga.ldo = Mpad;
-    ga.noise = t.zero_noise.p; ga.dvar = nullptr; ga.jitter_abs = sc.jit; ga.mirror = 0;
-    RC(launch_gram(ga, (int)tuu.size(), m->st));
-    RC(launch_pad_identity(t.a.A.p, Mpad, M, Mpad, m->st));
-    ga.tiles = t.tiles_uf.p; ga.xc = m->d_x.p; ga.ldxc = Npad; ga.ncols = m->N; ga.out = t.B.p; ga.ldo = Npad; ga.noise = nullptr; ga.jitter_abs = 0.0;
-    RC(t.ph_zx.prepare(sz.off, m->sx.off, C, m->T, Mpad, Npad, m->st, ga.ph));
-    RC(launch_gram(ga, (int)tuf.size(), m->st));
-
-    t.a.keep_L = true;
-    t.a.refine_panels = !(std::getenv("MOGP_REFINE_PANELS") && std::atoi(std::getenv("MOGP_REFINE_PANELS")) == 0);   // K_uu + jitter is ill-conditioned: mogp_api.hip:spd_potrf
+    RC(sparse_kuf(m, t, sz, m->st, false, nullptr));
     RC(spd_potrf(m, t.a));
     RC(spd_check_info(m, "Kuu", info));
     HIP_TRY(hipMemcpyAsync(t.v.p, t.B.p, (size_t)Mpad * Npad * sizeof(double), hipMemcpyDeviceToDevice, m->st));
@@ -187,8 +130,7 @@ int snelson_front(mogp_model* m, int64_t M, const double* Z, const double* noise
     std::vector<double> hg(Npad);
     HIP_TRY(hipMemcpyAsync(hg.data(), g, Npad * sizeof(double), hipMemcpyDeviceToHost, m->st));
     // Bq = I + (v sqrt G)(v sqrt G)^T
-    hipLaunchKernelGGL(k_scale_cols, dim3((unsigned)((Npad + 255) / 256), (unsigned)Mpad), dim3(256), 0, m->st, t.v.p, t.B.p, Npad, Npad, sg);
-    HIP_TRY(hipGetLastError());
+    RC(launch_scale_cols(t.v.p, t.B.p, Npad, Mpad, Npad, sg, m->st));
     RC(mm_lower_splitk(m, t, t.B.p, t.B.p, t.q.A.p, mt, Mpad, Npad, Npad));
     double* vGy = t.vec.p;
     RC(launch_gemv_rows(t.v.p, Npad, Mpad, Npad, Gy, vGy, m->st));
@@ -202,15 +144,8 @@ int snelson_front(mogp_model* m, int64_t M, const double* Z, const double* noise
     sc.ntot = (double)N;
     double nbad = bad >= 0 ? 1.0 : 0.0;
     if (sharded) {
-        RC(t.red.ensure((size_t)Mpad + 4));
         double hs[4] = {sc.sumlogg, sc.yGy, sc.ntot, nbad};
-        HIP_TRY(hipMemcpyAsync(t.red.p, vGy, Mpad * sizeof(double), hipMemcpyDeviceToDevice, m->st));
-        HIP_TRY(hipMemcpyAsync(t.red.p + Mpad, hs, sizeof(hs), hipMemcpyHostToDevice, m->st));
-        HIP_TRY(hipStreamSynchronize(m->st));
-        RC(comm_allreduce(m->ctx, t.red.p, Mpad + 4, m->st));
-        HIP_TRY(hipMemcpyAsync(vGy, t.red.p, Mpad * sizeof(double), hipMemcpyDeviceToDevice, m->st));
-        HIP_TRY(hipMemcpyAsync(hs, t.red.p + Mpad, sizeof(hs), hipMemcpyDeviceToHost, m->st));
-        HIP_TRY(hipStreamSynchronize(m->st));
+        RC(allreduce_vec_scalars(m, t, vGy, Mpad, hs, 4));
         sc.sumlogg = hs[0]; sc.yGy = hs[1]; sc.ntot = hs[2]; nbad = hs[3];
     }
     if (nbad > 0.0)
@@ -224,15 +159,7 @@ int snelson_front(mogp_model* m, int64_t M, const double* Z, const double* noise
     RC(launch_symmetrize(t.q.B.p, Mpad, Mpad, m->st));
     RC(launch_symmetrize(t.Qs.p, Mpad, Mpad, m->st));
     double* r = t.vec.p + Mpad;
-    {   // r = Pq (v G y): the explicit inverse plus one step of iterative refinement against Bq (see titsias.hip)
-        double* tmp = t.vec.p + 5 * Mpad;
-        double* res = t.vec.p + 6 * Mpad;
-        RC(launch_gemv_rows(t.q.B.p, Mpad, Mpad, Mpad, vGy, r, m->st));
-        RC(launch_gemv_rows(t.Qs.p, Mpad, Mpad, Mpad, r, tmp, m->st));
-        RC(launch_axpby(Mpad, 1.0, vGy, -1.0, tmp, res, m->st));
-        RC(launch_gemv_rows(t.q.B.p, Mpad, Mpad, Mpad, res, tmp, m->st));
-        RC(launch_axpby(Mpad, 1.0, r, 1.0, tmp, r, m->st));
-    }
+    RC(refined_apply(m, t, t.q.B.p, t.Qs.p, vGy, r));             // r = Pq (v G y): the explicit inverse plus one step of iterative refinement against Bq
     const int nbq = t.q.nb;
     std::vector<double> hv((size_t)2 * Mpad), hl(nbq);
     HIP_TRY(hipMemcpyAsync(hv.data(), t.vec.p, (size_t)2 * Mpad * sizeof(double), hipMemcpyDeviceToHost, m->st));
@@ -256,10 +183,8 @@ int snelson_eval_impl(mogp_model* m, int64_t M, const double* Z, const double* n
     const int64_t N = m->N, Npad = m->Npad;
     const bool grad = (flags & MOGP_EVAL_GRAD) != 0;
     SortedX sz;
-    std::vector<GTile> tuu, tuf;
-    std::vector<int> psuu, psuf;
     SnScalars sc;
-    RC(snelson_front(m, M, Z, noise_var, jitter, kff_diag, sz, tuu, psuu, tuf, psuf, sc, info, grad, sharded));
+    RC(snelson_front(m, M, Z, noise_var, jitter, kff_diag, sz, sc, info, sharded));
     TitsiasWork& t = *m->tw;
     const int64_t Mpad = t.Mpad;
     const int mt = (int)(Mpad / MOGP_TILE), nt = (int)(Npad / MOGP_TILE);
@@ -270,8 +195,6 @@ int snelson_eval_impl(mogp_model* m, int64_t M, const double* Z, const double* n
 
     RC(t.GB.ensure((size_t)Mpad * Npad)); RC(t.E.ensure((size_t)Mpad * Mpad)); RC(t.R.ensure((size_t)Mpad * Mpad));
     RC(t.GA.ensure((size_t)Mpad * Mpad));
-    RC(t.gz.ensure((size_t)D * Mpad));
-    if (t.zero_col.n < (size_t)Mpad) { RC(t.zero_col.ensure(Mpad)); HIP_TRY(hipMemsetAsync(t.zero_col.p, 0, Mpad * sizeof(double), m->st)); }
     double* r = t.vec.p + Mpad;
     double* beta = t.vec.p + 4 * Mpad;
     double* dga = t.vec.p + 2 * Mpad;
@@ -295,58 +218,18 @@ int snelson_eval_impl(mogp_model* m, int64_t M, const double* Z, const double* n
     HIP_TRY(hipGetLastError());
     // E = I - Pq + 2 (v diag h) v^T;  GA = 1/2 L^-T E L^-1 (the - 1/2 beta beta^T goes through the moment kernel's rank-one term).  The M x M x N
     // product first (it needs the whole chip); the two M x M solves behind it go to the side stream, underneath the M x N solve below
-    hipLaunchKernelGGL(k_scale_cols, gmn, dim3(256), 0, m->st, t.v.p, t.B.p, Npad, Npad, h);
-    HIP_TRY(hipGetLastError());
+    RC(launch_scale_cols(t.v.p, t.B.p, Npad, Mpad, Npad, h, m->st));
     RC(mm_lower_splitk(m, t, t.B.p, t.v.p, t.R.p, mt, Mpad, Npad, Npad));
     if (sharded) RC(comm_allreduce(m->ctx, t.R.p, Mpad * Mpad, m->st));
     RC(launch_symmetrize(t.R.p, Mpad, Mpad, m->st));
     hipStream_t side;
     RC(side_fork(m, t, &side));
     RC(launch_combine(t.E.p, t.q.B.p, t.R.p, Mpad, Mpad, 1.0, 1.0, -2.0, side));
-    RC(trsm_lower(m, t.a.A.p, Mpad, mt, t.E.p, Mpad, Mpad, true, side));
-    RC(launch_transpose(t.GA.p, t.E.p, Mpad, Mpad, side));
-    RC(trsm_lower(m, t.a.A.p, Mpad, mt, t.GA.p, Mpad, Mpad, true, side));
-    RC(launch_sym_lower_avg(t.GA.p, Mpad, Mpad, 0.5, side));
-    RC(launch_get_diag(t.GA.p, Mpad, Mpad, dga, side));
+    RC(adjoint_GA(m, t, 0.5, side));                                            // its diagonal -> dga
     // GB = L^-T T, with beta = L^-T r riding along (padding column, or a panel of its own)
-    const bool ride = Npad > N;
-    if (ride) RC(launch_copy2d(t.GB.p + N, Npad, r, 1, Mpad, 1, 1.0, m->st));
-    RC(trsm_lower(m, t.a.A.p, Mpad, mt, t.GB.p, Npad, Npad, true));
-    if (ride) {
-        RC(launch_copy2d(beta, 1, t.GB.p + N, Npad, Mpad, 1, 1.0, m->st));
-        RC(launch_copy2d(t.GB.p + N, Npad, t.zero_col.p, 1, Mpad, 1, 1.0, m->st));
-    } else {
-        RC(t.Hm.ensure((size_t)Mpad * MOGP_TILE));
-        HIP_TRY(hipMemsetAsync(t.Hm.p, 0, (size_t)Mpad * MOGP_TILE * sizeof(double), m->st));
-        RC(launch_copy2d(t.Hm.p, MOGP_TILE, r, 1, Mpad, 1, 1.0, m->st));
-        RC(trsm_lower(m, t.a.A.p, Mpad, mt, t.Hm.p, MOGP_TILE, MOGP_TILE, true));
-        RC(launch_copy2d(beta, 1, t.Hm.p, MOGP_TILE, Mpad, 1, 1.0, m->st));
-    }
-    HIP_TRY(hipMemsetAsync(t.gz.p, 0, (size_t)D * Mpad * sizeof(double), m->st));
-    RC(gz_prepare(m, t, sz.off, D));
-
-    MomentArgs ma{};
-    ma.tiles = t.tiles_uf.p; ma.ntiles = (int)tuf.size(); ma.x = t.zx.p; ma.ldx = Mpad; ma.xc = m->d_x.p; ma.ldxc = Npad;
-    ma.nrows = M; ma.ncols = N;
-    RC(t.ph_zx.prepare(sz.off, m->sx.off, C, T, Mpad, Npad, m->st, ma.ph));
-    ma.table = m->d_table.p; ma.T = T; ma.D = D; ma.C = C; ma.W = W;
-    ma.G = t.GB.p; ma.ldg = Npad; ma.ru = beta; ma.rw = alpha; ma.rcoef = 0.0; ma.sym = 0;
-    ma.gzr = t.gz.p; ma.gzc = nullptr; ma.ldgz = Mpad; ma.partial = t.partial_uf.p;
-    gz_attach(t, ma, true);
-    RC(launch_moments(ma, m->st));
-    RC(launch_moment_reduce(t.partial_uf.p, t.ps_uf.p, C * C, T, W, D, t.mom_uf.p, m->st, 0));
-    if (sharded) {
-        RC(comm_allreduce(m->ctx, t.mom_uf.p, (int64_t)C * C * T * W, m->st));
-        RC(comm_allreduce(m->ctx, t.gz.p, (int64_t)D * Mpad, m->st));
-    }
-    RC(side_join(m, t, side));
-    ma.tiles = t.tiles_uu.p; ma.ntiles = (int)tuu.size(); ma.xc = nullptr; ma.ldxc = 0; ma.ncols = M;
-    RC(t.ph_zz.prepare(sz.off, sz.off, C, T, Mpad, Mpad, m->st, ma.ph));
-    ma.G = t.GA.p; ma.ldg = Mpad; ma.ru = beta; ma.rw = beta; ma.rcoef = -0.5; ma.sym = 1;
-    ma.gzr = t.gz.p; ma.gzc = t.gz.p; ma.partial = t.partial_uu.p;
-    gz_attach(t, ma, false);
-    RC(launch_moments(ma, m->st));
-    RC(launch_moment_reduce(t.partial_uu.p, t.ps_uu.p, P, T, W, D, t.mom_uu.p, m->st, 1));
+    RC(solve_with_rider(m, t, t.GB.p, r, beta));
+    const MomentSpec uf{t.GB.p, Npad, beta, alpha, 0.0, true}, uu{t.GA.p, Mpad, beta, beta, -0.5, true};
+    RC(sparse_moments(m, t, sz, &uf, uu, sharded, side));
 
     std::vector<double> hgz((size_t)D * Mpad), hb(Mpad), hd(Mpad), hh(Npad);
     HIP_TRY(hipMemcpyAsync(mom_uu, t.mom_uu.p, (size_t)P * T * W * sizeof(double), hipMemcpyDeviceToHost, m->st));
@@ -373,19 +256,32 @@ int snelson_eval_impl(mogp_model* m, int64_t M, const double* Z, const double* n
         for (int pos = m->sx.off[c]; pos < m->sx.off[c + 1]; ++pos) s += hh[pos];
         hsum[c] = s;
     }
-    if (sharded) {                               // sum of h over the points of a channel: one more small all-reduce
-        RC(t.red.ensure((size_t)Mpad + 4 + C));
-        HIP_TRY(hipMemcpyAsync(t.red.p, hsum, C * sizeof(double), hipMemcpyHostToDevice, m->st));
-        HIP_TRY(hipStreamSynchronize(m->st));
-        RC(comm_allreduce(m->ctx, t.red.p, C, m->st));
-        HIP_TRY(hipMemcpyAsync(hsum, t.red.p, C * sizeof(double), hipMemcpyDeviceToHost, m->st));
-        HIP_TRY(hipStreamSynchronize(m->st));
-    }
+    if (sharded) RC(allreduce_vec_scalars(m, t, nullptr, 0, hsum, C));      // sum of h over the points of a channel: one more small all-reduce
     return MOGP_OK;
 }
 
 int snelson_predict_impl(mogp_model* m, int64_t M, const double* Z, const double* noise_var, double jitter, const double* kff_diag,
-                         const double* kss_diag, int64_t S, const double* Xs, double* mu, double* var, int64_t* info, bool sharded);
+                         const double* kss_diag, int64_t S, const double* Xs, double* mu, double* var, int64_t* info, bool sharded) {
+    if (m) m->mean_w = nullptr;                 // dp/dr of an earlier gradient evaluation: this call may overwrite or regrow its buffer (mogp_model_fetch 3)
+    if (!m || !Z || !noise_var || !kff_diag || !kss_diag || !Xs || !mu || !var || M <= 0 || S <= 0)
+        return fail(MOGP_EINVAL, "mogp_snelson_predict: bad argument");
+    RC(use_device(m->ctx));
+    if (info) *info = 0;
+    SortedX sz, ss;
+    SnScalars sc;
+    RC(snelson_front(m, M, Z, noise_var, jitter, kff_diag, sz, sc, info, sharded));
+    TitsiasWork& t = *m->tw;
+    const int64_t Mpad = t.Mpad;
+    RC(sparse_predict_panels(m, t, sz, S, Xs, ss));                                                        // a = L^-1 Kus
+    const int64_t Spad = ss.Mpad;
+    const int mt = (int)(Mpad / MOGP_TILE), st = (int)(Spad / MOGP_TILE);
+    GemmArgs g = make_gemm(t.Wq, Mpad, 0, t.Aus.p, Spad, 1, t.Bus.p, Spad, 1.0, GM_KHI_I, mt, st, Mpad);          // b = Lq^-1 a
+    RC(gemm_call(m, g, gemm_flops(g, nullptr)));
+    double* vGy = t.vec.p;
+    double* cvec = t.vec.p + 4 * Mpad;
+    RC(launch_trmv_lower(t.Wq, Mpad, Mpad, vGy, cvec, t.vec.p + 6 * Mpad, m->st));                         // c = Lq^-1 v G y
+    return sparse_predict_finish(m, t, ss, t.Bus.p, cvec, 1.0, kss_diag, mu, var);                         // mu = b^T c
+}
 
 }  // namespace
 
@@ -413,61 +309,3 @@ int mogp_snelson_predict_sharded(mogp_model* m, int64_t M, const double* Z, cons
 }
 
 }  // extern "C"
-
-namespace {
-
-int snelson_predict_impl(mogp_model* m, int64_t M, const double* Z, const double* noise_var, double jitter, const double* kff_diag,
-                         const double* kss_diag, int64_t S, const double* Xs, double* mu, double* var, int64_t* info, bool sharded) {
-    if (m) m->mean_w = nullptr;                 // dp/dr of an earlier gradient evaluation: this call may overwrite or regrow its buffer (mogp_model_fetch 3)
-    if (!m || !Z || !noise_var || !kff_diag || !kss_diag || !Xs || !mu || !var || M <= 0 || S <= 0)
-        return fail(MOGP_EINVAL, "mogp_snelson_predict: bad argument");
-    RC(use_device(m->ctx));
-    if (info) *info = 0;
-    const int C = m->C, D = m->D;
-    const bool env = m->Wt > 2 + 3 * D;
-    SortedX sz, ss;
-    std::vector<GTile> tuu, tuf, tus;
-    std::vector<int> psuu, psuf;
-    SnScalars sc;
-    RC(snelson_front(m, M, Z, noise_var, jitter, kff_diag, sz, tuu, psuu, tuf, psuf, sc, info, false, sharded));
-    TitsiasWork& t = *m->tw;
-    const int64_t Mpad = t.Mpad;
-    RC(sort_inputs(Xs, S, D, C, MOGP_TILE, ss));
-    const int64_t Spad = ss.Mpad;
-    const int mt = (int)(Mpad / MOGP_TILE), st = (int)(Spad / MOGP_TILE);
-    build_rect_tiles(sz.off, ss.off, C, tus);
-    RC(t.Kus.ensure((size_t)Mpad * Spad)); RC(t.Aus.ensure((size_t)Mpad * Spad)); RC(t.Bus.ensure((size_t)Mpad * Spad));
-    RC(m->d_xs.ensure((size_t)D * Spad)); RC(m->d_ptiles.ensure(tus.size()));
-    RC(m->d_mu.ensure(Spad)); RC(m->d_var.ensure(2 * Spad));
-    HIP_TRY(hipMemcpyAsync(m->d_xs.p, ss.xs.data(), (size_t)D * Spad * sizeof(double), hipMemcpyHostToDevice, m->st));
-    HIP_TRY(hipMemcpyAsync(m->d_ptiles.p, tus.data(), tus.size() * sizeof(GTile), hipMemcpyHostToDevice, m->st));
-    HIP_TRY(hipMemsetAsync(t.Kus.p, 0, (size_t)Mpad * Spad * sizeof(double), m->st));
-    GramArgs ga{};
-    ga.tiles = m->d_ptiles.p; ga.xr = t.zx.p; ga.ldxr = Mpad; ga.xc = m->d_xs.p; ga.ldxc = Spad; ga.nrows = M; ga.ncols = S;
-    RC(t.ph_zs.prepare(sz.off, ss.off, C, m->T, Mpad, Spad, m->st, ga.ph));
-    ga.table = m->d_table.p; ga.T = m->T; ga.D = D; ga.C = C; ga.W = m->Wt; ga.out = t.Kus.p; ga.ldo = Spad; ga.mirror = 0;
-    RC(launch_gram(ga, (int)tus.size(), m->st));
-    HIP_TRY(hipMemcpyAsync(t.Aus.p, t.Kus.p, (size_t)Mpad * Spad * sizeof(double), hipMemcpyDeviceToDevice, m->st));
-    RC(trsm_lower(m, t.a.A.p, Mpad, mt, t.Aus.p, Spad, Spad, false));                                      // a = L^-1 Kus
-    GemmArgs g = make_gemm(t.Wq, Mpad, 0, t.Aus.p, Spad, 1, t.Bus.p, Spad, 1.0, GM_KHI_I, mt, st, Mpad);          // b = Lq^-1 a
-    RC(gemm_call(m, g, gemm_flops(g, nullptr)));
-    double* vGy = t.vec.p;
-    double* cvec = t.vec.p + 4 * Mpad;
-    RC(launch_trmv_lower(t.Wq, Mpad, Mpad, vGy, cvec, t.vec.p + 6 * Mpad, m->st));                         // c = Lq^-1 v G y
-    RC(launch_gemv_cols(t.Bus.p, Spad, Mpad, Spad, cvec, m->d_mu.p, t.scratch.p, m->st));                  // mu = b^T c
-    RC(launch_gemv_cols(t.Aus.p, Spad, Mpad, Spad, nullptr, m->d_var.p, t.scratch.p, m->st));
-    RC(launch_gemv_cols(t.Bus.p, Spad, Mpad, Spad, nullptr, m->d_var.p + Spad, t.scratch.p, m->st));
-    std::vector<double> hmu(Spad), hv(2 * Spad);
-    HIP_TRY(hipMemcpyAsync(hmu.data(), m->d_mu.p, Spad * sizeof(double), hipMemcpyDeviceToHost, m->st));
-    HIP_TRY(hipMemcpyAsync(hv.data(), m->d_var.p, 2 * Spad * sizeof(double), hipMemcpyDeviceToHost, m->st));
-    HIP_TRY(hipStreamSynchronize(m->st));
-    RC(sparse_timeout_check(m));
-    for (int c = 0; c < C; ++c)
-        for (int pos = ss.off[c]; pos < ss.off[c + 1]; ++pos) {
-            mu[ss.perm[pos]] = hmu[pos];
-            var[ss.perm[pos]] = (env ? kss_diag[ss.perm[pos]] : kss_diag[c]) - hv[pos] + hv[Spad + pos];     // envelope: K_ss,diag per test point
-        }
-    return MOGP_OK;
-}
-
-}  // namespace

@@ -18,144 +18,9 @@
 #include <cstring>
 #include <limits>
 
-namespace mogp {
-int launch_potrf_trtri_tile(double* A, int64_t ld, int t, double* invd, double* logdet, unsigned long long* info, hipStream_t s,
-                            long long info_base = 0, int store_L = 0);
-}
 using namespace mogp;
 
 #define RC(x) do { int r__ = (x); if (r__) return r__; } while (0)
-
-
-
-namespace mogp {
-
-int side_fork(mogp_model* m, TitsiasWork& t, hipStream_t* side) {
-    static const bool on = !(std::getenv("MOGP_SIDE_STREAM") && std::atoi(std::getenv("MOGP_SIDE_STREAM")) == 0);
-    *side = m->st;
-    if (!on || !m->st3) return 0;
-    for (auto& e : t.side_ev) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(t.side_ev[0], m->st));
-    HIP_TRY(hipStreamWaitEvent(m->st3, t.side_ev[0], 0));
-    *side = m->st3;
-    return 0;
-}
-
-int side_join(mogp_model* m, TitsiasWork& t, hipStream_t side) {
-    if (side == m->st) return 0;
-    HIP_TRY(hipEventRecord(t.side_ev[1], side));
-    HIP_TRY(hipStreamWaitEvent(m->st, t.side_ev[1], 0));
-    return 0;
-}
-
-// defer_check: the caller reads the pivot word itself at its next synchronisation (a failed factorisation then runs on with garbage: bounded, harmless)
-int spd_invert(mogp_model* m, Spd& w, const char* which, int64_t* info, const double** W, bool defer_check) {
-    static const bool fused = std::getenv("MOGP_SPARSE_FUSED") && std::atoi(std::getenv("MOGP_SPARSE_FUSED")) != 0;
-    if (fused && w.nb <= 80) {
-        RC(spd_potri_fused(m, w));
-        RC(spd_potri_fused_finish(m, w));
-        if (!defer_check) RC(spd_check_info(m, which, info));
-        *W = w.Wm.p;
-        return 0;
-    }
-    RC(spd_potrf(m, w));
-    if (!defer_check) RC(spd_check_info(m, which, info));
-    RC(spd_trtri(m, w));                                                        // w.A = L^-1
-    RC(spd_lauum(m, w));                                                        // w.B = inverse (lower)
-    *W = w.A.p;
-    return 0;
-}
-
-int gz_prepare(mogp_model* m, TitsiasWork& t, const std::vector<int>& offz, int D) {
-    std::vector<int> hz, hx;
-    tile_blocks(offz, m->C, hz);
-    tile_blocks(m->sx.off, m->C, hx);
-    if (hz != t.hblk_z) {
-        RC(t.blk_z.ensure(hz.size()));
-        t.hblk_z = hz;
-        HIP_TRY(hipMemcpyAsync(t.blk_z.p, t.hblk_z.data(), hz.size() * sizeof(int), hipMemcpyHostToDevice, m->st));
-    }
-    if (hx != t.hblk_x) {
-        RC(t.blk_x.ensure(hx.size()));
-        t.hblk_x = hx;
-        HIP_TRY(hipMemcpyAsync(t.blk_x.p, t.hblk_x.data(), hx.size() * sizeof(int), hipMemcpyHostToDevice, m->st));
-    }
-    const int nbz = (int)hz.size() / 2, nbx = (int)hx.size() / 2;
-    return t.gzp.ensure(gz_scratch_doubles(nbz, std::max(nbz, nbx), D));
-}
-
-void gz_attach(const TitsiasWork& t, MomentArgs& ma, bool zx) {
-    ma.gzp = t.gzp.p;
-    ma.nrb = (int)t.hblk_z.size() / 2; ma.rblk = t.blk_z.p;
-    ma.ncb = zx ? (int)t.hblk_x.size() / 2 : ma.nrb; ma.cblk = zx ? t.blk_x.p : t.blk_z.p;
-}
-
-int spd_check_info(mogp_model* m, const char* which, int64_t* info) {
-    unsigned long long hinfo = 0;
-    HIP_TRY(hipMemcpyAsync(&hinfo, m->d_info.p, sizeof(hinfo), hipMemcpyDeviceToHost, m->st));
-    HIP_TRY(hipStreamSynchronize(m->st));
-    return spd_info_verdict(m, which, hinfo, info);
-}
-
-int spd_info_verdict(mogp_model* m, const char* which, unsigned long long hinfo, int64_t* info) {
-    if (hinfo == MOGP_INFO_CHAIN_TIMEOUT) {
-        m->no_chain = true;                                  // gates the chain kernel AND the stream-K launches (mogp_api.hip:stream_k_setup)
-        return fail(MOGP_EHIP, "a hand-off between workgroups timed out (chain kernel, chain.hip, or a stream-K GEMM, linalg.hip:k_gemm_sk: the GPU is "
-                               "shared with another process?).  The model has switched both forms off, as MOGP_CHAIN=0 and MOGP_SK=0 do: repeat the call");
-    }
-    if (hinfo != std::numeric_limits<unsigned long long>::max()) {
-        if (info) *info = (int64_t)hinfo;
-        return fail(MOGP_ENOTPD, std::string("linalg.cholesky: ") + which + " is not positive-definite (the leading minor of order " +
-                                 std::to_string(hinfo) + " is not positive-definite).");
-    }
-    return 0;
-}
-
-int sparse_timeout_check(mogp_model* m) {
-    unsigned long long hinfo = 1;
-    HIP_TRY(hipMemcpy(&hinfo, m->d_info.p, sizeof(hinfo), hipMemcpyDeviceToHost));     // the caller has just synchronised the stream
-    if (hinfo != MOGP_INFO_CHAIN_TIMEOUT) return 0;
-    m->no_chain = true;
-    return fail(MOGP_EHIP, "a hand-off between workgroups timed out during this evaluation (stream-K GEMM of a triangular solve, linalg.hip:k_gemm_sk, "
-                           "or the chain kernel: the GPU is shared with another process?): its result is not valid.  The model has switched both forms "
-                           "off, as MOGP_SK=0 and MOGP_CHAIN=0 do: repeat the call");
-}
-
-// mt (mt + 1) / 2 = 136 tiles at configs[4] would leave half the chip idle over K = N: K is cut into ks slices, each slice into a block of
-// its own, and the blocks are summed.  ks minimises rounds(tiles ks / 512 slots) / ks: 136 tiles -> ks = 15, 2040 workgroups = four
-// full rounds (two slices left every second CU with two workgroups and the rest with one: 12.5 ms; fifteen: see DESIGN 4b)
-int mm_lower_splitk(mogp_model* m, TitsiasWork& t, const double* A, const double* B, double* out, int mt, int64_t Mpad, int64_t ldk, int64_t K,
-                    double alpha) {
-    GemmArgs g = make_gemm(A, ldk, 0, B, ldk, 0, out, Mpad, alpha, GM_LOWER, mt, mt, K);
-    const int tiles_q = mt * (mt + 1) / 2;
-    int ks = 1;
-    static const int ks_env = []() { const char* e = std::getenv("MOGP_SYRK_KS"); return e ? atoi(e) : 0; }();      // > 0: that many slices, slice-major; < 0: |.| slices, one XCD each
-    if (tiles_q < 512 && K >= 4096) {
-        double best = 1e30;
-        for (int c = 1; c <= 16; ++c) {
-            if (K / c < 2048) break;
-            const double cost = std::ceil((double)tiles_q * c / 512.0) / c;
-            if (cost < best - 1e-12) { best = cost; ks = c; }
-        }
-        // (round 4: eight or sixteen slices, each on ONE XCD -- k_gemm: ksplit_xcd, the workgroups that share an L2 then share a k window as well --
-        // measured no faster than fifteen slice-major ones, 45.4 vs 45.3 ms at configs[4], although those fetch 12.4 GB for 1.6 GB of v: the product is
-        // not bound by that traffic; kept as a switch)
-        if (ks_env > 0) ks = ks_env;
-        if (ks_env < 0) { ks = -ks_env; g.ksplit_xcd = (ks % 8 == 0); }
-    }
-    if (ks > 1) {
-        if (t.kslices.n < (size_t)ks * Mpad * Mpad) {         // the upper tiles are never written: keep them finite
-            RC(t.kslices.ensure((size_t)ks * Mpad * Mpad));
-            HIP_TRY(hipMemsetAsync(t.kslices.p, 0, (size_t)ks * Mpad * Mpad * sizeof(double), m->st));
-        }
-        g.C = t.kslices.p; g.ksplit = ks; g.c_split = (int64_t)Mpad * Mpad;
-    }
-    RC(gemm_call(m, g, gemm_flops(g, nullptr)));
-    if (ks > 1) RC(launch_sum_slices(t.kslices.p, (int64_t)Mpad * Mpad, ks, out, m->st));
-    return 0;
-}
-
-}  // namespace mogp
 
 // Common front end: sort Z, build tiles, Kuu -> W (in tw.a.A), Kuf -> tw.B, v -> tw.v, Qs -> tw.Qs, Wq (tw.q.A), Pq (tw.q.B, full),
 // vy, t1 in tw.vec[0 : Mpad], tw.vec[Mpad : 2 Mpad].  Host scalars through `sc`.
@@ -164,81 +29,19 @@ struct TitsiasScalars { double logdet_q, yy, t1vy, t1t1, trPq, trQs, jit, ntot, 
 // sharded: this handle holds ONE SHARD of the training points (the ranks of the context's communicator hold the others; Z, sigma and the
 // terms are the same everywhere).  Everything that sums over data points -- v v^T, v y, y^T y, N, sum K_ff,nn -- is all-reduced, after which
 // every M x M quantity is the full model's on every rank (two collectives: Mpad^2 doubles and Mpad + 3).
-static int titsias_front(mogp_model* m, int64_t M, const double* Z, double sigma, double jitter, SortedX& sz,
-                         std::vector<GTile>& tuu, std::vector<int>& psuu, std::vector<GTile>& tuf, std::vector<int>& psuf,
-                         TitsiasScalars& sc, int64_t* info, bool need_moment_tiles, bool sharded = false, const double* kff_diag = nullptr) {
-    const int C = m->C, D = m->D, W = m->Wt;                   // 2 + 3 D, or 2 + 5 D: terms with an envelope on the input midpoint (MOHSM)
-    const bool env = W > 2 + 3 * D;
-    const int64_t Npad = m->Npad;
-    if (m->T <= 0) return fail(MOGP_EINVAL, "mogp_model_set_terms must be called before an evaluation");
+static int titsias_front(mogp_model* m, int64_t M, const double* Z, double sigma, double jitter, SortedX& sz, TitsiasScalars& sc, int64_t* info,
+                         bool sharded = false, const double* kff_diag = nullptr) {
     if (!(sigma > 0.0)) return fail(MOGP_EINVAL, "sigma must be positive");
-    RC(sort_inputs(Z, M, D, C, MOGP_TILE, sz));
-    const int64_t Mpad = sz.Mpad;
-    if (!m->tw) m->tw = new TitsiasWork();
+    RC(sparse_kuu(m, M, Z, jitter, true, sz, &sc.jit));
     TitsiasWork& t = *m->tw;
-    const int mt = (int)(Mpad / MOGP_TILE), nt = (int)(Npad / MOGP_TILE);
-    if (t.Mpad != Mpad) {
-        t.Mpad = Mpad;
-        RC(spd_alloc(t.a, Mpad)); RC(spd_alloc(t.q, Mpad));
-        RC(t.zx.ensure((size_t)D * Mpad));
-        RC(t.B.ensure((size_t)Mpad * Npad)); RC(t.v.ensure((size_t)Mpad * Npad));
-        RC(t.Qs.ensure((size_t)Mpad * Mpad));
-        RC(t.vec.ensure((size_t)8 * Mpad + 4 * Npad));
-        RC(t.scratch.ensure((size_t)(Mpad / 256 + 2) * std::max(Npad, Mpad) + (size_t)(Mpad / 512 + 2) * Mpad));
-        RC(t.zero_noise.ensure(C));
-        { int r__ = dev_fill_zero(t.zero_noise.p, C * sizeof(double)); if (r__) return r__; }
-        { int r__ = dev_fill_zero(t.B.p, (size_t)Mpad * Npad * sizeof(double)); if (r__) return r__; }      // padding of Kuf stays zero: the Gram kernel never writes it
-        { int r__ = dev_fill_zero(t.v.p, (size_t)Mpad * Npad * sizeof(double)); if (r__) return r__; }      // ... nor that of its working copy (the solves keep zeros zero)
-    }
-    m->gemm_ev_used = 0; m->gemm_launches = 0; m->gemm_flops = 0.0;
-    HIP_TRY(hipMemcpyAsync(t.zx.p, sz.xs.data(), (size_t)D * Mpad * sizeof(double), hipMemcpyHostToDevice, m->st));
-    // the tile lists depend on the channel offsets of Z and X only: built and uploaded when those change, not per evaluation (50 000 tiles and 1.2 MB
-    // of pageable copies at configs[4], all of it in front of the evaluation's first kernel); the (Z, X) list also as strip-kernel runs
-    std::vector<int> key(sz.off);
-    key.insert(key.end(), m->sx.off.begin(), m->sx.off.end());
-    if (key != t.tile_key) {
-        t.tile_key.clear();
-        build_sym_tiles(sz.off, C, tuu, psuu);
-        build_rect_tiles(sz.off, m->sx.off, C, tuf, &psuf);
-        HIP_TRY(hipStreamSynchronize(m->st));                   // a previous evaluation's kernels may still read the lists (first call / a new Z layout only)
-        RC(t.tiles_uu.ensure(tuu.size())); RC(t.tiles_uf.ensure(tuf.size()));
-        HIP_TRY(dev_upload(t.tiles_uu.p, tuu.data(), tuu.size() * sizeof(GTile)));
-        HIP_TRY(dev_upload(t.tiles_uf.p, tuf.data(), tuf.size() * sizeof(GTile)));
-        RC(t.strip_uf.build(tuf));
-        RC(t.ps_uu.ensure(psuu.size())); RC(t.ps_uf.ensure(psuf.size()));
-        HIP_TRY(dev_upload(t.ps_uu.p, psuu.data(), psuu.size() * sizeof(int)));
-        HIP_TRY(dev_upload(t.ps_uf.p, psuf.data(), psuf.size() * sizeof(int)));
-        t.n_tuu = tuu.size(); t.n_tuf = tuf.size();
-        t.tile_key = key;
-    }
-    if (need_moment_tiles) {
-        RC(t.partial_uu.ensure(t.n_tuu * (size_t)m->T * W)); RC(t.partial_uf.ensure(t.n_tuf * (size_t)m->T * W));
-        RC(t.mom_uu.ensure((size_t)(C * (C + 1) / 2) * m->T * W)); RC(t.mom_uf.ensure((size_t)C * C * m->T * W));
-    }
-    const unsigned long long big = std::numeric_limits<unsigned long long>::max();
-    HIP_TRY(hipMemcpyAsync(m->d_info.p, &big, sizeof(big), hipMemcpyHostToDevice, m->st));
-
-    // relative jitter on Kuu (reference gpr/model.py:710 -> :244)
-    sc.jit = jitter * table_diag_points(m, sz) / (double)M;    // with an envelope the diagonal of Kuu follows the inducing inputs
-
-    GramArgs ga{};
-    ga.tiles = t.tiles_uu.p; ga.xr = t.zx.p; ga.xc = t.zx.p; ga.ldxr = ga.ldxc = Mpad; ga.nrows = ga.ncols = M;
-    RC(t.ph_zz.prepare(sz.off, sz.off, C, m->T, Mpad, Mpad, m->st, ga.ph));
-    ga.table = m->d_table.p; ga.T = m->T; ga.D = D; ga.C = C; ga.W = W; ga.out = t.a.A.p; ga.ldo = Mpad;
-    ga.noise = t.zero_noise.p; ga.dvar = nullptr; ga.jitter_abs = sc.jit; ga.mirror = 0;
-    RC(launch_gram(ga, (int)t.n_tuu, m->st));
-    RC(launch_pad_identity(t.a.A.p, Mpad, M, Mpad, m->st));
+    const int C = m->C;
+    const bool env = m->Wt > 2 + 3 * m->D;                     // terms with an envelope on the input midpoint (MOHSM)
+    const int64_t Mpad = t.Mpad, Npad = m->Npad;
+    const int mt = (int)(Mpad / MOGP_TILE);
     // Kuf and its working copy on the side stream, underneath the (chain-bound) factorisation of Kuu
     hipStream_t side;
     RC(side_fork(m, t, &side));
-    ga.tiles = t.tiles_uf.p; ga.xc = m->d_x.p; ga.ldxc = Npad; ga.ncols = m->N; ga.out = t.B.p; ga.ldo = Npad; ga.noise = nullptr; ga.jitter_abs = 0.0;
-    ga.out2 = t.v.p;                                                            // the copy the solve below works in, written by the same kernel
-    t.strip_uf.attach(ga);                                                      // full interior tiles in runs of four on the strip kernel
-    RC(t.ph_zx.prepare(sz.off, m->sx.off, C, m->T, Mpad, Npad, side, ga.ph));
-    RC(launch_gram(ga, (int)t.n_tuf, side));
-
-    t.a.keep_L = true;                                                          // the solves below need L itself, diagonal tiles included
-    t.a.refine_panels = !(std::getenv("MOGP_REFINE_PANELS") && std::atoi(std::getenv("MOGP_REFINE_PANELS")) == 0);   // K_uu + jitter is ill-conditioned: mogp_api.hip:spd_potrf
+    RC(sparse_kuf(m, t, sz, side, true, t.v.p));                                // t.v: the copy the solve below works in, written by the same kernel
     // (round 5, measured and dropped: the chain of this factorisation on the CU-masked private stream, so that its one-workgroup kernels do not share
     // a CU with the K_uf Gram waves -- configs[4] 39.7-39.9 vs 39.3-39.5 ms, bit-identical: the panel and next-column products of the chain are
     // slower on 16 CUs than the leaves gain)
@@ -264,7 +67,6 @@ static int titsias_front(mogp_model* m, int64_t M, const double* Z, double sigma
         RC(side_join(m, t, side));
         RC(trsm_lower(m, t.a.A.p, Mpad, mt, t.v.p, Npad, Npad, false));          // v = L^-1 B   (reference gpr/model.py:711)
     }
-    (void)nt;
     // Qs = v v^T / s2 + I, with v y (one memory-bound pass over v) underneath the compute-bound product
     double* vy = t.vec.p;
     RC(side_fork(m, t, &side));
@@ -278,15 +80,8 @@ static int titsias_front(mogp_model* m, int64_t M, const double* Z, double sigma
     else if (kff_diag) for (int c = 0; c < C; ++c) sc.kff += (double)(m->sx.off[c + 1] - m->sx.off[c]) * kff_diag[c];
     if (sharded) {
         RC(comm_allreduce(m->ctx, t.q.A.p, Mpad * Mpad, m->st));
-        RC(t.red.ensure((size_t)Mpad + 4));
         double hs[3] = {sc.yy, sc.ntot, sc.kff};
-        HIP_TRY(hipMemcpyAsync(t.red.p, vy, Mpad * sizeof(double), hipMemcpyDeviceToDevice, m->st));
-        HIP_TRY(hipMemcpyAsync(t.red.p + Mpad, hs, sizeof(hs), hipMemcpyHostToDevice, m->st));
-        HIP_TRY(hipStreamSynchronize(m->st));                                   // hs is a stack buffer
-        RC(comm_allreduce(m->ctx, t.red.p, Mpad + 3, m->st));
-        HIP_TRY(hipMemcpyAsync(vy, t.red.p, Mpad * sizeof(double), hipMemcpyDeviceToDevice, m->st));
-        HIP_TRY(hipMemcpyAsync(hs, t.red.p + Mpad, sizeof(hs), hipMemcpyDeviceToHost, m->st));
-        HIP_TRY(hipStreamSynchronize(m->st));
+        RC(allreduce_vec_scalars(m, t, vy, Mpad, hs, 3));
         sc.yy = hs[0]; sc.ntot = hs[1]; sc.kff = hs[2];
     }
     RC(launch_add_diag(t.q.A.p, Mpad, Mpad, 1.0, m->st));
@@ -296,19 +91,9 @@ static int titsias_front(mogp_model* m, int64_t M, const double* Z, double sigma
     RC(launch_symmetrize(t.q.B.p, Mpad, Mpad, m->st));
     double* t1 = t.vec.p + Mpad;
     double* dg = t.vec.p + 2 * Mpad;                                            // diag Pq, diag Qs
-    // t1 = Pq (v y): the explicit inverse plus ONE step of iterative refinement against Qs.  Of the three places Pq enters the gradient,
-    // this vector is the one where the explicitly formed inverse costs accuracy on dELBO/dZ (tools/titsias_numerics.py: 1.3e-4 -> 7e-5, the
-    // same as two triangular solves with Lq), and three M x M mat-vecs are far cheaper than 2 nb dependent launches of a vector solve
+    // t1 = Pq (v y): the explicit inverse plus ONE step of iterative refinement against Qs (see refined_apply)
     RC(launch_symmetrize(t.Qs.p, Mpad, Mpad, m->st));
-    {
-        double* tmp = t.vec.p + 5 * Mpad;
-        double* res = t.vec.p + 6 * Mpad;
-        RC(launch_gemv_rows(t.q.B.p, Mpad, Mpad, Mpad, vy, t1, m->st));
-        RC(launch_gemv_rows(t.Qs.p, Mpad, Mpad, Mpad, t1, tmp, m->st));
-        RC(launch_axpby(Mpad, 1.0, vy, -1.0, tmp, res, m->st));
-        RC(launch_gemv_rows(t.q.B.p, Mpad, Mpad, Mpad, res, tmp, m->st));
-        RC(launch_axpby(Mpad, 1.0, t1, 1.0, tmp, t1, m->st));
-    }
+    RC(refined_apply(m, t, t.q.B.p, t.Qs.p, vy, t1));
     RC(launch_get_diag(t.q.B.p, Mpad, Mpad, dg, m->st));
     RC(launch_get_diag(t.Qs.p, Mpad, Mpad, dg + Mpad, m->st));
     const int nbq = t.q.nb;
@@ -337,13 +122,11 @@ static int titsias_eval_impl(mogp_model* m, int64_t M, const double* Z, double s
     RC(use_device(m->ctx));
     if (info) *info = 0;
     const int C = m->C, D = m->D, W = m->Wt, T = m->T, P = C * (C + 1) / 2;
-    const int64_t N = m->N, Npad = m->Npad;
+    const int64_t Npad = m->Npad;
     const bool grad = (flags & MOGP_EVAL_GRAD) != 0;
     SortedX sz;
-    std::vector<GTile> tuu, tuf;
-    std::vector<int> psuu, psuf;
     TitsiasScalars sc;
-    RC(titsias_front(m, M, Z, sigma, jitter, sz, tuu, psuu, tuf, psuf, sc, info, grad, sharded, kff_diag));
+    RC(titsias_front(m, M, Z, sigma, jitter, sz, sc, info, sharded, kff_diag));
     TitsiasWork& t = *m->tw;
     const int64_t Mpad = t.Mpad;
     const int mt = (int)(Mpad / MOGP_TILE), nt = (int)(Npad / MOGP_TILE);
@@ -363,9 +146,6 @@ static int titsias_eval_impl(mogp_model* m, int64_t M, const double* Z, double s
 
     RC(t.GB.ensure((size_t)Mpad * Npad)); RC(t.E.ensure((size_t)Mpad * Mpad)); RC(t.R.ensure((size_t)Mpad * Mpad));
     RC(t.GA.ensure((size_t)Mpad * Mpad));
-    RC(t.gz.ensure((size_t)D * Mpad));
-    if (t.zero_col.n < (size_t)Mpad) { RC(t.zero_col.ensure(Mpad)); HIP_TRY(hipMemsetAsync(t.zero_col.p, 0, Mpad * sizeof(double), m->st)); }
-    double* vy = t.vec.p; (void)vy;
     double* t1 = t.vec.p + Mpad;
     double* beta = t.vec.p + 4 * Mpad;            // [Mpad] (+ chunk scratch behind it, see launch_trmv_lower_t)
     double* dga = t.vec.p + 2 * Mpad;             // reuse: diag of GA
@@ -415,52 +195,13 @@ static int titsias_eval_impl(mogp_model* m, int64_t M, const double* Z, double s
     } else
     RC(gemm_call(m, g, gemm_flops(g, nullptr)));
     RC(launch_combine(t.E.p, t.q.B.p, t.Qs.p, Mpad, Mpad, 2.0, 1.0, 1.0, side));
-    RC(trsm_lower(m, t.a.A.p, Mpad, mt, t.E.p, Mpad, Mpad, true, side));
-    RC(launch_transpose(t.GA.p, t.E.p, Mpad, Mpad, side));
-    RC(trsm_lower(m, t.a.A.p, Mpad, mt, t.GA.p, Mpad, Mpad, true, side));
-    RC(launch_sym_lower_avg(t.GA.p, Mpad, Mpad, 0.5, side));
-    RC(launch_get_diag(t.GA.p, Mpad, Mpad, dga, side));
-    const bool ride = Npad > N && !gb_first;
-    if (ride) RC(launch_copy2d(t.GB.p + N, Npad, t1, 1, Mpad, 1, 1.0, m->st));
-    if (!gb_first) RC(trsm_lower(m, t.a.A.p, Mpad, mt, t.GB.p, Npad, Npad, true));
-    if (ride) {
-        RC(launch_copy2d(beta, 1, t.GB.p + N, Npad, Mpad, 1, 1.0, m->st));
-        RC(launch_copy2d(t.GB.p + N, Npad, t.zero_col.p, 1, Mpad, 1, 1.0, m->st));          // the padding column is zero again
-    } else {
-        RC(t.Hm.ensure((size_t)Mpad * MOGP_TILE));
-        HIP_TRY(hipMemsetAsync(t.Hm.p, 0, (size_t)Mpad * MOGP_TILE * sizeof(double), m->st));
-        RC(launch_copy2d(t.Hm.p, MOGP_TILE, t1, 1, Mpad, 1, 1.0, m->st));
-        RC(trsm_lower(m, t.a.A.p, Mpad, mt, t.Hm.p, MOGP_TILE, MOGP_TILE, true));
-        RC(launch_copy2d(beta, 1, t.Hm.p, MOGP_TILE, Mpad, 1, 1.0, m->st));
-    }
+    RC(adjoint_GA(m, t, 0.5, side));                                            // its diagonal -> dga
+    RC(solve_with_rider(m, t, gb_first ? nullptr : t.GB.p, t1, beta));          // gb_first: GB is finished above, beta alone is solved for
     RC(launch_gemv_cols(t.B.p, Npad, Mpad, Npad, beta, btb, t.scratch.p, m->st));                           // B^T beta
     RC(launch_axpby(Npad, 1.0 / (s2 * s2), m->d_y.p, -1.0 / (s2 * s2 * s2), btb, r, m->st));
-    HIP_TRY(hipMemsetAsync(t.gz.p, 0, (size_t)D * Mpad * sizeof(double), m->st));
-    RC(gz_prepare(m, t, sz.off, D));
-
-    MomentArgs ma{};
-    gz_attach(t, ma, true);
-    ma.tiles = t.tiles_uf.p; ma.ntiles = (int)t.n_tuf; ma.x = t.zx.p; ma.ldx = Mpad; ma.xc = m->d_x.p; ma.ldxc = Npad;
-    ma.nrows = M; ma.ncols = N;
-    RC(t.ph_zx.prepare(sz.off, m->sx.off, C, T, Mpad, Npad, m->st, ma.ph));
-    ma.table = m->d_table.p; ma.T = T; ma.D = D; ma.C = C; ma.W = W;
-    ma.G = t.GB.p; ma.ldg = Npad; ma.ru = beta; ma.rw = r; ma.rcoef = 1.0; ma.sym = 0;
-    ma.gzr = t.gz.p; ma.gzc = nullptr; ma.ldgz = Mpad; ma.partial = t.partial_uf.p;
     if (aside) HIP_TRY(hipStreamWaitEvent(m->st, t.prod_ev[1], 0));       // GB is there
-    RC(launch_moments(ma, m->st));
-    RC(launch_moment_reduce(t.partial_uf.p, t.ps_uf.p, C * C, T, W, D, t.mom_uf.p, m->st, 0));
-    if (sharded) {                       // the (Z, X) moments and their share of d/dZ are sums over data points; the (Z, Z) pass below is not
-        RC(comm_allreduce(m->ctx, t.mom_uf.p, (int64_t)C * C * T * W, m->st));
-        RC(comm_allreduce(m->ctx, t.gz.p, (int64_t)D * Mpad, m->st));
-    }
-    RC(side_join(m, t, side));
-    ma.tiles = t.tiles_uu.p; ma.ntiles = (int)t.n_tuu; ma.xc = nullptr; ma.ldxc = 0; ma.ncols = M;
-    RC(t.ph_zz.prepare(sz.off, sz.off, C, T, Mpad, Mpad, m->st, ma.ph));
-    ma.G = t.GA.p; ma.ldg = Mpad; ma.ru = beta; ma.rw = beta; ma.rcoef = -0.5 / (s2 * s2); ma.sym = 1;
-    ma.gzr = t.gz.p; ma.gzc = t.gz.p; ma.partial = t.partial_uu.p;
-    gz_attach(t, ma, false);
-    RC(launch_moments(ma, m->st));
-    RC(launch_moment_reduce(t.partial_uu.p, t.ps_uu.p, P, T, W, D, t.mom_uu.p, m->st, 1));
+    const MomentSpec uf{t.GB.p, Npad, beta, r, 1.0, true}, uu{t.GA.p, Mpad, beta, beta, -0.5 / (s2 * s2), true};
+    RC(sparse_moments(m, t, sz, &uf, uu, sharded, side));
 
     std::vector<double> hgz((size_t)D * Mpad), hb(Mpad), hd(Mpad);
     HIP_TRY(hipMemcpyAsync(mom_uu, t.mom_uu.p, (size_t)P * T * W * sizeof(double), hipMemcpyDeviceToHost, m->st));
@@ -478,12 +219,31 @@ static int titsias_eval_impl(mogp_model* m, int64_t M, const double* Z, double s
     double tr = 0.0;
     for (int64_t i = 0; i < M; ++i) tr += hd[i] - 0.5 * hb[i] * hb[i] / (s2 * s2);
     *trGA = tr;
-    (void)N;
     return MOGP_OK;
 }
 
 static int titsias_predict_impl(mogp_model* m, int64_t M, const double* Z, double sigma, double jitter, const double* kss_diag,
-                                int64_t S, const double* Xs, double* mu, double* var, int64_t* info, bool sharded);
+                                int64_t S, const double* Xs, double* mu, double* var, int64_t* info, bool sharded) {
+    if (m) m->mean_w = nullptr;                 // dp/dr of an earlier gradient evaluation: this call may overwrite or regrow its buffer (mogp_model_fetch 3)
+    if (!m || !Z || !kss_diag || !Xs || !mu || !var || M <= 0 || S <= 0) return fail(MOGP_EINVAL, "mogp_titsias_predict: bad argument");
+    RC(use_device(m->ctx));
+    if (info) *info = 0;
+    SortedX sz, ss;
+    TitsiasScalars sc;
+    RC(titsias_front(m, M, Z, sigma, jitter, sz, sc, info, sharded));
+    TitsiasWork& t = *m->tw;
+    const int64_t Mpad = t.Mpad;
+    RC(sparse_predict_panels(m, t, sz, S, Xs, ss));                                                          // a = L^-1 Kus
+    const int mt = (int)(Mpad / MOGP_TILE), st = (int)(ss.Mpad / MOGP_TILE);
+    const int64_t Spad = ss.Mpad;
+    GemmArgs g = make_gemm(t.Wq, Mpad, 0, t.Aus.p, Spad, 1, t.Bus.p, Spad, 1.0, GM_KHI_I, mt, st, Mpad);                    // b = Wq a
+    RC(gemm_call(m, g, gemm_flops(g, nullptr)));
+    double* vy = t.vec.p;
+    double* cvec = t.vec.p + 4 * Mpad;
+    RC(launch_trmv_lower(t.Wq, Mpad, Mpad, vy, cvec, t.vec.p + 6 * Mpad, m->st));                             // c s2 = Wq vy
+    // mu s2 = b^T (Wq vy);  var = K_ss,diag - colsum a^2 + colsum b^2
+    return sparse_predict_finish(m, t, ss, t.Bus.p, cvec, sigma * sigma, kss_diag, mu, var);
+}
 
 extern "C" {
 
@@ -532,66 +292,6 @@ int mogp_titsias_predict_sharded(mogp_model* m, int64_t M, const double* Z, doub
                                  int64_t S, const double* Xs, double* mu, double* var, int64_t* info) {
     return titsias_predict_impl(m, M, Z, sigma, jitter, kss_diag, S, Xs, mu, var, info, true);
 }
-
-}  // extern "C"
-
-static int titsias_predict_impl(mogp_model* m, int64_t M, const double* Z, double sigma, double jitter, const double* kss_diag,
-                                int64_t S, const double* Xs, double* mu, double* var, int64_t* info, bool sharded) {
-    if (m) m->mean_w = nullptr;                 // dp/dr of an earlier gradient evaluation: this call may overwrite or regrow its buffer (mogp_model_fetch 3)
-    if (!m || !Z || !kss_diag || !Xs || !mu || !var || M <= 0 || S <= 0) return fail(MOGP_EINVAL, "mogp_titsias_predict: bad argument");
-    RC(use_device(m->ctx));
-    if (info) *info = 0;
-    const int C = m->C, D = m->D;
-    const bool env = m->Wt > 2 + 3 * D;
-    SortedX sz, ss;
-    std::vector<GTile> tuu, tuf, tus;
-    std::vector<int> psuu, psuf;
-    TitsiasScalars sc;
-    RC(titsias_front(m, M, Z, sigma, jitter, sz, tuu, psuu, tuf, psuf, sc, info, false, sharded));
-    TitsiasWork& t = *m->tw;
-    const int64_t Mpad = t.Mpad;
-    const double s2 = sigma * sigma;
-    RC(sort_inputs(Xs, S, D, C, MOGP_TILE, ss));
-    t.pred_valid = false;
-    const int64_t Spad = ss.Mpad;
-    const int mt = (int)(Mpad / MOGP_TILE), st = (int)(Spad / MOGP_TILE);
-    build_rect_tiles(sz.off, ss.off, C, tus);
-    RC(t.Kus.ensure((size_t)Mpad * Spad)); RC(t.Aus.ensure((size_t)Mpad * Spad)); RC(t.Bus.ensure((size_t)Mpad * Spad));
-    RC(m->d_xs.ensure((size_t)D * Spad)); RC(m->d_ptiles.ensure(tus.size()));
-    RC(m->d_mu.ensure(Spad)); RC(m->d_var.ensure(2 * Spad));
-    HIP_TRY(hipMemcpyAsync(m->d_xs.p, ss.xs.data(), (size_t)D * Spad * sizeof(double), hipMemcpyHostToDevice, m->st));
-    HIP_TRY(hipMemcpyAsync(m->d_ptiles.p, tus.data(), tus.size() * sizeof(GTile), hipMemcpyHostToDevice, m->st));
-    HIP_TRY(hipMemsetAsync(t.Kus.p, 0, (size_t)Mpad * Spad * sizeof(double), m->st));
-    GramArgs ga{};
-    ga.tiles = m->d_ptiles.p; ga.xr = t.zx.p; ga.ldxr = Mpad; ga.xc = m->d_xs.p; ga.ldxc = Spad; ga.nrows = M; ga.ncols = S;
-    RC(t.ph_zs.prepare(sz.off, ss.off, C, m->T, Mpad, Spad, m->st, ga.ph));
-    ga.table = m->d_table.p; ga.T = m->T; ga.D = D; ga.C = C; ga.W = m->Wt; ga.out = t.Kus.p; ga.ldo = Spad; ga.mirror = 0;
-    RC(launch_gram(ga, (int)tus.size(), m->st));
-    HIP_TRY(hipMemcpyAsync(t.Aus.p, t.Kus.p, (size_t)Mpad * Spad * sizeof(double), hipMemcpyDeviceToDevice, m->st));
-    RC(trsm_lower(m, t.a.A.p, Mpad, mt, t.Aus.p, Spad, Spad, false));                                      // a = L^-1 Kus
-    GemmArgs g = make_gemm(t.Wq, Mpad, 0, t.Aus.p, Spad, 1, t.Bus.p, Spad, 1.0, GM_KHI_I, mt, st, Mpad);                    // b = Wq a
-    RC(gemm_call(m, g, gemm_flops(g, nullptr)));
-    double* vy = t.vec.p;
-    double* cvec = t.vec.p + 4 * Mpad;
-    RC(launch_trmv_lower(t.Wq, Mpad, Mpad, vy, cvec, t.vec.p + 6 * Mpad, m->st));                             // c s2 = Wq vy
-    RC(launch_gemv_cols(t.Bus.p, Spad, Mpad, Spad, cvec, m->d_mu.p, t.scratch.p, m->st));                    // mu s2 = b^T (Wq vy)
-    RC(launch_gemv_cols(t.Aus.p, Spad, Mpad, Spad, nullptr, m->d_var.p, t.scratch.p, m->st));               // colsum a^2
-    RC(launch_gemv_cols(t.Bus.p, Spad, Mpad, Spad, nullptr, m->d_var.p + Spad, t.scratch.p, m->st));        // colsum b^2
-    std::vector<double> hmu(Spad), hv(2 * Spad);
-    HIP_TRY(hipMemcpyAsync(hmu.data(), m->d_mu.p, Spad * sizeof(double), hipMemcpyDeviceToHost, m->st));
-    HIP_TRY(hipMemcpyAsync(hv.data(), m->d_var.p, 2 * Spad * sizeof(double), hipMemcpyDeviceToHost, m->st));
-    HIP_TRY(hipStreamSynchronize(m->st));
-    RC(sparse_timeout_check(m));
-    for (int c = 0; c < C; ++c)
-        for (int pos = ss.off[c]; pos < ss.off[c + 1]; ++pos) {
-            mu[ss.perm[pos]] = hmu[pos] / s2;
-            var[ss.perm[pos]] = (env ? kss_diag[ss.perm[pos]] : kss_diag[c]) - hv[pos] + hv[Spad + pos];     // envelope: K_ss,diag per test point
-        }
-    t.pred_ss = ss; t.pred_valid = true;
-    return MOGP_OK;
-}
-
-extern "C" {
 
 // Full predictive covariance of the LAST sparse prediction on this handle (mogp_titsias_predict, mogp_svgp_forward at test inputs; their
 // sharded forms): K_ss - a^T a + b^T b with a = L^-1 K_us and b as that call left them (reference gpr/model.py:758-760, 870-872), S x S in

@@ -972,8 +972,45 @@ def test_sparse_models_full_covariance_on_device():
     check_sparse_cov(tol=1e-7, tol_sample=1e-5)
 
 
+def test_sparse_models_share_one_handle():
+    """the three inducing-point models take turns on ONE handle (sparse.hip): the tile lists one model cached serve the next and come back
+    unharmed -- a Titsias evaluation behind a Snelson one returns the bits of the one before it -- and mogp_sparse_predict_cov belongs to the
+    LAST prediction whichever model made it: after a Snelson prediction at 70 points and a Titsias one at 50 others it is the 50 x 50
+    covariance of the latter.  C = 2, D = 1, N = 300 (three tile rows of X), M = 140 (Mpad = 256, padded), both channels on both sides."""
+    rng = np.random.default_rng(5)
+    C, Q, N, M, S = 2, 2, 300, 140, 70
+    X, y = synth.make_data(N, C)
+    h = synth.mosm_hypers(C, Q)
+    k = gpr.MultiOutputSpectralMixtureKernel(Q=Q, output_dims=C)
+    for name in ("weight", "mean", "variance", "delay", "phase"):
+        getattr(k, name).assign(h[name])
+    kd = k._spectral_diag(1)
+    Z = np.concatenate([np.stack([np.full(M // C, float(c)), np.sort(rng.uniform(0, 100, M // C))], axis=1) for c in range(C)])
+    noise = np.array([0.05, 0.2])
+    dev = _lib.ExactHandle(0, X, y, C)
+    dev.set_terms(k._spectral_terms(1))
+    t1 = dev.titsias_eval(Z, 0.3, 1e-6, kd, grad=True)
+    s1 = dev.snelson_eval(Z, noise, 1e-6, kd, grad=True)
+    assert np.isfinite(s1["lml"]) and np.all(np.isfinite(s1["gZ"]))
+    t2 = dev.titsias_eval(Z, 0.3, 1e-6, kd, grad=True)
+    for key in t1:
+        assert np.array_equal(np.asarray(t1[key]), np.asarray(t2[key])), key
+    q_mu, q_sqrt = rng.normal(0, 0.3, M), np.tril(rng.normal(0, 0.05, (M, M))) + 0.8 * np.eye(M)
+    f = dev.svgp_forward(Z, q_mu, q_sqrt, 1e-6, kd)
+    b = dev.svgp_backward(rng.standard_normal(N), -rng.uniform(0.5, 2.0, N))
+    assert np.all(np.isfinite(f["mu"])) and np.all(np.isfinite(b["gZ"])) and np.all(np.isfinite(b["mom_uf"]))
+    Xs = np.concatenate([np.stack([np.full(S // C, float(c)), np.linspace(0, 105, S // C)], axis=1) for c in range(C)])
+    mu_s, var_s = dev.snelson_predict(Z, noise, 1e-6, Xs, kd, kd)
+    assert mu_s.shape == (S, 1) and np.all(np.isfinite(var_s))
+    Xt = np.concatenate([np.stack([np.full(25, float(c)), rng.uniform(0, 100, 25)], axis=1) for c in range(C)])[rng.permutation(50)]
+    mu_t, var_t = dev.titsias_predict(Z, 0.3, 1e-6, Xt, kd)
+    cov = dev.sparse_predict_cov(50)
+    assert cov.shape == (50, 50)
+    assert np.max(np.abs(np.diag(cov) - var_t[:, 0])) <= 1e-10, float(np.max(np.abs(np.diag(cov) - var_t[:, 0])))
+
+
 def test_side_stream_schedule_equals_the_serial_one(tmp_path):
-    """the sparse models' M x M chains, K_uf and v y run on a side stream underneath the large products (titsias.hip:side_fork); with
+    """the sparse models' M x M chains, K_uf and v y run on a side stream underneath the large products (sparse.hip:side_fork); with
     MOGP_SIDE_STREAM=0 everything is enqueued on one stream -- same kernels, same arithmetic: the results must agree to rounding of the
     atomically accumulated d/dZ (a missing dependency between the streams would show up here)"""
     import os, subprocess, sys
