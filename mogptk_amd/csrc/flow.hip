@@ -25,6 +25,7 @@
 #include "mogp_model.h"
 #include <unistd.h>
 #include <chrono>
+#include <set>
 
 #include <cstdio>
 #include <cstdlib>
@@ -1015,6 +1016,172 @@ int spd_potri_flow(mogp_model* m, Spd& w, const FlowRhs* rhs) {
 }
 
 }  // namespace mogp
+
+// MOGP_FLOW_DEBUG: where every queue of the dataflow schedule stands, what its next tasks wait for, the private stream's waits; with MOGP_FLOW_TRACE=1
+// also the tasks finished per 5 ms.  (1: after a time-out; 2: 60 ms after the evaluation was enqueued, while whatever is stuck is still stuck)
+namespace mogp { void flow_debug_dump(mogp_model* m) {
+    if (!m->k.flow_flags.p || !m->k.flow_cur) return;
+    const FlowPlan& p = *m->k.flow_cur;
+    std::vector<unsigned> fl((size_t)p.nflags);
+    hipError_t e = hipMemcpy(fl.data(), m->k.flow_flags.p, fl.size() * sizeof(unsigned), hipMemcpyDeviceToHost); (void)e;
+    std::vector<unsigned long long> tr;
+    if (m->k.flow_trace.p && m->k.flow_trace.n >= FLOW_TRACE_W * p.tasks.size()) {
+        tr.resize(FLOW_TRACE_W * p.tasks.size());
+        e = hipMemcpy(tr.data(), m->k.flow_trace.p, tr.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost); (void)e;
+    }
+    fprintf(stderr, "  error word 0x%x\n", fl[p.base_err]);
+    std::set<unsigned> holders;
+    for (int q = 0; q < p.nq; ++q) {
+        const unsigned h = fl[p.base_heads + q];
+        const unsigned claimed = std::min<unsigned>(h, (unsigned)p.qsize[q]);
+        unsigned done = 0, shown = 0;
+        fprintf(stderr, "  queue %2d: head %u of %d", q, h, p.qsize[q]);
+        for (unsigned hh = 0; hh < (unsigned)p.qsize[q]; ++hh) {
+            const size_t ti = (size_t)p.qbase[q] + hh;
+            const FlowTask& t = p.tasks[ti];
+            const bool fin = !tr.empty() && tr[FLOW_TRACE_W * ti + 4] != 0;
+            if (fin) { ++done; continue; }
+            if (tr.empty() && hh + 4 < claimed) continue;              // without the trace: the last claimed ones and the head
+            if (hh > claimed || shown >= 6) continue;
+            ++shown;
+            fprintf(stderr, "\n      %s task %u key %u C(buf %d %d,%d) A(buf %d %d,%d) B(buf %d %d,%d) kt %d var %d:", hh < claimed ? "CLAIMED" : "head   ", hh, t.key,
+                    t.cbuf, t.cr, t.cc, t.abuf, t.ar, t.ac, t.bbuf, t.br, t.bc, t.kt, t.var);
+            for (int d = 0; d < t.ndep; ++d) fprintf(stderr, " flag[%u]=%u/%u", t.dep[d], fl[t.dep[d]], (unsigned)t.need[d]);
+            if (!tr.empty()) {
+                const unsigned long long w5 = tr[FLOW_TRACE_W * ti + 5];
+                if (w5 >> 63) { fprintf(stderr, "  (HELD by wg %llu%s)", w5 & 0xffff, tr[FLOW_TRACE_W * ti + 1] ? ": STARTED, not finished" : ""); holders.insert((unsigned)(w5 & 0xffff)); }
+                else fprintf(stderr, "  (taken by wg %llu: %s)", w5 & 0xffff, tr[FLOW_TRACE_W * ti + 1] ? "running" : "not started");
+            }
+        }
+        if (!tr.empty()) fprintf(stderr, "\n      finished %u", done);
+        fprintf(stderr, "\n");
+    }
+    if (!tr.empty() && !holders.empty()) {                                  // what the workgroups that HOLD unfinished tasks did last
+        unsigned long long t0 = ~0ull, tmax = 0;
+        for (size_t i = 0; i < p.tasks.size(); ++i) {
+            const unsigned long long s1 = tr[FLOW_TRACE_W * i + 1];
+            if (s1) { t0 = std::min(t0, s1); tmax = std::max(tmax, std::max(s1, tr[FLOW_TRACE_W * i + 4])); }
+        }
+        fprintf(stderr, "  last time stamp of the evaluation: %.1f us after its first task\n", (double)(tmax - t0) / 100.0);
+        int shown = 0;
+        for (unsigned wg : holders) {
+            size_t last = (size_t)-1, held = 0;
+            for (size_t i = 0; i < p.tasks.size(); ++i) {
+                const unsigned long long w5 = tr[FLOW_TRACE_W * i + 5];
+                if ((unsigned)(w5 & 0xffff) != wg) continue;
+                if (w5 >> 63) { ++held; if (!tr[FLOW_TRACE_W * i + 1]) continue; }
+                if (tr[FLOW_TRACE_W * i + 1] && (last == (size_t)-1 || tr[FLOW_TRACE_W * i + 1] > tr[FLOW_TRACE_W * last + 1])) last = i;
+            }
+            if (shown++ >= 24) break;
+            if (last == (size_t)-1) { fprintf(stderr, "  holder wg %u: holds %zu, has started NO task\n", wg, held); continue; }
+            const FlowTask& t = p.tasks[last];
+            fprintf(stderr, "  holder wg %u (xcc %llu): holds %zu; its last task %zu var %d kt %d: looked %.1f taken %.1f k loop %.1f .. %.1f signalled %.1f us%s\n", wg,
+                    (tr[FLOW_TRACE_W * last + 5] >> 16) & 0xff, held, last, t.var, t.kt,
+                    (double)((long long)(tr[FLOW_TRACE_W * last + 0] - t0)) / 100.0, (double)((long long)(tr[FLOW_TRACE_W * last + 1] - t0)) / 100.0,
+                    (double)((long long)(tr[FLOW_TRACE_W * last + 2] - t0)) / 100.0, (double)((long long)(tr[FLOW_TRACE_W * last + 3] - t0)) / 100.0,
+                    tr[FLOW_TRACE_W * last + 4] ? (double)((long long)(tr[FLOW_TRACE_W * last + 4] - t0)) / 100.0 : -1.0, tr[FLOW_TRACE_W * last + 4] ? "" : "  <- NOT FINISHED");
+        }
+    }
+    if (!tr.empty()) {                                                      // tasks finished and workgroups seen per 5 ms
+        unsigned long long t0 = ~0ull;
+        for (size_t i = 0; i < p.tasks.size(); ++i) if (tr[FLOW_TRACE_W * i + 1] && tr[FLOW_TRACE_W * i + 1] < t0) t0 = tr[FLOW_TRACE_W * i + 1];
+        std::map<long, std::pair<int, std::set<unsigned>>> win;
+        for (size_t i = 0; i < p.tasks.size(); ++i) {
+            const unsigned long long en = tr[FLOW_TRACE_W * i + 4];
+            if (!en) continue;
+            auto& w = win[(long)((en - t0) / 500000ull)];
+            ++w.first; w.second.insert((unsigned)(tr[FLOW_TRACE_W * i + 5] & 0xffff));
+        }
+        for (auto& kv : win) fprintf(stderr, "  %4ld ms: %6d tasks done by %3zu workgroups\n", kv.first * 5, kv.second.first, kv.second.second.size());
+    }
+    if (m->k.flow_post.p) {             // the workgroups' own reports: why each left, what it still held -- and who never reported
+        std::vector<unsigned> po(m->k.flow_post.n);
+        e = hipMemcpy(po.data(), m->k.flow_post.p, po.size() * sizeof(unsigned), hipMemcpyDeviceToHost); (void)e;
+        std::vector<unsigned char> dn(p.tasks.size(), 0);
+        if (m->k.flow_done.p && m->k.flow_done.n >= dn.size()) { e = hipMemcpy(dn.data(), m->k.flow_done.p, dn.size(), hipMemcpyDeviceToHost); (void)e; }
+        const size_t nwg = po.size() / FLOW_POST_W;
+        const int ncl = FLOW_NCAS * 8;
+        size_t n_to = 0, n_done = 0, n_silent = 0, n_never = 0;
+        std::map<size_t, std::vector<unsigned>> holder;          // task -> workgroups that hold its ticket
+        for (size_t wgi = 0; wgi < nwg; ++wgi) {
+            const unsigned* r = po.data() + wgi * FLOW_POST_W;
+            if (r[0] == 1) ++n_to; else if (r[0] == 2) ++n_done; else if (r[2] == 0) ++n_never; else {
+                ++n_silent;
+                fprintf(stderr, "  workgroup %zu NEVER LEFT: state %u (1 looking, 2 in task %u), last look at clock %u\n", wgi, r[2], r[3], r[4]);
+            }
+            if (r[0] != 1 && r[0] != 2) continue;
+            for (int lane = ncl; lane < 64; ++lane) {
+                if (!r[8 + lane]) continue;
+                const int q = FLOW_NCAS + (lane - ncl);
+                if (q >= p.nq) continue;
+                holder[(size_t)p.qbase[q] + (r[8 + lane] - 1)].push_back((unsigned)wgi);
+            }
+        }
+        fprintf(stderr, "  post-mortem: %zu workgroups left on the time-out, %zu left done, %zu never started, %zu never left; %zu tickets held\n", n_to, n_done, n_never, n_silent, holder.size());
+        // every task that has NOT signalled although its counters are met: who holds it, and what did the holder's last look say?
+        size_t nready = 0, nundone = 0;
+        std::set<unsigned> suspects;
+        for (int q = 0; q < p.nq; ++q) {
+            const unsigned h = fl[p.base_heads + q];
+            for (int k = 0; k < p.qsize[q]; ++k) {
+                const size_t ti = (size_t)p.qbase[q] + k;
+                if (dn[ti]) continue;
+                ++nundone;
+                const FlowTask& t = p.tasks[ti];
+                bool ready = true;
+                for (int d = 0; d < t.ndep; ++d) if (fl[t.dep[d]] < (unsigned)t.need[d]) ready = false;
+                if (!ready) continue;
+                if (nready++ >= 40) continue;
+                fprintf(stderr, "  READY BUT NOT DONE: queue %d task %d (head %u) key %u var %d C(buf %d %d,%d):", q, k, h, t.key, t.var, t.cbuf, t.cr, t.cc);
+                for (int d = 0; d < t.ndep; ++d) fprintf(stderr, " flag[%u]=%u/%u", t.dep[d], fl[t.dep[d]], (unsigned)t.need[d]);
+                auto it = holder.find(ti);
+                if (q < FLOW_NCAS) fprintf(stderr, "  [compare-and-swap queue: %s]", (unsigned)k == h ? "AT THE HEAD" : ((unsigned)k < h ? "taken, running or lost" : "behind the head"));
+                else if (it == holder.end()) fprintf(stderr, "  [%s]", (unsigned)k < h ? "TICKET GIVEN OUT, NO HOLDER REPORTED IT (running when the kernel froze, or lost)" : "no ticket given out yet");
+                else for (unsigned wgi : it->second) {
+                    const unsigned* r = po.data() + (size_t)wgi * FLOW_POST_W;
+                    const int lane = ncl + (q - FLOW_NCAS);
+                    const unsigned long long mr = ((unsigned long long)r[7] << 32) | r[6];
+                    fprintf(stderr, "  [held by workgroup %u: %u idle looks, its last look saw this task %s]", wgi, r[1], ((mr >> lane) & 1ull) ? "READY" : "not ready");
+                    suspects.insert(wgi);
+                }
+                fprintf(stderr, "\n");
+            }
+        }
+        fprintf(stderr, "  %zu tasks have not signalled; %zu of them have their counters met\n", nundone, nready);
+        // the life of every workgroup that holds such a task, and of the whole grid in numbers (clock: 0.16 us units since the first workgroup's first look)
+        unsigned t0 = ~0u;
+        for (size_t wgi = 0; wgi < nwg; ++wgi) { const unsigned* r = po.data() + wgi * FLOW_POST_W; if (r[72] && r[72] < t0) t0 = r[72]; }
+        auto us = [&](unsigned c) { return c ? 0.16 * (double)(int)(c - t0) : -1.0; };
+        for (unsigned wgi : suspects) {
+            const unsigned* r = po.data() + (size_t)wgi * FLOW_POST_W;
+            fprintf(stderr, "  workgroup %u: XCC %u HW_ID 0x%x (SE %u CU %u); first look at %.0f us, %u tasks run, last task %u started %.0f finished %.0f us, last look %.0f us, left %.0f us after %u idle looks\n",
+                    wgi, r[75] & 0xf, r[74], (r[74] >> 13) & 7, (r[74] >> 8) & 15, us(r[72]), r[73], r[3], us(r[76]), us(r[77]), us(r[4]), us(r[5]), r[1]);
+            fprintf(stderr, "      its waves' last marks (0x1.. entered, 0x2.. + k block whose successor's loads are in, 0x3.. past the k loop, 0x4.. stored) and when:");
+            for (int wv = 0; wv < 8; ++wv) fprintf(stderr, " %x", r[80 + wv]);
+            fprintf(stderr, "; wave 0 of its last task: entered %.0f, k block 0 / 8 / 16 / 24 at %.0f / %.0f / %.0f / %.0f, past the loop %.0f, stored %.0f us\n",
+                    us(r[88]), us(r[89]), us(r[90]), us(r[91]), us(r[92]), us(r[93]), us(r[94]));
+        }
+        {
+            std::vector<double> first, ntask;
+            for (size_t wgi = 0; wgi < nwg; ++wgi) { const unsigned* r = po.data() + wgi * FLOW_POST_W; if (r[72]) { first.push_back(us(r[72])); ntask.push_back((double)r[73]); } }
+            std::sort(first.begin(), first.end()); std::sort(ntask.begin(), ntask.end());
+            if (!first.empty()) fprintf(stderr, "  first looks: median %.0f us, latest %.0f us; tasks run per workgroup: least %.0f, median %.0f, most %.0f\n", first[first.size() / 2], first.back(), ntask.front(), ntask[ntask.size() / 2], ntask.back());
+        }
+        // workgroups in the middle of a task when the kernel froze
+        for (size_t wgi = 0; wgi < nwg; ++wgi) {
+            const unsigned* r = po.data() + wgi * FLOW_POST_W;
+            if (r[2] == 2 && r[3] < p.tasks.size() && !dn[r[3]]) fprintf(stderr, "  workgroup %zu was INSIDE task %u when it was last heard of\n", wgi, r[3]);
+        }
+    }
+    for (size_t b = 0; b < p.chain.size(); ++b) {
+        const FlowPlan::Chain& c = p.chain[b];
+        fprintf(stderr, "  chain %zu done flag[%u]=%u/%u; mini-panel waits", b, c.done_idx, fl[c.done_idx], c.expect);
+        for (int k = 0; k < c.t1_nwait; ++k) fprintf(stderr, " flag[%u]=%u/%u", c.t1_widx[k], fl[c.t1_widx[k]], c.t1_wval[k]);
+        fprintf(stderr, "; signals from %u:", c.t1_sig_base);
+        for (int k = 0; k < 4; ++k) fprintf(stderr, " %u", fl[c.t1_sig_base + k]);
+        fprintf(stderr, " (of %u); next-diagonal update waits flag[%u]=%u/%u\n", c.t1_sig_per_row, c.t2_widx, fl[c.t2_widx], c.t2_wval);
+    }
+} }
 
 // the time stamps of the last dataflow evaluation of the exact system (MOGP_FLOW_TRACE=1): [FLOW_TRACE_W ntasks] (see FlowArgs::trace)
 // in the order of mogp_flow_plan's task rows, then [4 nouter] chain kernel launch, wait over, end, spare

@@ -366,7 +366,7 @@ struct mogp_model {
     DevBuf<double> d_symv;
     DevBuf<double> d_x, d_y, d_table, d_noise, d_dvar, d_z, d_alpha, d_zz, d_partial, d_moments, d_diagG;
     DevBuf<GTile> d_tiles;
-    // Tiles of Kj^-1 the gradient actually reads (mogp_api.hip:kinv_plan): where every term of dK/dtheta is below e^-50 of its peak in a
+    // Tiles of Kj^-1 the gradient actually reads (exact.hip:kinv_plan): where every term of dK/dtheta is below e^-50 of its peak in a
     // 64 x 64 tile the moment kernel skips the tile, so the 128 x 128 tiles of the inverse under such tiles only are never formed.
     std::vector<GemmTask> kinv_acc_tasks, kinv_lauum_tasks;        // host lists of the current plan (tile-row-major)
     std::vector<int> kinv_prefix;                                 // [nb + 1]: tasks with tile row < r
@@ -378,7 +378,6 @@ struct mogp_model {
     DevBuf<double> d_pivots;            // [min, max] diagonal entry of the last factorisation's L (k_pivot_range)
     bool accurate = false, accurate_ran = false;      // mogp_model_set_accurate: gradient evaluations by refined panels + substitutions (factorize); the last one did
     DevBuf<double> acc_rhs;             // its 128-column right-hand-side block (y -> z -> alpha)
-    size_t pin_pivots = 0;              // where in the pinned block they come back
     double pivot_min = 0.0, pivot_max = 0.0;      // the same on the host, 0 when the last evaluation did not report them (sweep / sharded)
     DevBuf<unsigned long long> d_info;
 
@@ -457,7 +456,7 @@ int spd_info_verdict(mogp_model* m, const char* which, unsigned long long hinfo,
 // chain kernel) time out anywhere?  Then the numbers are not valid: the model drops those forms and the call fails, loudly
 int sparse_timeout_check(mogp_model* m);
 bool chain_enabled(const mogp_model* m);   // chain.hip
-int chain_fallback(mogp_model* m);     // mogp_api.hip: after MOGP_INFO_CHAIN_TIMEOUT -- drain, switch the model to the launch-per-step chain; the caller repeats the evaluation
+int chain_fallback(mogp_model* m);     // exact.hip: after MOGP_INFO_CHAIN_TIMEOUT -- drain, switch the model to the launch-per-step chain; the caller repeats the evaluation
 // w.A (SPD, lower tiles) -> w.B = its inverse (lower tiles, full diagonal tiles) and *W = L^-1 (lower; in w.A, or in w.Wm on the fused path),
 // w.logdet per tile: POTRF, TRTRI, LAUUM.  MOGP_SPARSE_FUSED=1 takes the fused factorisation + inversion schedule of the exact path
 // (potri.hip) instead -- measured SLOWER for the 16-tile-row systems of configs[4] (52.0 vs 49.9 ms per evaluation: four outer blocks give
@@ -499,6 +498,24 @@ int sparse_point_stats(mogp_model* m, TitsiasWork& t, const SortedX& pts, const 
                        const double* mu_vec, double mu_div, const double* kdiag, double* mu, double* var);
 int sparse_predict_finish(mogp_model* m, TitsiasWork& t, const SortedX& ss, const double* mu_panel, const double* mu_vec, double mu_div,
                           const double* kss_diag, double* mu, double* var);   // sparse_point_stats with a, b = t.Aus, t.Bus
+// The scaffold of the exact path (exact.hip), shared with the sweep / sharded evaluation (shard.hip).
+#define MOGP_RETRY_NO_CHAIN 0x7e7e      // internal return code: a hand-off between workgroups timed out, nothing is wrong with the data (chain_fallback)
+extern int g_outer;                     // outer Cholesky block of spd_potrf in tiles (mogp_api.hip; MOGP_OUTER overrides)
+// An entry point's opening, behind its own argument check: dp/dr of an earlier gradient evaluation ends (its buffer may be overwritten or regrown: mogp_model_fetch 3), device, *info = 0, one_gpu_call
+int begin_call(mogp_model* m, int64_t* info, bool one_gpu);
+// The prologue of an evaluation: argument checks, ensure_system, counters reset, the absolute jitter (relative to the mean diagonal) into jabs, noise / per-point
+// variances / pivot-word sentinel uploaded on m->st, mark 0, and ga = the training Gram into k.A over the whole tile list (the caller attaches the strips)
+int exact_begin(mogp_model* m, const double* noise_var, const double* data_var, double jitter, GramArgs& ga, double& jabs);
+int report_not_pd(unsigned long long hinfo, int64_t* info);      // the reference's message with the leading-minor order -> MOGP_ENOTPD
+// The test side of a prediction: Xs sorted, uploaded on st with kss_diag (expanded per point) and the (Xs, X) tile list; d_mu sized, K_sf (Spad + extra_rows rows)
+// zero-filled; ga = the Gram K_sf = K(Xs, X), which the caller launches over ts.ntiles tiles
+struct TestSide { SortedX ss; int64_t Spad = 0; int ntiles = 0; };
+int test_side(mogp_model* m, int64_t S, const double* Xs, const double* kss_diag, int64_t extra_rows, hipStream_t st, TestSide& ts, GramArgs& ga);
+inline void scatter_by_perm(const SortedX& ss, const double* sorted, double* out) { for (int64_t pos = 0; pos < ss.M; ++pos) out[ss.perm[pos]] = sorted[pos]; }   // back to the caller's order
+int moment_pass_device(mogp_model* m, const double* kinv, double ksign);      // gradient moments over this rank's rows of Kj^-1 into d_moments / d_diagG
+int moment_pass(mogp_model* m, const double* kinv, double ksign, double* moments, double* diagG);      // ... and to the host, with a stream sync
+void collect_timing(mogp_model* m, int last_mark);
+int eval_sweep(mogp_model* m, const double* noise_var, const double* data_var, double jitter, double* lml, double* jitter_abs, int64_t* info);   // shard.hip
 void one_gpu_call(mogp_model* m);   // ownership state of a previous sharded evaluation off (every one-GPU entry point calls this first)
 int ensure_system(mogp_model* m);     // the N x N system of the exact / OA paths and the tile lists over (X, X), on first use (mogp_api.hip)
 int spd_potrf(mogp_model* m, Spd& w, long long info_base = 0);
@@ -506,7 +523,7 @@ int spd_potri_fused(mogp_model* m, Spd& w);
 bool flow_enabled(const mogp_model* m, const Spd& w);   // flow.hip
 int launch_flow_alpha_sum(const Spd& w, double* alpha, hipStream_t st);
 int spd_potri_flow(mogp_model* m, Spd& w, const FlowRhs* rhs = nullptr);
-void flow_debug_dump(mogp_model* m);                 // MOGP_FLOW_DEBUG (mogp_api.hip)             // flow.hip: the same result as spd_potri_fused, as tile dataflow
+void flow_debug_dump(mogp_model* m);                 // MOGP_FLOW_DEBUG             // flow.hip: the same result as spd_potri_fused, as tile dataflow
 int spd_potri_fused_finish(mogp_model* m, Spd& w);   // joins the inverse stream: call before reading w.B   // potri.hip: w.A (SPD, lower) -> w.Wm = L^-1, w.B = inverse (lower); w.logdet per tile
 int spd_trtri(mogp_model* m, Spd& w);
 int spd_lauum(mogp_model* m, Spd& w);

@@ -346,7 +346,7 @@ int launch_sym_lower_avg(double* A, int64_t ld, int64_t n, double scale, hipStre
 
 // tri (square right-hand side): the solution is wanted -- forward: IS, the right-hand side being lower triangular -- in its lower block triangle only:
 // right-looking, block row i solved in and its update applied to the first i + 1 column tiles (L^-1 I and the lower half of L^-T (L^-1 I): half the
-// products of the full solves; the accurate form of the exact evaluation, mogp_api.hip:factorize)
+// products of the full solves; the accurate form of the exact evaluation, exact.hip:factorize)
 int trsm_lower(mogp_model* m, const double* L, int64_t ldl, int nb, double* B, int64_t ldb, int64_t ncols, bool trans, hipStream_t st, bool tri,
                const hipEvent_t* row_ready) {
     if (!st) st = m->st;

@@ -1009,6 +1009,58 @@ def test_sparse_models_share_one_handle():
     assert np.max(np.abs(np.diag(cov) - var_t[:, 0])) <= 1e-10, float(np.max(np.abs(np.diag(cov) - var_t[:, 0])))
 
 
+def test_exact_entry_points_share_one_handle():
+    """the exact entry points take turns on ONE handle (exact.hip: one prologue, one factorisation plan, one pinned-block layout for all of them): gradient
+    evaluation, prediction, LML only, accurate-mode gradient evaluation, accurate off and a full-covariance prediction, gradient evaluation with data_var,
+    the plain gradient evaluation again.  Every step returns what the same call returns on a fresh handle -- nothing a call sets for itself (the refined
+    factorisation, the right-hand sides of a prediction, which of W / Kj^-1 exist, the data_var buffer) outlives it -- and the last step the bits of the
+    first.  C = 3, D = 1, N = 1100: nine tile rows, ragged channels, a padded last tile; the gradient evaluations run as dataflow with the Gram in two launches."""
+    rng = np.random.default_rng(1100)
+    C, Q, N, S = 3, 2, 1100, 111
+    sizes = rng.multinomial(N - C, np.ones(C) / C) + 1
+    X = np.concatenate([np.stack([np.full(s, float(c)), rng.uniform(0, 10, s)], axis=1) for c, s in enumerate(sizes)])[rng.permutation(N)]
+    y = rng.standard_normal(N)
+    k = gpr.MultiOutputSpectralMixtureKernel(Q=Q, output_dims=C)
+    k.weight.assign(rng.uniform(0.5, 1.5, (C, Q))); k.mean.assign(rng.uniform(0.02, 0.4, (C, Q, 1)))
+    k.variance.assign(rng.uniform(0.05, 0.5, (C, Q, 1))); k.delay.assign(rng.normal(0, 0.3, (C, Q, 1))); k.phase.assign(rng.normal(0, 0.3, (C, Q)))
+    table, kss = k._spectral_terms(1), k._spectral_diag(1)
+    noise, dvar = rng.uniform(0.05, 0.2, C), rng.uniform(0.0, 0.1, N)
+    Xs = np.concatenate([np.stack([np.full(S // C, float(c)), rng.uniform(-1, 11, S // C)], axis=1) for c in range(C)])[rng.permutation(S)]
+    steps = [("grad", lambda h: h.eval(noise, 1e-8, grad=True)),
+             ("predict", lambda h: dict(zip(("mu", "var"), h.predict(noise, 1e-8, kss, Xs)))),
+             ("lml_only", lambda h: h.eval(noise, 1e-8, grad=False)),
+             ("accurate_grad", lambda h: (h.set_accurate(1), h.eval(noise, 1e-8, grad=True))[1]),
+             ("predict_full", lambda h: (h.set_accurate(0), dict(zip(("mu", "var"), h.predict(noise, 1e-8, kss, Xs, full=True))))[1]),
+             ("grad_data_var", lambda h: h.eval(noise, 1e-8, grad=True, data_var=dvar)),
+             ("grad_again", lambda h: h.eval(noise, 1e-8, grad=True))]
+
+    def fresh():
+        h = _lib.ExactHandle(0, X, y, C)
+        h.set_terms(table)
+        return h
+    shared = fresh()
+    got = []
+    for name, call in steps:
+        got.append(call(shared))
+        if name == "grad":
+            s = shared.schedule()
+            assert s["dataflow"] and not s["dataflow_fell_back"], s
+    worst, unequal = {}, []
+    for (name, call), a in zip(steps, got):
+        h = fresh()
+        b = call(h)
+        h.close()
+        for key in b:
+            if b[key] is not None:
+                worst[name + "." + key] = float(np.max(np.abs(np.asarray(a[key]) - np.asarray(b[key]))))
+                if not np.array_equal(np.asarray(a[key]), np.asarray(b[key])):
+                    unequal.append(name + "." + key)
+    print("shared handle against fresh handles, max |difference|:", worst)
+    assert not unequal, {u: worst[u] for u in unequal}
+    for key in got[0]:
+        assert np.array_equal(np.asarray(got[0][key]), np.asarray(got[-1][key])), key
+
+
 def test_side_stream_schedule_equals_the_serial_one(tmp_path):
     """the sparse models' M x M chains, K_uf and v y run on a side stream underneath the large products (sparse.hip:side_fork); with
     MOGP_SIDE_STREAM=0 everything is enqueued on one stream -- same kernels, same arithmetic: the results must agree to rounding of the

@@ -1,6 +1,6 @@
 """Gradient evaluation on a series ten times longer than BASELINE configs[1]'s (same N, C, Q and hyperparameters, inputs over [0, 1000]):
 the kernel's support is then a narrow band of the matrix and the evaluation forms only the tiles of Kj^-1 the gradient reads
-(mogp_api.hip:kinv_plan).  Times it against MOGP_FULL_INVERSE=1 in two subprocesses and compares loss and gradients.
+(exact.hip:kinv_plan).  Times it against MOGP_FULL_INVERSE=1 in two subprocesses and compares loss and gradients.
 usage: python tools/long_series.py [N] [stretch]        (run on the GPU box)"""
 import os, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
