@@ -5,6 +5,7 @@ the O(C^2 Q) parameter algebra (term table, chain rule) in numpy.
 """
 import sys
 import numpy as np
+from contextlib import contextmanager
 from math import erf, sqrt
 
 from .config import config
@@ -38,6 +39,21 @@ def _leaf_kernels(kernel):
     if not subs:
         return [kernel]
     return [leaf for k in subs for leaf in _leaf_kernels(k)]
+
+
+def _enveloped(table, D):
+    """rows of width 2 + 5 D (MOHSM): the kernel diagonal follows the points instead of being constant per channel"""
+    return table.shape[3] > 2 + 3 * D
+
+
+def _channel_counts(Xk, C):
+    """points per channel of inputs in kernel format"""
+    return np.bincount(Xk[:, 0].astype(np.int64), minlength=C).astype(np.float64)
+
+
+def _lml_constant(X):
+    """N/2 log 2 pi, the attribute the reference's models carry (gpr/model.py:436)"""
+    return 0.5 * X.shape[0] * np.log(2.0 * np.pi)
 
 
 _PAIR_INDEX = {}
@@ -100,12 +116,6 @@ class Model(ParameterHolder):
         if likelihood.output_dims is not None and likelihood.output_dims != kernel.output_dims:
             raise ValueError("kernel and likelihood must have matching output dimensions")
         likelihood.validate_y(X, y)
-        if not isinstance(self, Exact):
-            D = X.shape[1] - (0 if kernel.output_dims is None else 1)
-            if any(k._radial(D) for k in _leaf_kernels(kernel)):
-                raise NotImplementedError("%s with a non-Gaussian stationary kernel (rational quadratic, Matern, exponential) is not on the HIP path yet: "
-                                          "its per-point input gradients need the profile's derivative in a third place; gpr.Exact takes them" % self.name())
-
         # limit to number of significant digits (reference gpr/model.py:106-110)
         jitter = max(jitter, 1e-6 if config.dtype == np.float32 else 1e-15)
 
@@ -117,6 +127,9 @@ class Model(ParameterHolder):
         self.jitter = jitter
         self.input_dims = X.shape[1]
         self._handle = None
+        if not isinstance(self, Exact) and any(k._radial(self._D) for k in _leaf_kernels(kernel)):
+            raise NotImplementedError("%s with a non-Gaussian stationary kernel (rational quadratic, Matern, exponential) is not on the HIP path yet: "
+                                      "its per-point input gradients need the profile's derivative in a third place; gpr.Exact takes them" % self.name())
 
     def name(self):
         return self.__class__.__name__
@@ -144,8 +157,7 @@ class Model(ParameterHolder):
 
     def _mean_affine(self):
         channel_col = self.kernel.output_dims is not None
-        D = self.X.shape[1] - (1 if channel_col else 0)
-        return self.mean._affine(self.kernel._channels(), D, channel_col), channel_col
+        return self.mean._affine(self.kernel._channels(), self._D, channel_col), channel_col
 
     def _sync_mean(self, h):
         """before an evaluation: the affine table to the device (it re-forms the residual only when the table changed), or -- a user's
@@ -172,14 +184,95 @@ class Model(ParameterHolder):
         else:
             self.mean.backward(self.X, h.fetch(3).reshape(-1, 1))
 
+    def _add_mean(self, mu, X):
+        """a prediction's mean plus the mean function at its inputs"""
+        if self.mean is None:
+            return mu
+        return mu + np.asarray(self.mean(X)).reshape(-1, 1)
+
+    # -- the host scaffold every model evaluates through ------------------------------------------------------------------------
+    _device_mean = True       # _push hands a gpr.Mean to the device (the variational models refuse one at construction)
+    _noise_dtype = None       # the dtype the noise scale is squared in (None: the parameter's own)
+
+    @property
+    def _D(self):
+        """input dimensions without the channel column"""
+        return self.X.shape[1] - (0 if self.kernel.output_dims is None else 1)
+
+    def _device_handle(self):
+        if self._handle is None:
+            from .._lib import ExactHandle
+            self._handle = ExactHandle(config.device, self.kernel._kernel_format(self.X), self._handle_y(), self.kernel._channels())
+        return self._handle
+
+    def _push(self, table=None):
+        """what every evaluation starts with: the device handle, the mean and the term table (built here unless the caller had to look at it first)
+        on the device -> (h, table, D)"""
+        h = self._device_handle()
+        if self._device_mean:
+            self._sync_mean(h)
+        D = self._D
+        if table is None:
+            table = self.kernel._spectral_terms(D)
+        h.set_terms(table)
+        return h, table, D
+
+    @contextmanager
+    def _cholesky_guard(self):
+        """around every device call that factorises: not positive definite / non-finite becomes the reference's CholeskyException
+        (reference gpr/model.py:245-255: report, dump parameters, raise CholeskyException(msg, K, model)); any other error passes"""
+        from .._lib import MogpError, MOGP_ENOTPD, MOGP_ENONFINITE
+        try:
+            yield
+        except MogpError as e:
+            if e.code in (MOGP_ENOTPD, MOGP_ENONFINITE):
+                print("ERROR:", str(e), file=sys.__stdout__)
+                self.print_parameters()
+                raise CholeskyException(str(e), None, self)
+            raise
+
+    def _kernel_diag(self, table, Xk, D):
+        """K_diag as the device takes it: per point of Xk with enveloped terms, else per channel"""
+        return self.kernel._point_diag(table, Xk, D) if _enveloped(table, D) else self.kernel._spectral_diag(D)
+
+    def _train_counts(self):
+        """training points per channel.  X does not change under a model (reference gpr/model.py:113-118): counted once per X and number of channels"""
+        C = self.kernel._channels()
+        cache = self.__dict__.get("_count_cache")
+        if cache is None or cache[0] is not self.X or cache[1].shape[0] != C:
+            cache = self.__dict__["_count_cache"] = (self.X, _channel_counts(self.kernel._kernel_format(self.X), C))
+        return cache[1]
+
+    def _noise_per_channel(self, s):
+        return s.ndim == 1 and s.shape[0] == self.kernel._channels() and self.kernel.output_dims is not None
+
+    def _noise_var(self):
+        """sigma_c^2 per channel: the vector `_index_channel` (gpr/model.py:183-186) would gather from (a scalar scale is shared by all channels)"""
+        s = np.asarray(self.likelihood.scale(), dtype=self._noise_dtype)
+        if self._noise_per_channel(s):
+            return np.square(s)
+        s = s.reshape(-1)[0]               # (Snelson has always squared its shared scale as a power, which is not a product's bits for one float64 in a thousand)
+        return np.repeat(s ** 2 if self._noise_dtype else np.square(s), self.kernel._channels())
+
+    def _noise_backward(self, gvar):
+        """gvar[c] = d LML / d sigma_c^2 -> the noise scale's .grad (loss = -LML): d / d sigma_c = 2 sigma_c gvar[c]; a shared scale takes the sum"""
+        scale = self.likelihood.scale
+        sc = np.asarray(scale(), dtype=self._noise_dtype)
+        if self._noise_per_channel(sc):
+            gsc = 2.0 * sc * gvar
+        else:
+            gsc = np.reshape(2.0 * sc * np.sum(gvar), sc.shape)
+        scale.accumulate_grad(-gsc)
+
     def _get_name(self):
         return self.__class__.__name__
 
     def __getstate__(self):
         """device handles are never pickled; they are rebuilt lazily (reference gpr/model.py:131-136 drops
-        the traced forward the same way)"""
+        the traced forward the same way), and so is the per-channel count"""
         state = self.__dict__.copy()
         state["_handle"] = None
+        state.pop("_count_cache", None)
         return state
 
     def _check_input(self, X, y=None):
@@ -321,63 +414,39 @@ class Exact(Model):
             raise ValueError("variance must be float or have shape (channels,)")
 
         super().__init__(kernel, X, y, GaussianLikelihood(np.sqrt(variance)), jitter, mean)
-        self.log_marginal_likelihood_constant = 0.5 * self.X.shape[0] * np.log(2.0 * np.pi)
+        self.log_marginal_likelihood_constant = _lml_constant(self.X)
 
     # -- device plumbing ---------------------------------------------------------------------
-    def _device_handle(self):
-        if self._handle is None:
-            from .._lib import ExactHandle
-            self._handle = ExactHandle(config.device, self.kernel._kernel_format(self.X), self._handle_y(), self.kernel._channels())
-        return self._handle
-
-    def _noise_var(self):
-        """sigma_c^2 per channel: the vector `_index_channel` (gpr/model.py:183-186) would gather from"""
-        s2 = np.square(self.likelihood.scale())
-        C = self.kernel._channels()
-        if s2.ndim == 1 and s2.shape[0] == C and self.kernel.output_dims is not None:
-            return s2
-        return np.repeat(np.asarray(s2).reshape(-1)[0], C)
-
     def _push_terms(self):
         comm = getattr(config, "comm", None)
         if comm is not None and (comm.world > 1 or comm.force):
             self._mean_refuse("the sharded exact evaluation (use_distributed)")
-        D = self.X.shape[1] - (0 if self.kernel.output_dims is None else 1)
+        D = self._D
         table = self.kernel._spectral_terms(D)
         kind, shape = self.kernel._spectral_kinds(D)
         radial = bool(np.any(kind))
         if radial:                              # refused before any device call
             if comm is not None and (comm.world > 1 or comm.force):
                 raise NotImplementedError("non-Gaussian stationary kernels are not carried through the sharded exact evaluation (use_distributed)")
-            if table.shape[3] > 2 + 3 * D:
+            if _enveloped(table, D):
                 raise NotImplementedError("a sum of enveloped (harmonizable) terms and non-Gaussian stationary kernels is not on the HIP path")
-        h = self._device_handle()
-        self._sync_mean(h)
-        h.set_terms(table)
+        h, table, D = self._push(table)
         if radial:
             h.set_kinds(kind, shape)
         elif getattr(h, "radial_kinds", False):
             h.set_kinds(None, None)               # the kernel was replaced by an all-Gaussian one with the same number of terms
         h.radial_kinds = radial
-        if table.shape[3] > 2 + 3 * D:        # envelope: the diagonal varies from point to point and enters the relative jitter (:244)
+        if _enveloped(table, D):              # envelope: the diagonal varies from point to point and enters the relative jitter (:244)
             h.set_point_diag(self.kernel._point_diag(table, self.kernel._kernel_format(self.X), D))
         return h, table, D
 
     def _eval(self, grad):
-        from .._lib import MogpError, MOGP_ENOTPD, MOGP_ENONFINITE
         h, table, D = self._push_terms()
-        try:
+        with self._cholesky_guard():
             run = lambda: h.eval(self._noise_var(), self.jitter, grad=grad, data_var=self.data_variance)
             res = run()
             again = self._check_conditioning(h, run) if grad else None          # (the LML alone: the fast factorisation's log-determinant and z are good to ~1e-7 even at 1e8)
             return (res if again is None else again), table, D
-        except MogpError as e:
-            if e.code in (MOGP_ENOTPD, MOGP_ENONFINITE):
-                # reference gpr/model.py:245-255: report, dump parameters, raise CholeskyException(msg, K, model)
-                print("ERROR:", str(e), file=sys.__stdout__)
-                self.print_parameters()
-                raise CholeskyException(str(e), None, self)
-            raise
 
     CONDITION_WARN = 1e5       # on the pivot-spread estimate (max L_jj / min L_jj)^2, a LOWER bound of cond(Kj) -- 9e5 where cond is 7e7, 9e3 where it is 8e5;
                                # DESIGN 7 puts the envelope of the fast schedules at cond ~ 1e6 - 1e7
@@ -422,58 +491,36 @@ class Exact(Model):
         parameter in the graph.  Gradients come from the device's moment pass + the host chain rule."""
         self.zero_grad(set_to_none=True)
         res, table, D = self._eval(grad=True)
-        h = self._handle
-        C, T = h.C, h.T
-        N = self.X.shape[0]
-        W = 2 + 3 * D
-        mom = res["moments"]
-        if getattr(self, "_counts", None) is None or len(self._counts) != C:     # X is fixed per model (reference gpr/model.py:113-118)
-            self._counts = np.bincount(self.kernel._kernel_format(self.X)[:, 0].astype(np.int64), minlength=C).astype(np.float64)
-        counts = self._counts
-        jit_rel = self.jitter * res["trG"] / N            # d LML / d (mean diag) through the jitter term (:244)
+        counts = self._train_counts()
+        jit_rel = self.jitter * res["trG"] / self.X.shape[0]            # d LML / d (mean diag) through the jitter term (:244)
 
         # d LML / d table for the lower channel pairs (i >= j); zero elsewhere
-        gt = _gtable_from_moments(table, mom, D, lower=True)
-        if table.shape[3] > 2 + 3 * D:
+        gt = _gtable_from_moments(table, res["moments"], D, lower=True)
+        if _enveloped(table, D):
             gt += jit_rel * self.kernel._point_diag_table_grad(table, self.kernel._kernel_format(self.X), D)
         else:
-            for i in range(C):
+            for i in range(table.shape[0]):
                 gt[i, i, :, 0] += jit_rel * counts[i]
         self.kernel._spectral_backward(-gt)                    # loss = -LML
 
         # noise: d LML / d sigma_c = 2 sigma_c (sum_{k in c} G_kk + jitter n_c/N tr G)
-        scale = self.likelihood.scale
-        sc = scale()
-        gnoise = res["diagG"] + jit_rel * counts
-        if sc.ndim == 1 and sc.shape[0] == C and self.kernel.output_dims is not None:
-            gsc = 2.0 * sc * gnoise
-        else:
-            gsc = np.reshape(2.0 * sc * np.sum(gnoise), sc.shape)
-        scale.accumulate_grad(-gsc)
-        self._mean_backward(h)
+        self._noise_backward(res["diagG"] + jit_rel * counts)
+        self._mean_backward(self._handle)
         return config.dtype(-res["lml"] - self.log_prior())
 
     def predict_f(self, X, full=False):
         """reference gpr/model.py:455-483"""
-        from .._lib import MogpError, MOGP_ENOTPD, MOGP_ENONFINITE
         X = self._check_input(X)
         h, table, D = self._push_terms()
         Xk = self.kernel._kernel_format(X)
-        kss = self.kernel._point_diag(table, Xk, D) if table.shape[3] > 2 + 3 * D else self.kernel._spectral_diag(D)
-        try:
+        kss = self._kernel_diag(table, Xk, D)
+        with self._cholesky_guard():
             run = lambda: h.predict(self._noise_var(), self.jitter, kss, Xk, full=full, data_var=self.data_variance)
             mu, var = run()
             again = self._check_conditioning(h, run)           # an ill-conditioned system: said once, predicted again in the refined form (DESIGN 7)
             if again is not None:
                 mu, var = again
-        except MogpError as e:
-            if e.code in (MOGP_ENOTPD, MOGP_ENONFINITE):
-                print("ERROR:", str(e), file=sys.__stdout__)
-                self.print_parameters()
-                raise CholeskyException(str(e), None, self)
-            raise
-        if self.mean is not None:
-            mu = mu + np.asarray(self.mean(X)).reshape(-1, 1)
+        mu = self._add_mean(mu, X)
         return mu.astype(config.dtype, copy=False), var.astype(config.dtype, copy=False)
 
 
@@ -552,6 +599,9 @@ class _DataParallel:
         comm = self._data_shard()
         return a if comm is None else a[comm.rank::comm.world]
 
+    def _local_Xk(self):
+        return self._local(self.kernel._kernel_format(self.X))
+
     def _device_handle(self):
         comm = self._data_shard()
         key = None if comm is None else (comm.rank, comm.world)
@@ -559,12 +609,55 @@ class _DataParallel:
             from .._lib import ExactHandle
             if comm is not None:
                 self._mean_refuse("the data-parallel form (use_distributed)")
-            self._handle = ExactHandle(config.device, self._local(self.kernel._kernel_format(self.X)), self._local(self._handle_y()), self.kernel._channels())
+            self._handle = ExactHandle(config.device, self._local_Xk(), self._local(self._handle_y()), self.kernel._channels())
             self.__dict__["_handle_key"] = key
         return self._handle
 
 
-class Titsias(_DataParallel, Model):
+class _InducingPoints(_DataParallel):
+    """What Titsias, Snelson and the Hensman models share on the host: the inducing inputs `Z` as a parameter (their channel column carries no
+    gradient), the two kernel diagonals of a prediction, and the part of the chain rule that goes through K_uu and K_uf."""
+
+    def _init_inducing(self, Z, Z_init):
+        """the bound's constant, and -> `Z` as a parameter (the constructor assigns it: the assignment fixes its place in parameters())"""
+        self.log_marginal_likelihood_constant = _lml_constant(self.X)
+        Z = init_inducing_points(Z, self.X, method=Z_init, output_dims=self.kernel.output_dims)
+        Z = Parameter(self._check_input(Z), name="induction_points")
+        if self.kernel.output_dims is not None:
+            Z.num_parameters -= Z().shape[0]
+        return Z
+
+    def _kernel_diags(self, table, Xsk, D):
+        """(K_diag at this process's training points, K_diag at the test points Xsk): per point with enveloped terms, else one per channel for both"""
+        if _enveloped(table, D):
+            return self.kernel._point_diag(table, self._local_Xk(), D), self.kernel._point_diag(table, Xsk, D)
+        kd = self.kernel._spectral_diag(D)
+        return kd, kd
+
+    def _inducing_backward(self, table, D, Zk, mom_uu, mom_uf, trGA, gZ):
+        """-> d bound / d table through K_uu (moments over the lower channel pairs) and K_uf (all pairs), K_uu's relative jitter
+        jitter * mean(diag K_uu) (gpr/model.py:244) included; the model adds what belongs to its bound and runs the kernel's backward.
+        gZ = d bound / d Z goes to Z.grad past the channel column (None: Z is not trained)."""
+        C, M = table.shape[0], Zk.shape[0]
+        gt = _gtable_from_moments(table, mom_uu, D, lower=True) + _gtable_from_moments(table, mom_uf, D, lower=False)
+        gz_jit = 0.0
+        if _enveloped(table, D):
+            # with an envelope (MOHSM) the diagonal follows the points: jitter * mean(diag Kuu) depends on A, L, c AND on Z itself (through autograd in the reference)
+            gt += (self.jitter * trGA / M) * self.kernel._point_diag_table_grad(table, Zk, D)
+            gz_jit = (self.jitter * trGA / M) * self.kernel._point_diag_input_grad(table, Zk, D)
+        else:
+            zc = _channel_counts(Zk, C)
+            for i in range(C):
+                gt[i, i, :, 0] += self.jitter * trGA * zc[i] / M
+        if gZ is not None:
+            gz = np.zeros(self.Z.data.shape)
+            off = 0 if self.kernel.output_dims is None else 1
+            gz[:, off:] = -(gZ + gz_jit)
+            self.Z.accumulate_grad(gz)
+        return gt
+
+
+class Titsias(_InducingPoints, Model):
     """
     Sparse GP regression, Titsias 2009 (reference gpr/model.py:668-765): the bound
         ELBO = log N(y | 0, Kfu Kuu^-1 Kuf + s2 I) - tr(Kff - Kfu Kuu^-1 Kuf) / (2 s2)
@@ -574,12 +667,7 @@ class Titsias(_DataParallel, Model):
     def __init__(self, kernel, X, y, Z, Z_init="grid", variance=1.0, jitter=1e-8, mean=None):
         variance = Parameter.to_tensor(variance)
         super().__init__(kernel, X, y, GaussianLikelihood(np.sqrt(variance)), jitter, mean)
-        Z = init_inducing_points(Z, self.X, method=Z_init, output_dims=kernel.output_dims)
-        Z = self._check_input(Z)
-        self.log_marginal_likelihood_constant = 0.5 * self.X.shape[0] * np.log(2.0 * np.pi)
-        self.Z = Parameter(Z, name="induction_points")
-        if kernel.output_dims is not None:
-            self.Z.num_parameters -= self.Z().shape[0]
+        self.Z = self._init_inducing(Z, Z_init)
 
     def _sigma(self):
         s = np.asarray(self.likelihood.scale())
@@ -588,23 +676,11 @@ class Titsias(_DataParallel, Model):
         return float(s.reshape(-1)[0])
 
     def _run(self, grad):
-        from .._lib import MogpError, MOGP_ENOTPD, MOGP_ENONFINITE
-        h = self._device_handle()
-        self._sync_mean(h)
-        D = self.X.shape[1] - (0 if self.kernel.output_dims is None else 1)
-        table = self.kernel._spectral_terms(D)
-        h.set_terms(table)
+        h, table, D = self._push()
         Zk = self.kernel._kernel_format(self.Z())
-        Xk = self._local(self.kernel._kernel_format(self.X))
-        kff = self.kernel._point_diag(table, Xk, D) if table.shape[3] > 2 + 3 * D else self.kernel._spectral_diag(D)    # envelope: per point
-        try:
+        kff = self._kernel_diag(table, self._local_Xk(), D)                     # envelope: per point
+        with self._cholesky_guard():
             res = h.titsias_eval(Zk, self._sigma(), self.jitter, kff, grad=grad, sharded=self._data_shard() is not None)
-        except MogpError as e:
-            if e.code in (MOGP_ENOTPD, MOGP_ENONFINITE):
-                print("ERROR:", str(e), file=sys.__stdout__)
-                self.print_parameters()
-                raise CholeskyException(str(e), None, self)
-            raise
         return res, table, D, Zk
 
     def elbo(self):
@@ -620,28 +696,14 @@ class Titsias(_DataParallel, Model):
         res, table, D, Zk = self._run(grad=True)
         C = table.shape[0]
         s2 = self._sigma() ** 2
-        M = Zk.shape[0]
-        zc = np.bincount(Zk[:, 0].astype(np.int64), minlength=C).astype(np.float64)
-        xc = self.__dict__.get("_xc_cache")                    # training points per channel: X does not change under a model (O(N) per evaluation otherwise)
-        if xc is None or xc[0] is not self.X or xc[1].shape[0] != C:
-            xc = (self.X, np.bincount(self.kernel._kernel_format(self.X)[:, 0].astype(np.int64), minlength=C).astype(np.float64))
-            self.__dict__["_xc_cache"] = xc
-        xc = xc[1]
-        gt = _gtable_from_moments(table, res["mom_uu"], D, lower=True) + _gtable_from_moments(table, res["mom_uf"], D, lower=False)
-        env = table.shape[3] > 2 + 3 * D
-        gz_jit = 0.0
-        if env:
-            # with an envelope (MOHSM) the diagonal follows the points: jitter * mean(diag Kuu) depends on A, L, c AND on Z itself, and
-            # sum_k Kff_diag[k] is a sum over the training points (reference gpr/model.py:244, :723 through autograd)
-            gt += (self.jitter * res["trGA"] / M) * self.kernel._point_diag_table_grad(table, Zk, D)
-            gz_jit = (self.jitter * res["trGA"] / M) * self.kernel._point_diag_input_grad(table, Zk, D)
+        xc = self._train_counts()
+        gt = self._inducing_backward(table, D, Zk, res["mom_uu"], res["mom_uf"], res["trGA"], res["gZ"])
+        if _enveloped(table, D):
+            # sum_k Kff_diag[k] is a sum over the training points (reference gpr/model.py:723 through autograd)
             self.kernel._spectral_backward(-gt + (0.5 / s2) * self.kernel._point_diag_table_grad(table, self.kernel._kernel_format(self.X), D))
         else:
-            for i in range(C):
-                gt[i, i, :, 0] += self.jitter * res["trGA"] * zc[i] / M          # jitter * mean(diag Kuu), gpr/model.py:244
             # - 1/(2 s2) sum_k Kff_diag[k]  (gpr/model.py:723): K_diag is constant per channel.  Where K_diag[c] is the sum of the diagonal amplitudes
             # (the kernels that keep Kernel._spectral_diag_backward) that is a table gradient too: ONE pass through the parameter algebra instead of two
-            from .kernel import Kernel
             if type(self.kernel)._spectral_diag_backward is Kernel._spectral_diag_backward:
                 for i in range(C):
                     gt[i, i, :, 0] -= 0.5 * xc[i] / s2
@@ -651,80 +713,46 @@ class Titsias(_DataParallel, Model):
                 self.kernel._spectral_diag_backward(0.5 * xc / s2, D)
         scale = self.likelihood.scale
         scale.accumulate_grad(np.reshape(-res["dsigma"], scale.data.shape))
-        gz = np.zeros(self.Z.data.shape)
-        off = 0 if self.kernel.output_dims is None else 1
-        gz[:, off:] = -(res["gZ"] + gz_jit)
-        self.Z.accumulate_grad(gz)
         self._mean_backward(self._handle)
         return config.dtype(-res["elbo"] - self.log_prior())
 
     def predict_f(self, X, full=False):
         """reference gpr/model.py:730-765"""
         X = self._check_input(X)
-        h = self._device_handle()
-        self._sync_mean(h)
-        D = self.X.shape[1] - (0 if self.kernel.output_dims is None else 1)
-        h.set_terms(self.kernel._spectral_terms(D))
-        table = self.kernel._spectral_terms(D)
+        h, table, D = self._push()
         Xsk = self.kernel._kernel_format(X)
-        kss = self.kernel._point_diag(table, Xsk, D) if table.shape[3] > 2 + 3 * D else self.kernel._spectral_diag(D)
-        mu, var = h.titsias_predict(self.kernel._kernel_format(self.Z()), self._sigma(), self.jitter,
-                                    Xsk, kss, sharded=self._data_shard() is not None)
-        if full:                                        # K_ss - a^T a + b^T b with the a, b this prediction left on the device (reference :758-760)
-            var = h.sparse_predict_cov(X.shape[0])
-        if self.mean is not None:
-            mu = mu + np.asarray(self.mean(X)).reshape(-1, 1)
-        return mu, var
+        with self._cholesky_guard():
+            mu, var = h.titsias_predict(self.kernel._kernel_format(self.Z()), self._sigma(), self.jitter,
+                                        Xsk, self._kernel_diag(table, Xsk, D), sharded=self._data_shard() is not None)
+            if full:                                        # K_ss - a^T a + b^T b with the a, b this prediction left on the device (reference :758-760)
+                var = h.sparse_predict_cov(X.shape[0])
+        return self._add_mean(mu, X), var
 
 
-class Snelson(_DataParallel, Model):
+class Snelson(_InducingPoints, Model):
     """
     Sparse GP regression with pseudo-inputs, Snelson & Ghahramani 2005 (reference gpr/model.py:485-576): the FITC marginal likelihood
         p = log N(y | 0, Qff + diag(Kff - Qff) + sigma^2 I),   Qff = Kfu Kuu^-1 Kuf,
     with trainable inducing inputs `Z` (their channel column carries no gradient) and a scalar or per-channel noise variance.
     """
+    _noise_dtype = np.float64
 
     def __init__(self, kernel, X, y, Z=10, Z_init="grid", variance=1.0, jitter=1e-8, mean=None):
         variance = np.squeeze(Parameter.to_tensor(variance))
         if 1 < variance.ndim or variance.ndim == 1 and variance.shape[0] != kernel.output_dims:
             raise ValueError("variance must be float or have shape (channels,)")
         super().__init__(kernel, X, y, GaussianLikelihood(np.sqrt(variance)), jitter, mean)
-        Z = init_inducing_points(Z, self.X, method=Z_init, output_dims=kernel.output_dims)
-        Z = self._check_input(Z)
-        self.log_marginal_likelihood_constant = 0.5 * self.X.shape[0] * np.log(2.0 * np.pi)
-        self.Z = Parameter(Z, name="induction_points")
-        if kernel.output_dims is not None:
-            self.Z.num_parameters -= self.Z().shape[0]
-
-    def _noise_vector(self):
-        """sigma_c^2 per channel (a scalar scale is shared by all channels: reference _index_channel, gpr/model.py:183-186)"""
-        s = np.asarray(self.likelihood.scale(), dtype=np.float64)
-        C = self.kernel._channels()
-        if s.ndim == 1 and s.shape[0] == C and self.kernel.output_dims is not None:
-            return s * s
-        return np.repeat(s.reshape(-1)[0] ** 2, C)
+        self.Z = self._init_inducing(Z, Z_init)
 
     def _run(self, grad):
-        from .._lib import MogpError, MOGP_ENOTPD, MOGP_ENONFINITE
-        h = self._device_handle()
-        self._sync_mean(h)
-        D = self.X.shape[1] - (0 if self.kernel.output_dims is None else 1)
-        table = self.kernel._spectral_terms(D)
-        h.set_terms(table)
+        h, table, D = self._push()
         Zk = self.kernel._kernel_format(self.Z())
-        env = table.shape[3] > 2 + 3 * D                  # enveloped terms (MOHSM): the kernel diagonal follows the points
-        if env and self._data_shard() is not None:
+        if _enveloped(table, D) and self._data_shard() is not None:
             raise NotImplementedError("Snelson with an enveloped kernel (MOHSM) is single-process only: its per-point diagonal gradient is not reduced "
                                       "over the ranks of the data-parallel form")
-        kff = self.kernel._point_diag(table, self._local(self.kernel._kernel_format(self.X)), D) if env else self.kernel._spectral_diag(D)
-        try:
-            res = h.snelson_eval(Zk, self._noise_vector(), self.jitter, kff, grad=grad, sharded=self._data_shard() is not None)
-        except MogpError as e:
-            if e.code in (MOGP_ENOTPD, MOGP_ENONFINITE):
-                print("ERROR:", str(e), file=sys.__stdout__)
-                self.print_parameters()
-                raise CholeskyException(str(e), None, self)
-            raise
+        kff = self._kernel_diag(table, self._local_Xk(), D)
+        with self._cholesky_guard():
+            res = h.snelson_eval(Zk, self._noise_var(), self.jitter, kff, grad=grad, sharded=self._data_shard() is not None)
         return res, table, D, Zk
 
     def log_marginal_likelihood(self):
@@ -736,36 +764,18 @@ class Snelson(_DataParallel, Model):
         self.zero_grad(set_to_none=True)
         res, table, D, Zk = self._run(grad=True)
         C = table.shape[0]
-        M = Zk.shape[0]
-        zc = np.bincount(Zk[:, 0].astype(np.int64), minlength=C).astype(np.float64)
-        gt = _gtable_from_moments(table, res["mom_uu"], D, lower=True) + _gtable_from_moments(table, res["mom_uf"], D, lower=False)
-        gz_jit = 0.0
-        if table.shape[3] > 2 + 3 * D:
-            # enveloped terms: jitter * mean(diag Kuu) depends on A, L, c and on Z itself (gpr/model.py:244 through autograd); dp/dKff_nn comes
-            # back per training point and goes through the per-point diagonal K_diag(x_n) = sum_t A_t env_t(x_n)
+        gt = self._inducing_backward(table, D, Zk, res["mom_uu"], res["mom_uf"], res["trGA"], res["gZ"])
+        if _enveloped(table, D):
+            # enveloped terms: dp/dKff_nn comes back per training point and goes through the per-point diagonal K_diag(x_n) = sum_t A_t env_t(x_n)
             Xk = self.kernel._kernel_format(self.X)
             h_pt = np.asarray(res["hsum"], dtype=np.float64)
-            gt += (self.jitter * res["trGA"] / M) * self.kernel._point_diag_table_grad(table, Zk, D)
-            gz_jit = (self.jitter * res["trGA"] / M) * self.kernel._point_diag_input_grad(table, Zk, D)
             self.kernel._spectral_backward(-gt - self.kernel._point_diag_table_grad(table, Xk, D, weights=h_pt))
             hsum = np.bincount(Xk[:, 0].astype(np.int64), weights=h_pt, minlength=C).astype(np.float64)
         else:
-            for i in range(C):
-                gt[i, i, :, 0] += self.jitter * res["trGA"] * zc[i] / M          # jitter * mean(diag Kuu), gpr/model.py:244
             self.kernel._spectral_backward(-gt)
             hsum = np.asarray(res["hsum"], dtype=np.float64)                     # d p / d Kff_diag = d p / d sigma^2, summed per channel
             self.kernel._spectral_diag_backward(-hsum, D)
-        scale = self.likelihood.scale
-        sc = np.asarray(scale(), dtype=np.float64)
-        if sc.ndim == 1 and sc.shape[0] == C and self.kernel.output_dims is not None:
-            gsc = 2.0 * sc * hsum
-        else:
-            gsc = np.reshape(2.0 * sc * np.sum(hsum), sc.shape)
-        scale.accumulate_grad(-gsc)
-        gz = np.zeros(self.Z.data.shape)
-        off = 0 if self.kernel.output_dims is None else 1
-        gz[:, off:] = -(res["gZ"] + gz_jit)
-        self.Z.accumulate_grad(gz)
+        self._noise_backward(hsum)
         self._mean_backward(self._handle)
         return config.dtype(-res["lml"] - self.log_prior())
 
@@ -774,22 +784,13 @@ class Snelson(_DataParallel, Model):
         if full:
             raise NotImplementedError("full predictive covariance for Snelson is not on the HIP path")
         X = self._check_input(X)
-        h = self._device_handle()
-        self._sync_mean(h)
-        D = self.X.shape[1] - (0 if self.kernel.output_dims is None else 1)
-        table = self.kernel._spectral_terms(D)
-        h.set_terms(table)
+        h, table, D = self._push()
         Xsk = self.kernel._kernel_format(X)
-        if table.shape[3] > 2 + 3 * D:                    # enveloped terms: K_diag per training / test point
-            kd = self.kernel._point_diag(table, self._local(self.kernel._kernel_format(self.X)), D)
-            ks = self.kernel._point_diag(table, Xsk, D)
-        else:
-            kd = ks = self.kernel._spectral_diag(D)
-        mu, var = h.snelson_predict(self.kernel._kernel_format(self.Z()), self._noise_vector(), self.jitter,
-                                    Xsk, kd, ks, sharded=self._data_shard() is not None)
-        if self.mean is not None:
-            mu = mu + np.asarray(self.mean(X)).reshape(-1, 1)
-        return mu, var
+        kd, ks = self._kernel_diags(table, Xsk, D)
+        with self._cholesky_guard():
+            mu, var = h.snelson_predict(self.kernel._kernel_format(self.Z()), self._noise_var(), self.jitter,
+                                        Xsk, kd, ks, sharded=self._data_shard() is not None)
+        return self._add_mean(mu, X), var
 
 
 class OpperArchambeau(Model):
@@ -800,6 +801,7 @@ class OpperArchambeau(Model):
     O(N)) returns its expectation and dE/dmu, dE/dvar; backward -> the gradients of kernel, q_nu, q_lambda.  Any likelihood of gpr/likelihood.py (its expectation and derivatives are the host's; the device algebra never sees it).
     No jitter enters (the reference's Cholesky calls here pass add_jitter=False); `jitter` is kept for the signature.
     """
+    _device_mean = False
 
     def __init__(self, kernel, X, y, likelihood=None, jitter=1e-8, mean=None):
         if likelihood is None:
@@ -810,26 +812,13 @@ class OpperArchambeau(Model):
         self.q_nu = Parameter(np.zeros((n, 1)))
         self.q_lambda = Parameter(np.ones((n, 1)), lower=config.positive_minimum)
 
-    def _device_handle(self):
-        if self._handle is None:
-            from .._lib import ExactHandle
-            self._handle = ExactHandle(config.device, self.kernel._kernel_format(self.X), self.y, self.kernel._channels())
-        return self._handle
+    def _handle_y(self):
+        return self.y                       # a mean function is subtracted on the host (_targets)
 
     def _forward(self):
-        from .._lib import MogpError, MOGP_ENOTPD, MOGP_ENONFINITE
-        h = self._device_handle()
-        D = self.X.shape[1] - (0 if self.kernel.output_dims is None else 1)
-        table = self.kernel._spectral_terms(D)
-        h.set_terms(table)
-        try:
+        h, table, D = self._push()
+        with self._cholesky_guard():
             res = h.oa_forward(self.q_nu(), self.q_lambda())
-        except MogpError as e:
-            if e.code in (MOGP_ENOTPD, MOGP_ENONFINITE):
-                print("ERROR:", str(e), file=sys.__stdout__)
-                self.print_parameters()
-                raise CholeskyException(str(e), None, self)
-            raise
         return h, res, table, D
 
     def _targets(self, mu):
@@ -864,16 +853,13 @@ class OpperArchambeau(Model):
     def predict_f(self, X, full=False):
         """reference gpr/model.py:640-668"""
         X = self._check_input(X)
-        h = self._device_handle()
-        D = self.X.shape[1] - (0 if self.kernel.output_dims is None else 1)
-        h.set_terms(self.kernel._spectral_terms(D))
-        mu, var = h.oa_predict(self.q_nu(), self.q_lambda(), self.kernel._spectral_diag(D), self.kernel._kernel_format(X), full=full)
-        if self.mean is not None:
-            mu = mu + np.asarray(self.mean(X)).reshape(-1, 1)
-        return mu, var
+        h, _, D = self._push()
+        with self._cholesky_guard():
+            mu, var = h.oa_predict(self.q_nu(), self.q_lambda(), self.kernel._spectral_diag(D), self.kernel._kernel_format(X), full=full)
+        return self._add_mean(mu, X), var
 
 
-class SparseHensman(_DataParallel, Model):
+class SparseHensman(_InducingPoints, Model):
     """
     Sparse variational GP of Hensman et al. 2015, whitened (reference gpr/model.py:767-878): q(u) = N(L q_mu, L S S^T L^T), L L^T = Kuu,
     S = tril(q_sqrt);  ELBO = E_q[log p(y | f)] - KL(q || p).  The O(N M^2) algebra runs on the device in two calls around the
@@ -881,28 +867,24 @@ class SparseHensman(_DataParallel, Model):
     dE/dmu, dE/dvar; backward -> the gradients of kernel, inducing inputs, q_mu, q_sqrt.  Any likelihood of gpr/likelihood.py (its expectation and derivatives are the host's; the device algebra never sees it).
     The KL term mirrors the reference's (:816-822), which counts only the DIAGONAL of q_sqrt in the trace and the determinant.
     """
+    _device_mean = False
 
     def __init__(self, kernel, X, y, Z=None, Z_init="grid", likelihood=None, jitter=1e-8, mean=None):
         if likelihood is None:
             likelihood = GaussianLikelihood(1.0)
         super().__init__(kernel, X, y, likelihood, jitter, mean)
         self._mean_refuse("%s (the variational expectation's derivative with respect to y)" % self.__class__.__name__)
-        n = self.X.shape[0]
         self.is_sparse = Z is not None
         if self.is_sparse:
-            Z = init_inducing_points(Z, self.X, method=Z_init, output_dims=kernel.output_dims)
-            Z = self._check_input(Z)
-            n = Z.shape[0]
-        self.log_marginal_likelihood_constant = 0.5 * self.X.shape[0] * np.log(2.0 * np.pi)
+            Z = self._init_inducing(Z, Z_init)
+        else:
+            self.log_marginal_likelihood_constant = _lml_constant(self.X)
+            Z = Parameter(self.X, train=False)              # the data points themselves, not trained (reference :812)
+        n = Z.data.shape[0]
         self.q_mu = Parameter(np.zeros((n, 1)))
         self.q_sqrt = Parameter(np.eye(n))
         self.q_sqrt.num_parameters = int((n * n + n) / 2)
-        if self.is_sparse:
-            self.Z = Parameter(Z, name="induction_points")
-            if kernel.output_dims is not None:
-                self.Z.num_parameters -= self.Z().shape[0]
-        else:
-            self.Z = Parameter(self.X, train=False)         # the data points themselves, not trained (reference :812)
+        self.Z = Z
 
     def _shardable(self):
         return self.is_sparse               # the non-sparse model lives on all data points
@@ -922,25 +904,14 @@ class SparseHensman(_DataParallel, Model):
         return 0.5 * (float(np.sum(q_mu * q_mu)) - np.sum(np.log(S_diag)) + np.sum(S_diag) - q_mu.shape[0])
 
     def _forward(self):
-        from .._lib import MogpError, MOGP_ENOTPD, MOGP_ENONFINITE
-        h = self._device_handle()
-        D = self.X.shape[1] - (0 if self.kernel.output_dims is None else 1)
-        table = self.kernel._spectral_terms(D)
-        h.set_terms(table)
+        h, table, D = self._push()
         Zk = self.kernel._kernel_format(self.Z())
-        env = table.shape[3] > 2 + 3 * D                  # enveloped terms (MOHSM): the kernel diagonal follows the points
-        if env and self._data_shard() is not None:
+        if _enveloped(table, D) and self._data_shard() is not None:
             raise NotImplementedError("SparseHensman with an enveloped kernel (MOHSM) is single-process only: the per-point diagonal gradient is not "
                                       "reduced over the ranks of the data-parallel form")
-        kff = self.kernel._point_diag(table, self._local(self.kernel._kernel_format(self.X)), D) if env else self.kernel._spectral_diag(D)
-        try:
+        kff = self._kernel_diag(table, self._local_Xk(), D)
+        with self._cholesky_guard():
             res = h.svgp_forward(Zk, self.q_mu(), self.q_sqrt(), self.jitter, kff, dense=not self.is_sparse)
-        except MogpError as e:
-            if e.code in (MOGP_ENOTPD, MOGP_ENONFINITE):
-                print("ERROR:", str(e), file=sys.__stdout__)
-                self.print_parameters()
-                raise CholeskyException(str(e), None, self)
-            raise
         return h, res, table, D, Zk
 
     def _y(self):
@@ -972,59 +943,36 @@ class SparseHensman(_DataParallel, Model):
         q_mu, q_sqrt = np.asarray(self.q_mu(), dtype=np.float64), np.asarray(self.q_sqrt(), dtype=np.float64)
         elbo = ve - self.kl_gaussian(q_mu, q_sqrt)
         bw = h.svgp_backward(e, f, sharded=sharded)
-        C = table.shape[0]
-        M = Zk.shape[0]
-        zc = np.bincount(Zk[:, 0].astype(np.int64), minlength=C).astype(np.float64)
-        xc = self._local(self.kernel._kernel_format(self.X))[:, 0].astype(np.int64)
-        gt = _gtable_from_moments(table, bw["mom_uu"], D, lower=True) + _gtable_from_moments(table, bw["mom_uf"], D, lower=False)
-        gz_jit = 0.0
-        if table.shape[3] > 2 + 3 * D:
-            # enveloped terms: jitter * mean(diag Kuu) depends on A, L, c and on the inducing inputs themselves (gpr/model.py:244 through autograd),
-            # and var_n = K_diag(x_n) - ... goes back through the per-point diagonal with the likelihood's d/dvar_n as weights
-            gt += (self.jitter * bw["trGA"] / M) * self.kernel._point_diag_table_grad(table, Zk, D)
-            gz_jit = (self.jitter * bw["trGA"] / M) * self.kernel._point_diag_input_grad(table, Zk, D)
+        gt = self._inducing_backward(table, D, Zk, bw["mom_uu"], bw["mom_uf"], bw["trGA"], bw["gZ"] if self.is_sparse else None)
+        # var_n = K_diag(x_n) - ... goes back through the kernel diagonal with the likelihood's d/dvar_n as weights (the dense model's variance at its own
+        # inputs has no such term): per point with enveloped terms, else summed per channel
+        if _enveloped(table, D):
             if self.is_sparse:
-                gt += self.kernel._point_diag_table_grad(table, self._local(self.kernel._kernel_format(self.X)), D, weights=f)
+                gt += self.kernel._point_diag_table_grad(table, self._local_Xk(), D, weights=f)
             self.kernel._spectral_backward(-gt)
         else:
-            for i in range(C):
-                gt[i, i, :, 0] += self.jitter * bw["trGA"] * zc[i] / M          # jitter * mean(diag Kuu), gpr/model.py:244
             self.kernel._spectral_backward(-gt)
-            if self.is_sparse:                          # var_n = K_diag[c(n)] - ... (the dense model's variance at its own inputs has no such term)
-                self.kernel._spectral_diag_backward(-self._reduce(np.bincount(xc, weights=f, minlength=C)), D)
+            if self.is_sparse:
+                xc = self._local_Xk()[:, 0].astype(np.int64)
+                self.kernel._spectral_diag_backward(-self._reduce(np.bincount(xc, weights=f, minlength=table.shape[0])), D)
         for p, g in pgrads:
             p.accumulate_grad(np.reshape(-np.asarray(g, dtype=np.float64), p.data.shape))
         self.q_mu.accumulate_grad(-(np.reshape(bw["g_qmu"], q_mu.shape) - q_mu))
         s = np.diagonal(q_sqrt)
         self.q_sqrt.accumulate_grad(-(np.tril(bw["g_qsqrt"]) - np.diag(s - 1.0 / s)))
-        if self.is_sparse:
-            gz = np.zeros(self.Z.data.shape)
-            off = 0 if self.kernel.output_dims is None else 1
-            gz[:, off:] = -(bw["gZ"] + gz_jit)
-            self.Z.accumulate_grad(gz)
         return config.dtype(-elbo - self.log_prior())
 
     def predict_f(self, X, full=False):
         """reference gpr/model.py:851-878"""
         X = self._check_input(X)
-        h = self._device_handle()
-        D = self.X.shape[1] - (0 if self.kernel.output_dims is None else 1)
-        table = self.kernel._spectral_terms(D)
-        h.set_terms(table)
+        h, table, D = self._push()
         Xsk = self.kernel._kernel_format(X)
-        if table.shape[3] > 2 + 3 * D:                    # enveloped terms: K_diag per training / test point
-            kd = self.kernel._point_diag(table, self._local(self.kernel._kernel_format(self.X)), D)
-            ks = self.kernel._point_diag(table, Xsk, D)
-        else:
-            kd = ks = self.kernel._spectral_diag(D)
-        res = h.svgp_forward(self.kernel._kernel_format(self.Z()), self.q_mu(), self.q_sqrt(), self.jitter, kd,
-                             Xs=Xsk, kss_diag=ks)
-        mu = np.reshape(res["mu"], (-1, 1))
-        if self.mean is not None:
-            mu = mu + np.asarray(self.mean(X)).reshape(-1, 1)
-        if full:                                        # reference :870-872
-            return mu, h.sparse_predict_cov(X.shape[0])
-        return mu, np.reshape(res["var"], (-1, 1))
+        kd, ks = self._kernel_diags(table, Xsk, D)
+        with self._cholesky_guard():
+            res = h.svgp_forward(self.kernel._kernel_format(self.Z()), self.q_mu(), self.q_sqrt(), self.jitter, kd,
+                                 Xs=Xsk, kss_diag=ks)
+            var = h.sparse_predict_cov(X.shape[0]) if full else np.reshape(res["var"], (-1, 1))      # reference :870-872
+        return self._add_mean(np.reshape(res["mu"], (-1, 1)), X), var
 
 
 class Hensman(SparseHensman):

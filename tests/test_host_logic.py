@@ -1288,3 +1288,52 @@ def test_ill_conditioned_models_warn_once_and_switch_to_the_backward_stable_form
     finally:
         gpr.config.accurate_fallback = True
         L.ExactHandle = old
+
+
+# ---- the one Cholesky guard of gpr/model.py: every device call that factorises, loss() and predict_f() of all six models -----------------------
+def _guard_models():
+    rng = np.random.default_rng(5)
+    x = np.sort(rng.uniform(0, 10, 12))
+    X = np.c_[np.repeat([0, 1], 6), x]
+    y = np.sin(x) + 0.1 * rng.standard_normal(12)
+    k = lambda: gpr.MultiOutputSpectralMixtureKernel(Q=1, output_dims=2)
+    return X, [gpr.Exact(k(), X, y, variance=0.04), gpr.Titsias(k(), X, y, Z=2, variance=0.04), gpr.Snelson(k(), X, y, Z=2, variance=0.04),
+               gpr.OpperArchambeau(k(), X, y), gpr.SparseHensman(k(), X, y, Z=2), gpr.Hensman(k(), X, y)]
+
+
+_GUARDED = {"Exact": ("eval", "predict"), "Titsias": ("titsias_eval", "titsias_predict"), "Snelson": ("snelson_eval", "snelson_predict"),
+            "OpperArchambeau": ("oa_forward", "oa_predict"), "SparseHensman": ("svgp_forward", "svgp_forward"), "Hensman": ("svgp_forward", "svgp_forward")}
+
+
+def test_not_positive_definite_becomes_cholesky_exception_in_every_model(monkeypatch, capsys):
+    """the device reports MOGP_ENOTPD from the call loss() / predict_f() makes: CholeskyException(message, None, model) as the reference raises it
+    (gpr/model.py:245-255), `ERROR:` on sys.__stdout__ and the parameter table printed; any other code passes through unchanged"""
+    import io
+    import sys
+    X, models = _guard_models()
+    assert [m.Z().shape[0] for m in models[1:3] + models[4:5]] == [4, 4, 4]
+    code = [L.MOGP_ENOTPD]
+
+    def fail(self, *a, **k):
+        raise L.MogpError(code[0], "matrix is not positive definite at pivot 3")
+
+    for m in models:
+        for method, call in zip(_GUARDED[m.name()], (m.loss, lambda: m.predict_f(X[:3]))):
+            real_out = io.StringIO()
+            with monkeypatch.context() as mp:
+                mp.setattr(TableDevice, method, fail)
+                mp.setattr(sys, "__stdout__", real_out)
+                capsys.readouterr()
+                with pytest.raises(gpr.CholeskyException) as e:
+                    call()
+            assert str(e.value) == e.value.message == "matrix is not positive definite at pivot 3", (m.name(), method)
+            assert e.value.model is m and e.value.K is None
+            assert real_out.getvalue() == "ERROR: matrix is not positive definite at pivot 3\n"
+            table = capsys.readouterr().out.splitlines()
+            assert table[0].split() == ["Name", "Value"] and len(table) == 1 + len(list(m.parameters())), (m.name(), method, table)
+    code[0] = L.MOGP_EINVAL
+    with monkeypatch.context() as mp:
+        mp.setattr(TableDevice, "titsias_predict", fail)
+        with pytest.raises(L.MogpError) as e:
+            models[1].predict_f(X[:3])
+    assert e.value.code == L.MOGP_EINVAL and not isinstance(e.value, gpr.CholeskyException)
