@@ -109,7 +109,18 @@ int  mogp_gram_ex(mogp_ctx* ctx, int C, int D, int T, int width, const double* t
  * zero: Gaussian, and nothing of an evaluation changes.  With a non-zero kind the exact evaluation and prediction (mogp_exact_eval,
  * mogp_exact_predict) build every Gram tile entry by entry and form the whole of Kj^-1; the gradient moments keep their layout and host
  * formulas, with psi = -2 dphi/ds in place of phi in m1_d and m2_d (u_d^2 psi = u_d psi = 0 where kind 2 has r = 0).  Rows of width 2 + 3 D
- * only.  The sparse, variational and sharded entry points do not take kinds: gpr/ refuses them before any call. */
+ * only.  The sparse, variational and sharded entry points do not take kinds: gpr/ refuses them before any call.
+ *   kind 5  exp(V (cos theta - 1)), theta = 2 pi (M u + Psi)   (periodic, reference PeriodicKernel.K :362-374 with V = 1 / l^2, M = 1 / p):
+ *           the phase is the ARGUMENT of the profile, there is no cosine factor beside it; D = 1 only.  Its moments, E the profile:
+ *           m0 = sum g E, m4 = sum g E V sin theta, m1 = sum g E 2 (1 - cos theta), m2 = 0, m3 = sum g E V u sin theta -- the host formulas hold.
+ * Product groups (reference MulKernel.K, gpr/kernel.py:258-259): a kind with MOGP_KIND_TIMES set multiplies its row with the NEXT row of the
+ * same pair; the low 8 bits stay the profile.  A maximal run of flagged rows plus the row that ends it is a group, its value the product
+ * of its rows' values A phi cos, and K the sum over groups (a plain row is a group of one).  At most 4 rows per group, the last row of a
+ * table unflagged, the same flags in every channel pair; anything else is MOGP_EINVAL.  A row's moments are then those of the row alone
+ * with the adjoint weighted, entry by entry, by the product of the group's OTHER rows, so dK/d(row) keeps its formulas.  K(x, x) of a
+ * group is the product of its amplitudes (the relative jitter uses it).  A flag alone (all profiles Gaussian) is a non-zero kind. */
+#define MOGP_KIND_PERIODIC 5
+#define MOGP_KIND_TIMES (1 << 8)
 int  mogp_model_set_kinds(mogp_model* m, int T, const int* kind, const double* shape);
 /* mogp_gram_ex with kinds (NULL: mogp_gram_ex itself): replaces Kernel.K of the kernels above, and of their sums, IndependentMultiOutputKernel
  * and LinearModelOfCoregionalizationKernel compositions (gpr/kernel.py:138-150, :232-246, gpr/multioutput.py:5-39, :456-502) */

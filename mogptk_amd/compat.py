@@ -252,7 +252,7 @@ def _convert_kernel(bag):
         return cls(*subs, output_dims=odims, input_dims=idims, Rq=params["weight"].data.shape[2])
     if name == "SpectralMixtureKernel":
         return cls(Q=params["magnitude"].data.shape[0], input_dims=idims)
-    if name == "SquaredExponentialKernel":
+    if name in ("SquaredExponentialKernel", "PeriodicKernel", "LocallyPeriodicKernel"):
         return cls(order=st.get("order", 0), input_dims=idims)
     if name == "RationalQuadraticKernel":
         return cls(alpha=float(st.get("alpha", 1.0)), order=st.get("order", 0), input_dims=idims)
@@ -471,6 +471,7 @@ _REF_KERNEL_MODULE = {
     "AddKernel": "kernel", "MulKernel": "kernel", "MixtureKernel": "kernel",
     "SpectralKernel": "singleoutput", "SpectralMixtureKernel": "singleoutput", "SquaredExponentialKernel": "singleoutput",
     "RationalQuadraticKernel": "singleoutput", "MaternKernel": "singleoutput", "ExponentialKernel": "singleoutput",
+    "ConstantKernel": "singleoutput", "CosineKernel": "singleoutput", "PeriodicKernel": "singleoutput", "LocallyPeriodicKernel": "singleoutput",
     "IndependentMultiOutputKernel": "multioutput", "MultiOutputSpectralMixtureKernel": "multioutput", "CrossSpectralKernel": "multioutput",
     "LinearModelOfCoregionalizationKernel": "multioutput", "GaussianConvolutionProcessKernel": "multioutput",
     "MultiOutputHarmonizableSpectralKernel": "multioutput", "MultiOutputSpectralKernel": "multioutput",

@@ -226,13 +226,15 @@ __device__ __forceinline__ void stage_item_load(StageItem<DM>& I, int which, int
 // AMP: fold the amplitude A_t into the row factors (Gram); otherwise unit amplitude (moments).  `tab`: the pair's term rows (LDS copy or
 // global memory -- a generic pointer), W doubles each.
 // RAD: a launch with radial profiles (below): no Gaussian factor is split off, every term runs entry by entry (GT_GENERAL) and the staged
-// factors are the plain phase factors (times the amplitude)
+// factors are the plain phase factors (times the amplitude; not for the periodic profile, whose phase is the profile's argument).
+// `kinds`: the pair's kind row (RAD only)
 template <int DM, bool AMP, bool RAD = false>
 __device__ __forceinline__ void stage_item_compute(TileLds<DM>& L, const StageItem<DM>& I, const TileCtx<DM>& X, const double* tab, int W,
-                                                   int which, int t, int pnt, int D, int t0) {
+                                                   int which, int t, int pnt, int D, int t0, const int* kinds = nullptr) {
     const double* row = tab + (size_t)(t0 + t) * W;
     const double A = row[0];
     if constexpr (RAD) {
+        const bool per = (kinds[t0 + t] & MOGP_KIND_MASK) == MOGP_KIND_PERIODIC;
         const int deg = (AMP && A == 0.0) ? GT_SKIP : GT_GENERAL;
         if (pnt == 0 && which == 0) {
             L.deg[t] = deg; L.A[t] = A;
@@ -242,7 +244,7 @@ __device__ __forceinline__ void stage_item_compute(TileLds<DM>& L, const StageIt
             }
         }
         if (deg == GT_SKIP) return;
-        const double f = AMP ? A : 1.0;
+        const double f = (AMP && !per) ? A : 1.0;
         if (which == 0) { L.cu[t][pnt] = f * I.cs; L.su[t][pnt] = f * I.sn; }
         else { L.cw[t][pnt] = I.cs; L.sw[t][pnt] = I.sn; }
         return;
@@ -312,7 +314,7 @@ __device__ __forceinline__ void stage_item_compute(TileLds<DM>& L, const StageIt
 template <int DM, bool AMP, bool BATCH, bool RAD = false>
 __device__ __forceinline__ void stage_chunk(TileLds<DM>& L, const TileCtx<DM>& X, const GTile& tl, const double* tab, int W, int D,
                                             int C, int T, int t0, int nt, const PhaseView& v, const double* __restrict__ xr, int64_t ldxr,
-                                            const double* __restrict__ xc, int64_t ldxc, int tid) {
+                                            const double* __restrict__ xc, int64_t ldxc, int tid, const int* kinds = nullptr) {
     STAGE_MAP(tid);
     if (BATCH) {
         StageItem<DM> I[STAGE_ITEMS];
@@ -321,12 +323,12 @@ __device__ __forceinline__ void stage_chunk(TileLds<DM>& L, const TileCtx<DM>& X
             if (st_tb + 2 * k < nt) stage_item_load<DM>(I[k], st_which, st_tb + 2 * k, st_pnt, tl, D, C, T, t0, v, xr, ldxr, xc, ldxc);
 #pragma unroll
         for (int k = 0; k < STAGE_ITEMS; ++k)
-            if (st_tb + 2 * k < nt) stage_item_compute<DM, AMP, RAD>(L, I[k], X, tab, W, st_which, st_tb + 2 * k, st_pnt, D, t0);
+            if (st_tb + 2 * k < nt) stage_item_compute<DM, AMP, RAD>(L, I[k], X, tab, W, st_which, st_tb + 2 * k, st_pnt, D, t0, kinds);
     } else {
         for (int t = st_tb; t < nt; t += 2) {
             StageItem<DM> I;
             stage_item_load<DM>(I, st_which, t, st_pnt, tl, D, C, T, t0, v, xr, ldxr, xc, ldxc);
-            stage_item_compute<DM, AMP, RAD>(L, I, X, tab, W, st_which, t, st_pnt, D, t0);
+            stage_item_compute<DM, AMP, RAD>(L, I, X, tab, W, st_which, t, st_pnt, D, t0, kinds);
         }
     }
 }
@@ -421,18 +423,58 @@ __device__ __forceinline__ double radial_s(const double (&p)[DM], const double (
     return arg;
 }
 
+// The periodic profile (MOGP_KIND_PERIODIC, D = 1): exp(V (cos theta - 1)) with theta the term's phase -- the Gaussian profile of
+// s = 2 V (1 - cos theta), and no cosine factor beside it.  `cc` = cos theta from the staged UNIT phase factors; the amplitude is L.A[t].
+__device__ __forceinline__ double periodic_s(double V, double cc) { return 2.0 * V * (1.0 - cc); }
+
+// Chunks of a radial launch end at a group end (a group never straddles two chunks): at most MOGP_TC rows from t0 on, shortened while the
+// last one still multiplies with its successor.  `kinds`: one pair's kind row -- the flags are the same in every pair.
+__device__ __forceinline__ int radial_chunk(const int* kinds, int T, int t0) {
+    int nt = min(MOGP_TC, T - t0);
+    while (nt > 1 && t0 + nt < T && (kinds[t0 + nt - 1] & MOGP_KIND_TIMES)) --nt;
+    return nt;
+}
+
 template <int DM>
 __device__ __forceinline__ void gram_term_radial(double (&acc)[4][4], const double (&p)[4][DM], const double (&q)[4][DM], const TileLds<DM>& L, int t,
                                                  int D, int kind, double shape, const double (&cu)[4], const double (&su)[4],
                                                  const double (&cw)[4], const double (&sw)[4]) {
+    const bool per = kind == MOGP_KIND_PERIODIC;
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
         __builtin_amdgcn_sched_barrier(0);                  // one row of four library exps at a time: interleaving all sixteen is what spills
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
             double phi, psi;
-            radial_profile<false>(kind, shape, radial_s<DM>(p[m], q[n], L.V[t], L.s[t], D), phi, psi);
-            acc[m][n] = fma(phi, fma(cu[m], cw[n], su[m] * sw[n]), acc[m][n]);
+            const double cc = fma(cu[m], cw[n], su[m] * sw[n]);
+            radial_profile<false>(kind, shape, per ? periodic_s(L.V[t][0], cc) : radial_s<DM>(p[m], q[n], L.V[t], L.s[t], D), phi, psi);
+            acc[m][n] = per ? fma(L.A[t], phi, acc[m][n]) : fma(phi, cc, acc[m][n]);
+        }
+    }
+}
+
+// One row of a product group: prod *= k_t per entry, k_t = A phi cos theta (the amplitude rides in the staged row factors when AMPF, else
+// it is L.A[t]: the moment pass stages unit amplitudes).
+template <int DM, bool AMPF>
+__device__ __forceinline__ void group_factor_radial(double (&prod)[4][4], const double (&p)[4][DM], const double (&q)[4][DM],
+                                                    const TileLds<DM>& L, int t, int D, int kind, double shape, int rg, int cg) {
+    const bool per = kind == MOGP_KIND_PERIODIC;
+    const double A = L.A[t];
+    double cw[4], sw[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) { cw[n] = L.cw[t][cg * 4 + n]; sw[n] = L.sw[t][cg * 4 + n]; }
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        __builtin_amdgcn_sched_barrier(0);
+        const double cu = L.cu[t][rg * 4 + m], su = L.su[t][rg * 4 + m];
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            double phi, psi;
+            const double cc = fma(cu, cw[n], su * sw[n]);
+            radial_profile<false>(kind, shape, per ? periodic_s(L.V[t][0], cc) : radial_s<DM>(p[m], q[n], L.V[t], L.s[t], D), phi, psi);
+            double k = per ? phi : phi * cc;
+            if (per || !AMPF) k *= A;
+            prod[m][n] *= k;
         }
     }
 }
@@ -500,7 +542,9 @@ __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a, int ntiles) {
     __shared__ TileLds<DM> Lb[2];
     extern __shared__ __attribute__((aligned(16))) double s_tab[];     // the whole term table when it fits (a.tab_lds)
     const PhaseView v = phase_view(a.ph.ws, a.C, a.T, D, a.ldxr, a.ldxc);
-    const int stride = gridDim.x, nt0 = min(MOGP_TC, a.T);
+    const int stride = gridDim.x;
+    int nt0 = min(MOGP_TC, a.T);
+    if constexpr (RAD) nt0 = radial_chunk(a.kind, a.T, 0);     // (the same in every pair)
     STAGE_MAP(tid);
 
     int tile = blockIdx.x;
@@ -530,9 +574,9 @@ __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a, int ntiles) {
         if (BATCH) {
 #pragma unroll
             for (int k = 0; k < STAGE_ITEMS; ++k)
-                if (st_tb + 2 * k < nt0) stage_item_compute<DM, true, RAD>(L, I[k], X, tab, W, st_which, st_tb + 2 * k, st_pnt, D, 0);
+                if (st_tb + 2 * k < nt0) stage_item_compute<DM, true, RAD>(L, I[k], X, tab, W, st_which, st_tb + 2 * k, st_pnt, D, 0, RAD ? a.kind + (size_t)cur.pair * a.T : nullptr);
         } else {
-            stage_chunk<DM, true, false, RAD>(L, X, cur, tab, W, D, a.C, a.T, 0, nt0, v, a.xr, a.ldxr, a.xc, a.ldxc, tid);
+            stage_chunk<DM, true, false, RAD>(L, X, cur, tab, W, D, a.C, a.T, 0, nt0, v, a.xr, a.ldxr, a.xc, a.ldxc, tid, RAD ? a.kind + (size_t)cur.pair * a.T : nullptr);
         }
         double pc[4][DM], qc[4][DM];
 #pragma unroll
@@ -558,15 +602,50 @@ __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a, int ntiles) {
         for (int m = 0; m < 4; ++m)
 #pragma unroll
             for (int n = 0; n < 4; ++n) acc[m][n] = 0.0;
-        for (int t0 = 0; t0 < a.T; t0 += MOGP_TC) {
-            const int nt = min(MOGP_TC, a.T - t0);
+        for (int t0 = 0, nt; t0 < a.T; t0 += RAD ? nt : MOGP_TC) {
+            if constexpr (RAD) nt = radial_chunk(a.kind, a.T, t0); else nt = min(MOGP_TC, a.T - t0);
             if (t0 > 0) {                                   // more than MOGP_TC terms: the later chunks are staged in place
                 __syncthreads();
                 TileCtx<DM> Xc;
                 tile_centres<DM>(Xc, cur, D, v, a.ldxr, a.ldxc);
-                stage_chunk<DM, true, false, RAD>(L, Xc, cur, tab, W, D, a.C, a.T, t0, nt, v, a.xr, a.ldxr, a.xc, a.ldxc, tid);
+                stage_chunk<DM, true, false, RAD>(L, Xc, cur, tab, W, D, a.C, a.T, t0, nt, v, a.xr, a.ldxr, a.xc, a.ldxc, tid, RAD ? a.kind + (size_t)cur.pair * a.T : nullptr);
                 __syncthreads();
             }
+            if constexpr (RAD) {
+                // group by group: [t, te] is a maximal run of rows flagged MOGP_KIND_TIMES plus the row that ends it (a chunk holds whole groups);
+                // a row of zero amplitude makes its whole group zero
+                const int* kd = a.kind + (size_t)cur.pair * a.T + t0;
+                const double* sh = a.shape + (size_t)cur.pair * a.T + t0;
+                for (int t = 0, te; t < nt; t = te + 1) {
+                    bool skip = GRAM_DBG(a, 2);
+                    for (te = t;; ++te) {
+                        skip |= L.deg[te] == GT_SKIP;
+                        if (te == nt - 1 || !(__builtin_amdgcn_readfirstlane(kd[te]) & MOGP_KIND_TIMES)) break;
+                    }
+                    if (skip) continue;
+                    if (te == t) {                          // a group of one: the plain radial term
+                        double cu[4], su[4], cw[4], sw[4];
+#pragma unroll
+                        for (int m = 0; m < 4; ++m) {
+                            cu[m] = L.cu[t][rg * 4 + m]; su[m] = L.su[t][rg * 4 + m];
+                            cw[m] = L.cw[t][cg * 4 + m]; sw[m] = L.sw[t][cg * 4 + m];
+                        }
+                        gram_term_radial<DM>(acc, pc, qc, L, t, D, __builtin_amdgcn_readfirstlane(kd[t]) & MOGP_KIND_MASK, sh[t], cu, su, cw, sw);
+                        continue;
+                    }
+                    double prod[4][4];
+#pragma unroll
+                    for (int m = 0; m < 4; ++m)
+#pragma unroll
+                        for (int n = 0; n < 4; ++n) prod[m][n] = 1.0;
+                    for (int f = t; f <= te; ++f)
+                        group_factor_radial<DM, true>(prod, pc, qc, L, f, D, __builtin_amdgcn_readfirstlane(kd[f]) & MOGP_KIND_MASK, sh[f], rg, cg);
+#pragma unroll
+                    for (int m = 0; m < 4; ++m)
+#pragma unroll
+                        for (int n = 0; n < 4; ++n) acc[m][n] += prod[m][n];
+                }
+            } else
             for (int t = 0; t < nt; ++t) {
                 const int deg = L.deg[t];
                 if (deg == GT_SKIP || GRAM_DBG(a, 2)) continue;
@@ -575,12 +654,6 @@ __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a, int ntiles) {
                 for (int m = 0; m < 4; ++m) {
                     cu[m] = L.cu[t][rg * 4 + m]; su[m] = L.su[t][rg * 4 + m];
                     cw[m] = L.cw[t][cg * 4 + m]; sw[m] = L.sw[t][cg * 4 + m];
-                }
-                if constexpr (RAD) {
-                    const size_t kt = (size_t)cur.pair * a.T + t0 + t;
-                    const int kind = __builtin_amdgcn_readfirstlane(a.kind[kt]);
-                    gram_term_radial<DM>(acc, pc, qc, L, t, D, kind, a.shape[kt], cu, su, cw, sw);
-                    continue;
                 }
                 switch (deg) {
                     #define GT_CASE(N) case N: gram_term<DM, N>(acc, pc, qc, L, t, D, cu, su, cw, sw); break;
@@ -1180,6 +1253,7 @@ __device__ __forceinline__ void moment_term_radial(double* mom, const double (&g
                                                    const double (&cu)[4], const double (&su)[4], const double (&cw)[4], const double (&sw)[4]) {
     const double* V = L.V[t];
     const double* s = L.s[t];
+    const bool per = kind == MOGP_KIND_PERIODIC;             // (D = 1: the moment slots are 0, 1, 2, 3, 4)
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
 #pragma unroll
@@ -1191,8 +1265,17 @@ __device__ __forceinline__ void moment_term_radial(double* mom, const double (&g
                 arg = fma(V[d] * u[d], u[d], arg);
             }
             double phi, psi;
-            radial_profile<true>(kind, shape, arg, phi, psi);
             const double cc = fma(cu[m], cw[n], su[m] * sw[n]), sn = fma(su[m], cw[n], -cu[m] * sw[n]);
+            if (per) {                                      // E = exp(V (cos - 1)): m0 = g E, m4 = g E V sin, m1 = g E 2 (1 - cos), m2 = 0, m3 = g E V u sin
+                radial_profile<false>(MOGP_KIND_GAUSS, shape, periodic_s(V[0], cc), phi, psi);
+                const double ge = g[m][n] * phi, ks = ge * V[0] * sn;
+                mom[0] += ge;
+                mom[1] += ks;
+                mom[2] = fma(ge, 2.0 * (1.0 - cc), mom[2]);
+                mom[4] = fma(u[0], ks, mom[4]);
+                continue;
+            }
+            radial_profile<true>(kind, shape, arg, phi, psi);
             const double kc = g[m][n] * phi * cc;
             const double ks = g[m][n] * phi * sn;
             const double kp = g[m][n] * psi * cc;
@@ -1286,11 +1369,13 @@ __global__ __launch_bounds__(256, (DT == 1 && !RAD ? 2 : 1)) void k_moments(Mome
     }
 
     int nred = 0;                                            // reductions done so far (selects the staging buffer)
-    for (int t0 = 0; t0 < a.T; t0 += MOGP_TC) {
-        const int nt = min(MOGP_TC, a.T - t0);
+    int tg = 0, te = -1;                                     // RAD: the product group [tg, te] (chunk-relative) that row t belongs to
+    for (int t0 = 0, nt; t0 < a.T; t0 += RAD ? nt : MOGP_TC) {
+        if constexpr (RAD) nt = radial_chunk(a.kind, a.T, t0); else nt = min(MOGP_TC, a.T - t0);
         if (t0 > 0) __syncthreads();                         // the first chunk has nothing to wait for
-        stage_chunk<DM, false, (DT == 1 && !RAD), RAD>(L, X, tl, tab, W, D, a.C, a.T, t0, nt, v, a.x, a.ldx, xcol, ldxc, tid);
+        stage_chunk<DM, false, (DT == 1 && !RAD), RAD>(L, X, tl, tab, W, D, a.C, a.T, t0, nt, v, a.x, a.ldx, xcol, ldxc, tid, RAD ? a.kind + (size_t)tl.pair * a.T : nullptr);
         __syncthreads();
+        te = -1;
         for (int t = 0; t < nt; ++t) {
             const int deg = L.deg[t];
             if (deg == GT_SKIP) {                            // uniform across the workgroup
@@ -1307,9 +1392,27 @@ __global__ __launch_bounds__(256, (DT == 1 && !RAD ? 2 : 1)) void k_moments(Mome
                 cw[m] = L.cw[t][cg * 4 + m]; sw[m] = L.sw[t][cg * 4 + m];
             }
             if constexpr (RAD) {
-                const size_t kt = (size_t)tl.pair * a.T + t0 + t;
-                const int kind = __builtin_amdgcn_readfirstlane(a.kind[kt]);
-                moment_term_radial<DM>(mom, g, p, q, L, t, D, kind, a.shape[kt], cu, su, cw, sw);
+                // Row t of a product group: today's radial moments with g replaced by g prod_{h != t} k_h per entry (the other rows' values are
+                // recomputed, never divided out: a cosine factor passes through zero).  A group of one keeps g itself.
+                const int* kd = a.kind + (size_t)tl.pair * a.T + t0;
+                const double* sh = a.shape + (size_t)tl.pair * a.T + t0;
+                if (t > te) {
+                    tg = t;
+                    for (te = t; te < nt - 1 && (__builtin_amdgcn_readfirstlane(kd[te]) & MOGP_KIND_TIMES); ++te) {}
+                }
+                const int kind = __builtin_amdgcn_readfirstlane(kd[t]) & MOGP_KIND_MASK;
+                if (te > tg) {
+                    double wg[4][4];
+#pragma unroll
+                    for (int m = 0; m < 4; ++m)
+#pragma unroll
+                        for (int n = 0; n < 4; ++n) wg[m][n] = g[m][n];
+                    for (int h = tg; h <= te; ++h)
+                        if (h != t) group_factor_radial<DM, false>(wg, p, q, L, h, D, __builtin_amdgcn_readfirstlane(kd[h]) & MOGP_KIND_MASK, sh[h], rg, cg);
+                    moment_term_radial<DM>(mom, wg, p, q, L, t, D, kind, sh[t], cu, su, cw, sw);
+                } else {
+                    moment_term_radial<DM>(mom, g, p, q, L, t, D, kind, sh[t], cu, su, cw, sw);
+                }
             } else
             switch (deg) {
                 #define GT_CASE(N) case N: moment_term<DM, N, ZG, ENV>(mom, g, p, q, L, t, D, cu, su, cw, sw, zr, zc); break;

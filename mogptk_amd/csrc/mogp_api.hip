@@ -526,6 +526,17 @@ int spd_make_whole(Spd& w) {
 namespace mogp { double table_diag(const mogp_model* m, int c) {
     const int D = m->D, W = m->Wt;
     const double* tab = m->table.data() + (size_t)(c * m->C + c) * m->T * W;
+    if (m->radial && !m->hkind.empty()) {
+        // kinds are set: every profile is 1 at zero distance, so a row's diagonal value is its amplitude; a product group's is the product
+        // of its rows', and the diagonal is the sum over groups
+        const int* kd = m->hkind.data() + (size_t)(c * m->C + c) * m->T;
+        double s = 0.0, prod = 1.0;
+        for (int t = 0; t < m->T; ++t) {
+            prod *= tab[(size_t)t * W];
+            if (t == m->T - 1 || !(kd[t] & MOGP_KIND_TIMES)) { s += prod; prod = 1.0; }
+        }
+        return s;
+    }
     double s = 0.0;
     for (int t = 0; t < m->T; ++t) {
         const double* r = tab + (size_t)t * W;
@@ -534,6 +545,34 @@ namespace mogp { double table_diag(const mogp_model* m, int c) {
         s += r[0] * std::exp(-0.5 * arg) * std::cos(2.0 * M_PI * ph);
     }
     return s;
+}
+
+const char* check_kinds(const int* kind, const double* shape, int C, int D, int T, bool* any) {
+    *any = false;
+    if (!kind) return nullptr;
+    const size_t n = (size_t)C * C * T;
+    for (size_t i = 0; i < n; ++i) {
+        const int k = kind[i] & MOGP_KIND_MASK;
+        if (kind[i] < 0 || (kind[i] & ~(MOGP_KIND_MASK | MOGP_KIND_TIMES)) || k > MOGP_KIND_PERIODIC) return "unknown kind";
+        if (k == MOGP_KIND_PERIODIC && D != 1) return "the periodic profile takes one input dimension";
+        *any |= kind[i] != MOGP_KIND_GAUSS;
+    }
+    if (!*any) return nullptr;
+    if (!shape) return "shape is null";
+    for (size_t i = 0; i < n; ++i)
+        if ((kind[i] & MOGP_KIND_MASK) == MOGP_KIND_RQ && !(shape[i] > 0.0 && std::isfinite(shape[i]))) return "the rational quadratic shape must be positive";
+    // product groups: at most MOGP_GROUP_MAX rows, closed by the end of the pair's table, and the same in every channel pair
+    for (int p = 0; p < C * C; ++p) {
+        const int* kd = kind + (size_t)p * T;
+        int run = 0;
+        for (int t = 0; t < T; ++t) {
+            if ((kd[t] & MOGP_KIND_TIMES) != (kind[t] & MOGP_KIND_TIMES)) return "product groups must be the same in every channel pair";
+            run = (kd[t] & MOGP_KIND_TIMES) ? run + 1 : 0;
+            if (run >= MOGP_GROUP_MAX) return "a product group has more than 4 rows";
+        }
+        if (run) return "the last row of a pair's table multiplies with nothing";
+    }
+    return nullptr;
 }
 }  // namespace mogp
 
@@ -761,17 +800,11 @@ int mogp_model_set_kinds(mogp_model* m, int T, const int* kind, const double* sh
     if (T != m->T || T <= 0) return fail(MOGP_EINVAL, "mogp_model_set_kinds: T must be that of the last mogp_model_set_terms");
     const size_t n = (size_t)m->C * m->C * T;
     bool any = false;
-    if (kind)
-        for (size_t i = 0; i < n; ++i) {
-            if (kind[i] < MOGP_KIND_GAUSS || kind[i] > MOGP_KIND_MATERN52) return fail(MOGP_EINVAL, "mogp_model_set_kinds: unknown kind");
-            any |= kind[i] != MOGP_KIND_GAUSS;
-        }
+    if (const char* bad = check_kinds(kind, shape, m->C, m->D, T, &any)) return fail(MOGP_EINVAL, std::string("mogp_model_set_kinds: ") + bad);
     m->radial = false;
     if (!any) return MOGP_OK;                   // all Gaussian: as if never called
-    if (!shape) return fail(MOGP_EINVAL, "mogp_model_set_kinds: shape is null");
     if (m->Wt != 2 + 3 * m->D) return fail(MOGP_EINVAL, "mogp_model_set_kinds: radial profiles do not combine with enveloped term rows");
-    for (size_t i = 0; i < n; ++i)
-        if (kind[i] == MOGP_KIND_RQ && !(shape[i] > 0.0 && std::isfinite(shape[i]))) return fail(MOGP_EINVAL, "mogp_model_set_kinds: the rational quadratic shape must be positive");
+    m->hkind.assign(kind, kind + n);            // table_diag needs the groups on the host
     int rc;
     if ((rc = use_device(m->ctx))) return rc;
     if ((rc = m->d_kind.ensure(n))) return rc;
@@ -808,12 +841,8 @@ int mogp_gram_kinds(mogp_ctx* ctx, int C, int D, int T, int width, const double*
     if (!ctx || !table || !X1 || !K_out || M1 <= 0 || T <= 0 || C <= 0 || D <= 0 || D > MOGP_MAXD || (width != 2 + 3 * D && width != 2 + 5 * D))
         return fail(MOGP_EINVAL, "mogp_gram: bad argument");
     bool radial = false;
-    if (kind)
-        for (size_t i = 0; i < (size_t)C * C * T; ++i) {
-            if (kind[i] < MOGP_KIND_GAUSS || kind[i] > MOGP_KIND_MATERN52) return fail(MOGP_EINVAL, "mogp_gram_kinds: unknown kind");
-            radial |= kind[i] != MOGP_KIND_GAUSS;
-        }
-    if (radial && (!shape || width != 2 + 3 * D)) return fail(MOGP_EINVAL, "mogp_gram_kinds: kinds need shapes and rows of width 2 + 3 D");
+    if (const char* bad = check_kinds(kind, shape, C, D, T, &radial)) return fail(MOGP_EINVAL, std::string("mogp_gram_kinds: ") + bad);
+    if (radial && width != 2 + 3 * D) return fail(MOGP_EINVAL, "mogp_gram_kinds: kinds need shapes and rows of width 2 + 3 D");
     int rc;
     if ((rc = use_device(ctx))) return rc;
     const bool sym = (X2 == nullptr);

@@ -17,6 +17,22 @@
 #define MOGP_KIND_MATERN12 2   // exp(-r)
 #define MOGP_KIND_MATERN32 3   // (1 + sqrt(3) r) exp(-sqrt(3) r)
 #define MOGP_KIND_MATERN52 4   // (1 + sqrt(5) r + 5 r^2 / 3) exp(-sqrt(5) r)
+#ifndef MOGP_KIND_PERIODIC      // (the two new values are public: include/mogp_hip.h)
+#define MOGP_KIND_PERIODIC 5   // exp(V (cos theta - 1)), theta = 2 pi (M u + Psi): the phase is the profile's ARGUMENT, not a cosine factor (D = 1)
+#endif
+// Product groups: a row whose kind carries MOGP_KIND_TIMES multiplies with the next row.  A maximal run of flagged rows plus the row that
+// ends it is a group (at most MOGP_GROUP_MAX rows); the Gram is the sum over groups of the product of their rows' values.
+#ifndef MOGP_KIND_TIMES
+#define MOGP_KIND_TIMES (1 << 8)
+#endif
+#define MOGP_KIND_MASK 0xff
+#define MOGP_GROUP_MAX 4
+
+namespace mogp {
+// Shared validation of mogp_model_set_kinds / mogp_gram_kinds: profile numbers, shapes and group structure.  *any: some kind is non-zero.
+// Returns null, or what is wrong.
+const char* check_kinds(const int* kind, const double* shape, int C, int D, int T, bool* any);
+}
 
 namespace mogp {
 

@@ -320,6 +320,7 @@ struct mogp_model {
     std::vector<double> table;          // host copy [C*C*T*W]
     bool radial = false;                // mogp_model_set_kinds: some (pair, term) has a non-Gaussian profile; d_kind / d_shape [C*C*T] then hold them
     mogp::DevBuf<int> d_kind;
+    std::vector<int> hkind;             // host copy of the kinds while `radial` (table_diag: a product group's diagonal is the product of its amplitudes)
     mogp::DevBuf<double> d_shape;
     hipStream_t st = nullptr;           // critical-path stream (high priority)
     hipStream_t st2 = nullptr;          // bulk trailing updates of the fused schedule (CU-masked: everything but the reserved CUs)

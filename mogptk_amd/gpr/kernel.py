@@ -35,6 +35,35 @@ def pad_width(table, width):
     return out
 
 
+# Product groups (DESIGN 1b): a row whose kind carries KIND_TIMES multiplies with the next row; a maximal run of flagged rows plus the row that
+# ends it is a group of at most GROUP_MAX rows, and the kernel is the sum over groups of the product of their rows.  The low bits stay the profile.
+KIND_TIMES, KIND_MASK, GROUP_MAX = 1 << 8, 0xff, 4
+
+
+def group_slices(kind_row):
+    """[(first, last + 1)] of the groups of one (channel pair)'s kind row"""
+    out, t0 = [], 0
+    for t, k in enumerate(kind_row):
+        if not (int(k) & KIND_TIMES) or t == len(kind_row) - 1:
+            out.append((t0, t + 1))
+            t0 = t + 1
+    return out
+
+
+def group_diag(A, kind_row):
+    """sum over groups of the product of the rows' amplitudes: the diagonal K(x, x) of a pair whose profiles are 1 at zero distance"""
+    return float(sum(np.prod(A[a:b]) for a, b in group_slices(kind_row)))
+
+
+def group_diag_grad(A, kind_row):
+    """d group_diag / d A_t: the product of the OTHER rows of t's group (1 for a group of one)"""
+    g = np.ones(len(A))
+    for a, b in group_slices(kind_row):
+        for t in range(a, b):
+            g[t] = np.prod(np.delete(A[a:b], t - a))
+    return g
+
+
 # One evaluation asks every kernel of a composition for its term table several times (push to the device, then again at each level
 # of the chain rule -- AddKernel even asks only to learn T) while no parameter can change.  A model evaluation opens this cache.
 _TERMS_CACHE = None
@@ -169,20 +198,29 @@ class Kernel(ParameterHolder):
 
     def _spectral_diag(self, D):
         """K_diag value per channel AS THE REFERENCE RETURNS IT (constant per channel for every spectral kernel).
-        Default: the true diagonal sum_t A_cct (Delta = Psi = 0 on i == j blocks); SM overrides (its K_diag
-        differs from diag K when D > 1, reference singleoutput.py:602-605)."""
+        Default: the true diagonal sum_t A_cct (Delta = Psi = 0 on i == j blocks), over product groups the sum of their amplitudes' products;
+        SM overrides (its K_diag differs from diag K when D > 1, reference singleoutput.py:602-605)."""
         table = self._spectral_terms(D)
         C = table.shape[0]
+        kind = self._spectral_kinds(D)[0]
+        if np.any(kind & KIND_TIMES):
+            return np.array([group_diag(table[c, c, :, 0], kind[c, c]) for c in range(C)])
         return np.array([np.sum(table[c, c, :, 0]) for c in range(C)])
 
     def _spectral_diag_backward(self, gc, D):
         """accumulate d loss / d K_diag[c] = gc[c] (K_diag as `_spectral_diag` defines it) into the raw gradients.
-        Default: K_diag[c] = sum_t A_cct, so it is a table gradient on the diagonal amplitudes."""
+        Default: K_diag[c] = sum_t A_cct (over groups: the product rule), so it is a table gradient on the diagonal amplitudes."""
         table = self._spectral_terms(D)
         gt = np.zeros_like(table)
         for c in range(table.shape[0]):
             gt[c, c, :, 0] = gc[c]
-        self._spectral_backward(gt)
+        self._spectral_backward(gt * _table_diag_weights(table, self._spectral_kinds(D)[0]))
+
+    def _product_refusal(self):
+        """why this kernel cannot be a factor of a MulKernel on this path (None: it can)"""
+        if self.output_dims is not None:
+            return "a product of multi-output kernels is not on the MI355X spectral path: MulKernel multiplies single-output kernels"
+        return None
 
     def K(self, X1, X2=None):
         """Kernel matrix, reference gpr/kernel.py:138-150 (MO: :446-481).  Runs the HIP Gram builder."""
@@ -317,11 +355,72 @@ class AddKernel(Kernels):
             t0 += T
 
 
-class MulKernel(Kernels):
-    """Product kernel (reference gpr/kernel.py:248-262): not a sum of spectral terms -> out of scope."""
+def _table_diag_weights(table, kind):
+    """[C, C, T, 1] factor of the amplitude column's gradient when d/d(diagonal of pair (c, c)) is spread over its rows: 1 for plain rows, the
+    product of the group's other amplitudes inside a product group"""
+    w = np.ones(table.shape[:3] + (1,))
+    if np.any(kind & KIND_TIMES):
+        for c in range(table.shape[0]):
+            w[c, c, :, 0] = group_diag_grad(table[c, c, :, 0], kind[c, c])
+    return w
 
+
+class MulKernel(Kernels):
+    """Product of single-output kernels (reference gpr/kernel.py:248-262).  Every factor is a sum of groups of table rows (a plain kernel: groups
+    of one); the product is the sum over the Cartesian product of the factors' groups, each combination ONE group of the concatenated rows --
+    (a + b) * c = a * c + b * c.  The device multiplies the rows of a group entry by entry; at most GROUP_MAX rows per group."""
+
+    def _plan(self, D):
+        """(tables, kinds, shapes of the factors, [(factor, row)] of every produced row, flags of every produced row)"""
+        for k in self.kernels:
+            why = k._product_refusal()
+            if why is not None:
+                raise NotImplementedError(why)
+        tabs = [k._spectral_terms(D) for k in self.kernels]
+        if any(t.shape[0] != 1 or t.shape[3] != term_width(D) for t in tabs):
+            raise NotImplementedError("a product with enveloped (harmonizable) terms is not on the MI355X spectral path")
+        kinds = [k._spectral_kinds(D) for k in self.kernels]
+        combos = [[]]
+        for f, (kd, _) in enumerate(kinds):
+            groups = [[(f, t) for t in range(a, b)] for a, b in group_slices(kd[0, 0])]
+            combos = [c + g for c in combos for g in groups]
+        rows, flags = [], []
+        for c in combos:
+            if len(c) > GROUP_MAX:
+                raise NotImplementedError("a product of more than %d table rows (%s: %d) is not on the MI355X spectral path: the device multiplies "
+                                          "groups of at most %d rows" % (GROUP_MAX, self.name(), len(c), GROUP_MAX))
+            rows += c
+            flags += [KIND_TIMES] * (len(c) - 1) + [0]
+        return tabs, kinds, rows, np.array(flags, dtype=np.int32)
+
+    @cached_terms
     def _spectral_terms(self, D):
-        raise NotImplementedError("MulKernel is not on the MI355X spectral path")
+        tabs, _, rows, _ = self._plan(D)
+        return np.stack([tabs[f][0, 0, t] for f, t in rows])[None, None]
+
+    @cached_terms
+    def _spectral_kinds(self, D):
+        _, kinds, rows, flags = self._plan(D)
+        kind = np.array([int(kinds[f][0][0, 0, t]) & KIND_MASK for f, t in rows], dtype=np.int32) | flags
+        return kind[None, None], np.array([kinds[f][1][0, 0, t] for f, t in rows])[None, None]
+
+    def _spectral_backward(self, gtable):
+        """every produced row's gradient back to the factor row it is a copy of (a row used in several groups accumulates)"""
+        D = self.input_dims if self.input_dims is not None else (gtable.shape[3] - 2) // 3
+        tabs, _, rows, _ = self._plan(D)
+        gts = [np.zeros_like(t) for t in tabs]
+        for r, (f, t) in enumerate(rows):
+            gts[f][0, 0, t] += gtable[0, 0, r, :tabs[f].shape[3]]
+        for k, g in zip(self.kernels, gts):
+            k._spectral_backward(g)
+
+    def _spectral_diag(self, D):
+        return np.prod([k._spectral_diag(D) for k in self.kernels], axis=0)          # :261-262
+
+    def _spectral_diag_backward(self, gc, D):
+        kd = [k._spectral_diag(D) for k in self.kernels]
+        for f, k in enumerate(self.kernels):
+            k._spectral_diag_backward(np.asarray(gc) * np.prod([d for h, d in enumerate(kd) if h != f], axis=0), D)
 
 
 class MixtureKernel(AddKernel):

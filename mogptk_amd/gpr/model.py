@@ -10,7 +10,7 @@ from math import erf, sqrt
 
 from .config import config
 from .parameter import Parameter, ParameterHolder
-from .kernel import Kernel, terms_cache
+from .kernel import Kernel, MulKernel, terms_cache, KIND_TIMES, group_diag_grad
 from .likelihood import Likelihood, GaussianLikelihood
 from .mean import Mean
 
@@ -36,7 +36,7 @@ def _to_array(X):
 def _leaf_kernels(kernel):
     """the kernels of a composition that carry parameters of their own"""
     subs = getattr(kernel, "kernels", None)
-    if not subs:
+    if not subs or isinstance(kernel, MulKernel):          # a product is radial as a whole, whatever its factors are
         return [kernel]
     return [leaf for k in subs for leaf in _leaf_kernels(k)]
 
@@ -128,8 +128,9 @@ class Model(ParameterHolder):
         self.input_dims = X.shape[1]
         self._handle = None
         if not isinstance(self, Exact) and any(k._radial(self._D) for k in _leaf_kernels(kernel)):
-            raise NotImplementedError("%s with a non-Gaussian stationary kernel (rational quadratic, Matern, exponential) is not on the HIP path yet: "
-                                      "its per-point input gradients need the profile's derivative in a third place; gpr.Exact takes them" % self.name())
+            raise NotImplementedError("%s with a non-Gaussian stationary kernel (rational quadratic, Matern, exponential, periodic, locally periodic) "
+                                      "or a product kernel (MulKernel) is not on the HIP path yet: its per-point input gradients need the profile's "
+                                      "derivative, and a product's other factors, in a third place; gpr.Exact takes them" % self.name())
 
     def name(self):
         return self.__class__.__name__
@@ -427,7 +428,8 @@ class Exact(Model):
         radial = bool(np.any(kind))
         if radial:                              # refused before any device call
             if comm is not None and (comm.world > 1 or comm.force):
-                raise NotImplementedError("non-Gaussian stationary kernels are not carried through the sharded exact evaluation (use_distributed)")
+                raise NotImplementedError("non-Gaussian stationary kernels (periodic ones included) and product kernels are not carried through the "
+                                          "sharded exact evaluation (use_distributed)")
             if _enveloped(table, D):
                 raise NotImplementedError("a sum of enveloped (harmonizable) terms and non-Gaussian stationary kernels is not on the HIP path")
         h, table, D = self._push(table)
@@ -436,6 +438,7 @@ class Exact(Model):
         elif getattr(h, "radial_kinds", False):
             h.set_kinds(None, None)               # the kernel was replaced by an all-Gaussian one with the same number of terms
         h.radial_kinds = radial
+        h.group_kinds = kind if radial and np.any(kind & KIND_TIMES) else None      # product groups: _loss_impl's jitter term needs them
         if _enveloped(table, D):              # envelope: the diagonal varies from point to point and enters the relative jitter (:244)
             h.set_point_diag(self.kernel._point_diag(table, self.kernel._kernel_format(self.X), D))
         return h, table, D
@@ -499,8 +502,13 @@ class Exact(Model):
         if _enveloped(table, D):
             gt += jit_rel * self.kernel._point_diag_table_grad(table, self.kernel._kernel_format(self.X), D)
         else:
-            for i in range(table.shape[0]):
-                gt[i, i, :, 0] += jit_rel * counts[i]
+            kind = getattr(self._handle, "group_kinds", None)
+            if kind is not None:                    # product groups: the diagonal is sum_groups prod_t A_t, not sum_t A_t
+                for i in range(table.shape[0]):
+                    gt[i, i, :, 0] += jit_rel * counts[i] * group_diag_grad(table[i, i, :, 0], kind[i, i])
+            else:
+                for i in range(table.shape[0]):
+                    gt[i, i, :, 0] += jit_rel * counts[i]
         self.kernel._spectral_backward(-gt)                    # loss = -LML
 
         # noise: d LML / d sigma_c = 2 sigma_c (sum_{k in c} G_kk + jitter n_c/N tr G)

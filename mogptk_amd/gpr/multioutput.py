@@ -13,7 +13,7 @@ import numpy as np
 
 from .config import config
 from .parameter import Parameter, _STRUCTURE_EPOCH
-from .kernel import Kernel, MultiOutputKernel, term_width, cached_terms
+from .kernel import Kernel, MultiOutputKernel, term_width, cached_terms, KIND_TIMES, group_slices
 
 PI = np.pi
 
@@ -40,26 +40,40 @@ class IndependentMultiOutputKernel(MultiOutputKernel):
     def name(self):
         return "%s[%s]" % (self.__class__.__name__, ",".join(k.name() for k in self.kernels))
 
+    def _layout(self, D):
+        """(first row of every channel's terms, T, product flags [T] of every pair).  Without product groups the channels' terms share the rows
+        0 .. T_c - 1.  The device wants the SAME groups in every channel pair: where the channels' groups line up they still share rows;
+        otherwise each channel gets rows of its own (the other channels' amplitudes there are zero, which makes those groups zero)."""
+        flags = [k._spectral_kinds(D)[0][0, 0] & KIND_TIMES for k in self.kernels]
+        T = max(len(f) for f in flags)
+        union = np.zeros(T, dtype=np.int32)
+        for f in flags:
+            union[:len(f)] |= f
+        if all(np.array_equal(f, union[:len(f)]) for f in flags):
+            return [0] * len(flags), T, union
+        starts = np.concatenate([[0], np.cumsum([len(f) for f in flags])])
+        return [int(v) for v in starts[:-1]], int(starts[-1]), np.concatenate(flags).astype(np.int32)
+
     @cached_terms
     def _spectral_terms(self, D):
         subs = [k._spectral_terms(D)[0, 0] for k in self.kernels]      # each (T_c, W)
-        T = max(s.shape[0] for s in subs)
+        starts, T, _ = self._layout(D)
         C = self.output_dims
         table = np.zeros((C, C, T, term_width(D)))                       # A = 0 off the block diagonal (:34)
         for c, s in enumerate(subs):
-            table[c, c, :s.shape[0]] = s
+            table[c, c, starts[c]:starts[c] + s.shape[0]] = s
         return table
 
     @cached_terms
     def _spectral_kinds(self, D):
         subs = [k._spectral_kinds(D) for k in self.kernels]            # on the block diagonal, as the tables; padding rows are Gaussian
-        T = max(kd.shape[2] for kd, _ in subs)
+        starts, T, flags = self._layout(D)
         C = self.output_dims
         kind, shape = np.zeros((C, C, T), dtype=np.int32), np.zeros((C, C, T))
         for c, (kd, sh) in enumerate(subs):
-            kind[c, c, :kd.shape[2]] = kd[0, 0]
-            shape[c, c, :sh.shape[2]] = sh[0, 0]
-        return kind, shape
+            kind[c, c, starts[c]:starts[c] + kd.shape[2]] = kd[0, 0] & ~KIND_TIMES
+            shape[c, c, starts[c]:starts[c] + sh.shape[2]] = sh[0, 0]
+        return kind | flags[None, None, :], shape
 
     def _spectral_diag(self, D):
         return np.array([k._spectral_diag(D)[0] for k in self.kernels])   # reference :36-39
@@ -70,9 +84,10 @@ class IndependentMultiOutputKernel(MultiOutputKernel):
 
     def _spectral_backward(self, gtable):
         D = (gtable.shape[3] - 2) // 3
+        starts = self._layout(D)[0]
         for c, k in enumerate(self.kernels):
             T = k._spectral_terms(D).shape[2]
-            k._spectral_backward(gtable[c:c + 1, c:c + 1, :T])
+            k._spectral_backward(gtable[c:c + 1, c:c + 1, starts[c]:starts[c] + T])
 
 
 class MultiOutputSpectralMixtureKernel(MultiOutputKernel):
@@ -434,6 +449,13 @@ class LinearModelOfCoregionalizationKernel(MultiOutputKernel):
         w = self.weight()                                                   # (C,Q,Rq)
         return np.einsum("iqr,jqr->ijq", w, w)                               # B_q[i,j]  (:493)
 
+    def _lead(self, k, D):
+        """rows of base kernel k that take the coregionalization factor B_q: every row, but only the FIRST of a product group (B once per group)"""
+        kd = k._spectral_kinds(D)[0][0, 0]
+        lead = np.zeros(len(kd), dtype=bool)
+        lead[[a for a, _ in group_slices(kd)]] = True
+        return lead
+
     @cached_terms
     def _spectral_terms(self, D):
         B = self._coreg()
@@ -442,7 +464,8 @@ class LinearModelOfCoregionalizationKernel(MultiOutputKernel):
         for q, k in enumerate(self.kernels):
             sub = k._spectral_terms(D)[0, 0]                                 # (T_q, W): Psi = Delta = 0 for single-output kernels
             part = np.broadcast_to(sub, (C, C) + sub.shape).copy()
-            part[..., 0] = B[:, :, q, None] * sub[None, None, :, 0]
+            lead = self._lead(k, D)
+            part[..., lead, 0] = B[:, :, q, None] * sub[None, None, lead, 0]
             parts.append(part)
         return np.concatenate(parts, axis=2)
 
@@ -485,9 +508,10 @@ class LinearModelOfCoregionalizationKernel(MultiOutputKernel):
             sub = k._spectral_terms(D)[0, 0]
             T = sub.shape[0]
             g = gtable[:, :, t0:t0 + T, :]                                   # zero above the diagonal, double count included
-            gB[:, :, q] = np.sum(g[..., 0] * sub[None, None, :, 0], axis=2)
+            lead = self._lead(k, D)
+            gB[:, :, q] = np.sum(g[..., lead, 0] * sub[None, None, lead, 0], axis=2)
             gsub = np.sum(g, axis=(0, 1))                                    # V, M columns: the same base value in every pair
-            gsub[:, 0] = np.einsum("ijt,ij->t", g[..., 0], B[:, :, q])
+            gsub[lead, 0] = np.einsum("ijt,ij->t", g[..., lead, 0], B[:, :, q])
             k._spectral_backward(gsub[None, None])
             t0 += T
         self._weight_backward(gB)

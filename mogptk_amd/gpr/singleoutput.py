@@ -9,7 +9,7 @@ import numpy as np
 
 from .config import config
 from .parameter import Parameter
-from .kernel import Kernel, term_width, cached_terms
+from .kernel import Kernel, term_width, cached_terms, KIND_TIMES
 from .multioutput import _accumulate
 
 FOUR_PI2 = 4.0 * np.pi ** 2
@@ -96,7 +96,7 @@ class SpectralKernel(Kernel):
 
 
 # radial profile of a term (include/mogp_hip.h: mogp_model_set_kinds)
-KIND_GAUSS, KIND_RQ, KIND_MATERN12, KIND_MATERN32, KIND_MATERN52 = 0, 1, 2, 3, 4
+KIND_GAUSS, KIND_RQ, KIND_MATERN12, KIND_MATERN32, KIND_MATERN52, KIND_PERIODIC = 0, 1, 2, 3, 4, 5
 
 
 class _RadialKernel(Kernel):
@@ -207,3 +207,136 @@ class ExponentialKernel(_RadialKernel):
         _check_one_dim(input_dims, "ExponentialKernel", "sum_d |tau_d| / l_d")
         self.magnitude = Parameter(1.0, lower=config.positive_minimum)
         self.lengthscale = Parameter(np.ones(input_dims), lower=config.positive_minimum)
+
+
+class _MagnitudeKernel(Kernel):
+    """shared by the kernels below: K_diag = magnitude (reference :64-67, :376-379, :433-436, :470-473)"""
+
+    def _check_dims(self, D):
+        if D != self.input_dims:
+            raise ValueError("X must have %d input dimensions" % self.input_dims)
+
+    def _spectral_diag(self, D):
+        return np.array([float(self.magnitude())])
+
+    def _spectral_diag_backward(self, gc, D):
+        _accumulate(self.magnitude, np.reshape(float(gc[0]), self.magnitude.shape))
+
+
+class ConstantKernel(_MagnitudeKernel):
+    """K = mag (reference :37-67): a Gaussian term with V = M = 0, so it runs wherever term tables run; times another kernel it scales it."""
+
+    def __init__(self, input_dims=1, active_dims=None):
+        super().__init__(input_dims, active_dims)
+        self.magnitude = Parameter(1.0, lower=config.positive_minimum)
+
+    @cached_terms
+    def _spectral_terms(self, D):
+        self._check_dims(D)
+        table = np.zeros((1, 1, 1, term_width(D)))
+        table[0, 0, 0, 0] = self.magnitude()
+        return table
+
+    def _spectral_backward(self, gtable):
+        _accumulate(self.magnitude, np.reshape(gtable[0, 0, 0, 0], self.magnitude.shape))
+
+
+class CosineKernel(_MagnitudeKernel):
+    """K = mag cos(2 pi sum_d tau_d / l_d) (reference :438-473): a Gaussian term with V = 0 and M_d = 1 / l_d -- an ordinary table row."""
+
+    def __init__(self, input_dims=1, active_dims=None):
+        super().__init__(input_dims, active_dims)
+        self.magnitude = Parameter(1.0, lower=config.positive_minimum)
+        self.lengthscale = Parameter(np.ones(input_dims), lower=config.positive_minimum)
+
+    @cached_terms
+    def _spectral_terms(self, D):
+        self._check_dims(D)
+        table = np.zeros((1, 1, 1, term_width(D)))
+        table[0, 0, 0, 0] = self.magnitude()
+        table[0, 0, 0, 2 + D:2 + 2 * D] = 1.0 / np.asarray(self.lengthscale(), dtype=np.float64)
+        return table
+
+    def _spectral_backward(self, gtable):
+        D = self.input_dims
+        g = gtable[0, 0, 0]
+        _accumulate(self.magnitude, np.reshape(g[0], self.magnitude.shape))
+        l = np.asarray(self.lengthscale(), dtype=np.float64)
+        _accumulate(self.lengthscale, -g[2 + D:2 + 2 * D] / np.square(l))         # d M_d / d l_d
+
+
+def _check_periodic(order, input_dims, name):
+    _check_order(order, name)
+    if input_dims != 1:
+        raise NotImplementedError("%s with input_dims > 1 is not on the HIP path: the reference sums sin^2(pi tau_d / p_d) / l_d^2 over the "
+                                  "dimensions, which is not a function of the one phase a term of the device's table carries" % name)
+
+
+class PeriodicKernel(_MagnitudeKernel):
+    """K = mag exp(-2 sin^2(pi tau / p) / l^2) = mag exp(V (cos theta - 1)), V = 1 / l^2, theta = 2 pi tau / p (reference :325-379): one row of
+    kind 5, whose phase (M = 1 / p) is the ARGUMENT of the profile.  One input dimension; order 0 or -1 (the lengthscale's shape)."""
+
+    def __init__(self, order=0, input_dims=1, active_dims=None):
+        super().__init__(input_dims, active_dims)
+        _check_periodic(order, input_dims, "PeriodicKernel")
+        self.order = order
+        self.magnitude = Parameter(1.0, lower=config.positive_minimum)
+        self.period = Parameter(np.ones(input_dims), lower=config.positive_minimum)
+        self.lengthscale = Parameter(np.ones(input_dims) if -1 < order else 1.0, lower=config.positive_minimum)
+
+    def _l(self):
+        return float(np.asarray(self.lengthscale(), dtype=np.float64).reshape(-1)[0])
+
+    @cached_terms
+    def _spectral_terms(self, D):
+        self._check_dims(D)
+        table = np.zeros((1, 1, 1, term_width(D)))
+        table[0, 0, 0, 0] = self.magnitude()
+        table[0, 0, 0, 2] = 1.0 / self._l() ** 2
+        table[0, 0, 0, 3] = 1.0 / float(self.period()[0])
+        return table
+
+    @cached_terms
+    def _spectral_kinds(self, D):
+        return np.full((1, 1, 1), KIND_PERIODIC, dtype=np.int32), np.zeros((1, 1, 1))
+
+    def _periodic_backward(self, g, gV):
+        """g: the periodic row's table gradient; gV: d / d V summed over every row that carries V = 1 / l^2"""
+        _accumulate(self.magnitude, np.reshape(g[0], self.magnitude.shape))
+        _accumulate(self.period, np.reshape(-g[3] / float(self.period()[0]) ** 2, self.period.shape))
+        _accumulate(self.lengthscale, np.reshape(-2.0 * gV / self._l() ** 3, self.lengthscale.shape))
+
+    def _spectral_backward(self, gtable):
+        g = gtable[0, 0, 0]
+        self._periodic_backward(g, g[2])
+
+
+class LocallyPeriodicKernel(PeriodicKernel):
+    """K = mag exp(-2 sin^2(pi tau / p) / l^2) exp(-tau^2 / (2 l^2)) (reference :381-436): ONE product group of a periodic row (the magnitude on
+    it) and a Gaussian row of unit amplitude; both carry V = 1 / l^2."""
+
+    def __init__(self, order=0, input_dims=1, active_dims=None):
+        Kernel.__init__(self, input_dims, active_dims)
+        _check_periodic(order, input_dims, "LocallyPeriodicKernel")
+        self.order = order
+        self.magnitude = Parameter(1.0, lower=config.positive_minimum)
+        self.period = Parameter(np.ones(input_dims), lower=config.positive_minimum)
+        self.lengthscale = Parameter(np.ones(input_dims) if -1 < order else 1.0, lower=config.positive_minimum)
+
+    @cached_terms
+    def _spectral_terms(self, D):
+        self._check_dims(D)
+        table = np.zeros((1, 1, 2, term_width(D)))
+        table[0, 0, 0, 0] = self.magnitude()
+        table[0, 0, :, 2] = 1.0 / self._l() ** 2
+        table[0, 0, 0, 3] = 1.0 / float(self.period()[0])
+        table[0, 0, 1, 0] = 1.0
+        return table
+
+    @cached_terms
+    def _spectral_kinds(self, D):
+        return np.array([[[KIND_PERIODIC | KIND_TIMES, KIND_GAUSS]]], dtype=np.int32), np.zeros((1, 1, 2))
+
+    def _spectral_backward(self, gtable):
+        g = gtable[0, 0]
+        self._periodic_backward(g[0], g[0, 2] + g[1, 2])
