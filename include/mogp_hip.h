@@ -118,8 +118,21 @@ int  mogp_gram_ex(mogp_ctx* ctx, int C, int D, int T, int width, const double* t
  * of its rows' values A phi cos, and K the sum over groups (a plain row is a group of one).  At most 4 rows per group, the last row of a
  * table unflagged, the same flags in every channel pair; anything else is MOGP_EINVAL.  A row's moments are then those of the row alone
  * with the adjoint weighted, entry by entry, by the product of the group's OTHER rows, so dK/d(row) keeps its formulas.  K(x, x) of a
- * group is the product of its amplitudes (the relative jitter uses it).  A flag alone (all profiles Gaussian) is a non-zero kind. */
+ * group is the product of its amplitudes (the relative jitter uses it).  A flag alone (all profiles Gaussian) is a non-zero kind.
+ *   kind 6  sinc(r) = sin(pi r) / (pi r)   (reference SincKernel.K :503-513 with V = bandwidth^2, M = frequency): an ordinary profile with
+ *           psi = (sinc(r) - cos(pi r)) / r^2; both by their series in pi^2 s below pi^2 s = 1 (phi(0) = 1, psi(0) = pi^2 / 3).  D = 1 only.
+ *   kind 7  the dot product row  (A sum_d x_a,d x_b,d + c)^n   (reference LinearKernel.K :91-96, PolynomialKernel.K :128-133): A the row's
+ *           amplitude, the bias c >= 0 in the row's Psi slot, n = shape an integer 1 .. 8; V, M and Delta of the row are not read and no
+ *           cosine stands beside it.  The row is NOT stationary and its value is not A times something: a zero amplitude does not silence
+ *           its group (the value is c^n), inside a group it weighs the other rows' adjoints with its full value, and its own moments are
+ *           m0 = sum g n b^(n-1) <x_a, x_b> = d/dA and m1_0 = sum g n b^(n-1) = d/dc, b = A <x_a, x_b> + c (the other slots 0; both slots
+ *           are even in tau, so the diagonal channel blocks keep them).  K(x, x) = (A |x|^2 + c)^n follows the point: as with enveloped
+ *           rows, supply mogp_model_set_point_diag (without it the library forms the diagonal from the table and the kinds itself) and
+ *           pass kss_diag to mogp_exact_predict per TEST POINT.  A group's diagonal is the product of its rows' diagonals at that point. */
 #define MOGP_KIND_PERIODIC 5
+#define MOGP_KIND_SINC 6
+#define MOGP_KIND_DOT 7
+#define MOGP_DOT_DEGREE_MAX 8
 #define MOGP_KIND_TIMES (1 << 8)
 int  mogp_model_set_kinds(mogp_model* m, int T, const int* kind, const double* shape);
 /* mogp_gram_ex with kinds (NULL: mogp_gram_ex itself): replaces Kernel.K of the kernels above, and of their sums, IndependentMultiOutputKernel

@@ -258,6 +258,8 @@ def _convert_kernel(bag):
         return cls(alpha=float(st.get("alpha", 1.0)), order=st.get("order", 0), input_dims=idims)
     if name == "MaternKernel":
         return cls(nu=float(st.get("nu", 0.5)), input_dims=idims)
+    if name == "PolynomialKernel":
+        return cls(degree=st.get("degree"), input_dims=idims)
     try:
         return cls(input_dims=idims)                       # the other single-output kernels: Spectral, Exponential, ...
     except TypeError:
@@ -472,6 +474,7 @@ _REF_KERNEL_MODULE = {
     "SpectralKernel": "singleoutput", "SpectralMixtureKernel": "singleoutput", "SquaredExponentialKernel": "singleoutput",
     "RationalQuadraticKernel": "singleoutput", "MaternKernel": "singleoutput", "ExponentialKernel": "singleoutput",
     "ConstantKernel": "singleoutput", "CosineKernel": "singleoutput", "PeriodicKernel": "singleoutput", "LocallyPeriodicKernel": "singleoutput",
+    "LinearKernel": "singleoutput", "PolynomialKernel": "singleoutput", "SincKernel": "singleoutput",
     "IndependentMultiOutputKernel": "multioutput", "MultiOutputSpectralMixtureKernel": "multioutput", "CrossSpectralKernel": "multioutput",
     "LinearModelOfCoregionalizationKernel": "multioutput", "GaussianConvolutionProcessKernel": "multioutput",
     "MultiOutputHarmonizableSpectralKernel": "multioutput", "MultiOutputSpectralKernel": "multioutput",
@@ -536,7 +539,7 @@ class _Exporter:
         own = {"input_dims": None if name == "IndependentMultiOutputKernel" else k.input_dims, "_active_dims": None, "output_dims": k.output_dims}
         if "twopi" in k.__dict__:
             own["twopi"] = np.float64(k.twopi)
-        for attr in ("alpha", "nu", "order"):                     # plain attributes of the stationary kernels, in the reference constructors' order
+        for attr in ("alpha", "nu", "order", "degree"):                     # plain attributes of the stationary kernels, in the reference constructors' order
             if attr in k.__dict__:
                 own[attr] = k.__dict__[attr]
         mods = []

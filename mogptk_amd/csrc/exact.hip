@@ -152,6 +152,9 @@ int exact_begin(mogp_model* m, const double* noise_var, const double* data_var, 
     if (!m->point_diag.empty()) {       // non-stationary kernels: the caller supplied K_diag per point (mogp_model_set_point_diag)
         for (int c = 0; c < C; ++c)
             for (int k = m->sx.off[c]; k < m->sx.off[c + 1]; ++k) dsum += m->point_diag[k] + noise_var[c];
+    } else if (m->radial && m->point_kinds) {      // dot-product rows and no diagonal from the caller: from the table and the kinds, point by point
+        dsum = table_diag_points(m, m->sx);
+        for (int c = 0; c < C; ++c) dsum += (double)(m->sx.off[c + 1] - m->sx.off[c]) * noise_var[c];
     } else
     for (int c = 0; c < C; ++c) dsum += (double)(m->sx.off[c + 1] - m->sx.off[c]) * (table_diag(m, c) + noise_var[c]);
     if (data_var) {
@@ -475,7 +478,7 @@ int test_side(mogp_model* m, int64_t S, const double* Xs, const double* kss_diag
     if ((rc = m->d_kdiag.ensure(Spad))) return rc;
     if ((rc = m->d_ptiles.ensure(std::max<size_t>(pt.size(), 1)))) return rc;
     std::vector<double> kd(Spad, 0.0);
-    const bool per_point = m->Wt > 2 + 3 * D;          // terms with an envelope: kss_diag holds one value per test point (caller order)
+    const bool per_point = m->Wt > 2 + 3 * D || (m->radial && m->point_kinds);      // terms with an envelope, dot-product rows: kss_diag holds one value per test point (caller order)
     for (int c = 0; c < C; ++c)
         for (int pos = ss.off[c]; pos < ss.off[c + 1]; ++pos) kd[pos] = per_point ? kss_diag[ss.perm[pos]] : kss_diag[c];
     HIP_TRY(hipMemcpyAsync(m->d_xs.p, ss.xs.data(), (size_t)D * Spad * sizeof(double), hipMemcpyHostToDevice, st));

@@ -234,16 +234,20 @@ __device__ __forceinline__ void stage_item_compute(TileLds<DM>& L, const StageIt
     const double* row = tab + (size_t)(t0 + t) * W;
     const double A = row[0];
     if constexpr (RAD) {
-        const bool per = (kinds[t0 + t] & MOGP_KIND_MASK) == MOGP_KIND_PERIODIC;
-        const int deg = (AMP && A == 0.0) ? GT_SKIP : GT_GENERAL;
+        const int kd = kinds[t0 + t] & MOGP_KIND_MASK;
+        const bool per = kd == MOGP_KIND_PERIODIC, dot = kd == MOGP_KIND_DOT;
+        const int deg = (AMP && A == 0.0 && !dot) ? GT_SKIP : GT_GENERAL;      // (a dot-product row of zero amplitude is c^n, not zero)
         if (pnt == 0 && which == 0) {
             L.deg[t] = deg; L.A[t] = A;
             for (int d = 0; d < D; ++d) {
                 L.V[t][d] = row[2 + d]; L.M[t][d] = row[2 + D + d];
                 L.s[t][d] = (X.cr[d] - X.cc[d]) + row[2 + 2 * D + d];
+                L.Kp[t][d] = X.cr[d]; L.L[t][d] = X.cc[d];      // the tile centres: a dot-product row needs the inputs themselves (dot_row_base)
             }
+            L.e[t][0] = row[1];                                 // its bias rides in the Psi slot
         }
         if (deg == GT_SKIP) return;
+        if (dot) return;                                        // no phase factors: the staged slots of the row are not read
         const double f = (AMP && !per) ? A : 1.0;
         if (which == 0) { L.cu[t][pnt] = f * I.cs; L.su[t][pnt] = f * I.sn; }
         else { L.cw[t][pnt] = I.cs; L.sw[t][pnt] = I.sn; }
@@ -406,6 +410,41 @@ __device__ __forceinline__ void radial_profile(int kind, double shape, double s,
             phi = fma(r, r, 3.0 * (1.0 + r)) * (e * (1.0 / 3.0));
             if (PSI) psi = (5.0 / 3.0) * fma(r, e, e);
         } break;
+        case MOGP_KIND_SINC: {
+            // phi = sin(pi r) / (pi r), psi = (phi - cos(pi r)) / r^2; both are even power series in x = pi^2 s with removable singularities at 0:
+            //   phi = sum_k (-x)^k / (2k + 1)!,   psi = pi^2 sum_k (-x)^k (2k + 2) / (2k + 3)!   (phi(0) = 1, psi(0) = pi^2 / 3).
+            // Below x = 1 (r < 0.32) the series: the first neglected terms are x^9 / 19! < 9e-18 (beside 1) and 18 x^8 / 19! < 1.5e-16 (beside 1/3); above it the
+            // closed forms, where the difference phi - cos has lost at most log2(3 / x) < 2 bits.  No 0 / 0 is ever formed.
+            const double x = 9.869604401089358 * s;
+            if (x <= 1.0) {
+                double a = 2.8114572543455206e-15;                       // 1 / 17!
+                a = fma(-x, a, 7.6471637318198164e-13);                 // 1 / 15!
+                a = fma(-x, a, 1.6059043836821613e-10);                 // 1 / 13!
+                a = fma(-x, a, 2.505210838544172e-08);                  // 1 / 11!
+                a = fma(-x, a, 2.7557319223985893e-06);                 // 1 / 9!
+                a = fma(-x, a, 1.984126984126984e-04);                  // 1 / 7!
+                a = fma(-x, a, 8.333333333333333e-03);                  // 1 / 5!
+                a = fma(-x, a, 1.6666666666666666e-01);                 // 1 / 3!
+                phi = fma(-x, a, 1.0);
+                if (PSI) {
+                    double b = 4.4983316069528329e-14;                   // 16 / 17!
+                    b = fma(-x, b, 1.0706029224547743e-11);             // 14 / 15!
+                    b = fma(-x, b, 1.9270852604185937e-09);             // 12 / 13!
+                    b = fma(-x, b, 2.505210838544172e-07);              // 10 / 11!
+                    b = fma(-x, b, 2.2045855379188714e-05);             // 8 / 9!
+                    b = fma(-x, b, 1.1904761904761906e-03);             // 6 / 7!
+                    b = fma(-x, b, 3.3333333333333333e-02);             // 4 / 5!
+                    b = fma(-x, b, 3.3333333333333331e-01);             // 2 / 3!
+                    psi = 9.869604401089358 * b;
+                }
+            } else {
+                const double r = sqrt(s);
+                double sn, cs;
+                sincospi(r, &sn, &cs);
+                phi = sn / (3.14159265358979323846 * r);
+                if (PSI) psi = (phi - cs) / s;
+            }
+        } break;
         default:
             phi = exp(-0.5 * s);
             if (PSI) psi = phi;
@@ -427,6 +466,24 @@ __device__ __forceinline__ double radial_s(const double (&p)[DM], const double (
 // s = 2 V (1 - cos theta), and no cosine factor beside it.  `cc` = cos theta from the staged UNIT phase factors; the amplitude is L.A[t].
 __device__ __forceinline__ double periodic_s(double V, double cc) { return 2.0 * V * (1.0 - cc); }
 
+// The dot-product row (MOGP_KIND_DOT): k = b^n, b = A <x_a, x_b> + c -- LinearKernel (n = 1) and PolynomialKernel of the reference.  Not a
+// profile of s and not stationary: it needs the inputs themselves, which a thread holds relative to the tile centres (p = x_a - c_r,
+// q = x_b - c_c); the staging keeps the centres in L.Kp / L.L and the bias c (the row's Psi slot) in L.e[t][0], none of which a radial
+// launch uses otherwise.  x = p + c_r is the input to half an ulp.
+template <int DM>
+__device__ __forceinline__ double dot_row_inner(const double (&p)[DM], const double (&q)[DM], const TileLds<DM>& L, int t, int D) {
+    double ip = (p[0] + L.Kp[t][0]) * (q[0] + L.L[t][0]);
+    for (int d = 1; d < D; ++d) ip = fma(p[d] + L.Kp[t][d], q[d] + L.L[t][d], ip);
+    return ip;
+}
+// b^n by repeated multiplication (n = 1 .. MOGP_DOT_DEGREE_MAX, uniform over the tile)
+__device__ __forceinline__ double dot_row_power(double b, int n) {
+    double k = b;
+    for (int i = 1; i < n; ++i) k *= b;
+    return k;
+}
+__device__ __forceinline__ int dot_row_degree(double shape) { return __builtin_amdgcn_readfirstlane((int)shape); }
+
 // Chunks of a radial launch end at a group end (a group never straddles two chunks): at most MOGP_TC rows from t0 on, shortened while the
 // last one still multiplies with its successor.  `kinds`: one pair's kind row -- the flags are the same in every pair.
 __device__ __forceinline__ int radial_chunk(const int* kinds, int T, int t0) {
@@ -440,6 +497,14 @@ __device__ __forceinline__ void gram_term_radial(double (&acc)[4][4], const doub
                                                  int D, int kind, double shape, const double (&cu)[4], const double (&su)[4],
                                                  const double (&cw)[4], const double (&sw)[4]) {
     const bool per = kind == MOGP_KIND_PERIODIC;
+    if (kind == MOGP_KIND_DOT) {                            // the row's value is the whole entry: no amplitude in front, no cosine beside it
+        const int n = dot_row_degree(shape);
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int nn = 0; nn < 4; ++nn) acc[m][nn] += dot_row_power(fma(L.A[t], dot_row_inner<DM>(p[m], q[nn], L, t, D), L.e[t][0]), n);
+        return;
+    }
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
         __builtin_amdgcn_sched_barrier(0);                  // one row of four library exps at a time: interleaving all sixteen is what spills
@@ -454,12 +519,21 @@ __device__ __forceinline__ void gram_term_radial(double (&acc)[4][4], const doub
 }
 
 // One row of a product group: prod *= k_t per entry, k_t = A phi cos theta (the amplitude rides in the staged row factors when AMPF, else
-// it is L.A[t]: the moment pass stages unit amplitudes).
+// it is L.A[t]: the moment pass stages unit amplitudes) -- for a row whose value is A times something, the moment pass leaves the row's OWN
+// amplitude to the host and this function supplies the other rows'.  A dot-product row is not of that form and always brings its full value.
 template <int DM, bool AMPF>
 __device__ __forceinline__ void group_factor_radial(double (&prod)[4][4], const double (&p)[4][DM], const double (&q)[4][DM],
                                                     const TileLds<DM>& L, int t, int D, int kind, double shape, int rg, int cg) {
     const bool per = kind == MOGP_KIND_PERIODIC;
     const double A = L.A[t];
+    if (kind == MOGP_KIND_DOT) {                            // the full value b^n with or without AMPF: the row's amplitude is inside the power, and
+        const int n = dot_row_degree(shape);                // the host's chain rule never multiplies a dot-product row's moments by it
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int nn = 0; nn < 4; ++nn) prod[m][nn] *= dot_row_power(fma(A, dot_row_inner<DM>(p[m], q[nn], L, t, D), L.e[t][0]), n);
+        return;
+    }
     double cw[4], sw[4];
 #pragma unroll
     for (int n = 0; n < 4; ++n) { cw[n] = L.cw[t][cg * 4 + n]; sw[n] = L.sw[t][cg * 4 + n]; }
@@ -1254,6 +1328,22 @@ __device__ __forceinline__ void moment_term_radial(double* mom, const double (&g
     const double* V = L.V[t];
     const double* s = L.s[t];
     const bool per = kind == MOGP_KIND_PERIODIC;             // (D = 1: the moment slots are 0, 1, 2, 3, 4)
+    if (kind == MOGP_KIND_DOT) {
+        // k = b^n, b = A <x_a, x_b> + c:  m0 = sum g n b^(n-1) <x_a, x_b> = d/dA,  m1_0 = sum g n b^(n-1) = d/dc (slots 0 and 2: both even in tau,
+        // k_moment_reduce keeps them on diagonal channel blocks); the other slots stay 0
+        const int n = dot_row_degree(shape);
+        const double A = L.A[t], c = L.e[t][0];
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int nn = 0; nn < 4; ++nn) {
+                const double ip = dot_row_inner<DM>(p[m], q[nn], L, t, D);
+                const double w = g[m][nn] * ((double)n * (n > 1 ? dot_row_power(fma(A, ip, c), n - 1) : 1.0));
+                mom[0] = fma(w, ip, mom[0]);
+                mom[2] += w;
+            }
+        return;
+    }
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
 #pragma unroll
@@ -1319,6 +1409,8 @@ __global__ __launch_bounds__(256, (DT == 1 && !RAD ? 2 : 1)) void k_moments(Mome
     double* outp = a.partial + (size_t)blockIdx.x * a.T * W;
     bool any = false;
     for (int t = 0; t < a.T; ++t) any |= (tab[(size_t)t * W] != 0.0);
+    if constexpr (RAD)                                       // (a dot-product row of zero amplitude is c^n)
+        for (int t = 0; t < a.T; ++t) any |= (a.kind[(size_t)tl.pair * a.T + t] & MOGP_KIND_MASK) == MOGP_KIND_DOT;
     if (!any) {
         for (int idx = tid; idx < a.T * W; idx += 256) outp[idx] = 0.0;
         return;

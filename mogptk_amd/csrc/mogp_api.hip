@@ -553,14 +553,18 @@ const char* check_kinds(const int* kind, const double* shape, int C, int D, int 
     const size_t n = (size_t)C * C * T;
     for (size_t i = 0; i < n; ++i) {
         const int k = kind[i] & MOGP_KIND_MASK;
-        if (kind[i] < 0 || (kind[i] & ~(MOGP_KIND_MASK | MOGP_KIND_TIMES)) || k > MOGP_KIND_PERIODIC) return "unknown kind";
+        if (kind[i] < 0 || (kind[i] & ~(MOGP_KIND_MASK | MOGP_KIND_TIMES)) || k > MOGP_KIND_DOT) return "unknown kind";
         if (k == MOGP_KIND_PERIODIC && D != 1) return "the periodic profile takes one input dimension";
+        if (k == MOGP_KIND_SINC && D != 1) return "the sinc profile takes one input dimension";
         *any |= kind[i] != MOGP_KIND_GAUSS;
     }
     if (!*any) return nullptr;
     if (!shape) return "shape is null";
-    for (size_t i = 0; i < n; ++i)
+    for (size_t i = 0; i < n; ++i) {
         if ((kind[i] & MOGP_KIND_MASK) == MOGP_KIND_RQ && !(shape[i] > 0.0 && std::isfinite(shape[i]))) return "the rational quadratic shape must be positive";
+        if ((kind[i] & MOGP_KIND_MASK) == MOGP_KIND_DOT && !(shape[i] >= 1.0 && shape[i] <= (double)MOGP_DOT_DEGREE_MAX && shape[i] == std::floor(shape[i])))
+            return "the degree of a dot-product row must be an integer from 1 to 8";
+    }
     // product groups: at most MOGP_GROUP_MAX rows, closed by the end of the pair's table, and the same in every channel pair
     for (int p = 0; p < C * C; ++p) {
         const int* kd = kind + (size_t)p * T;
@@ -581,6 +585,31 @@ const char* check_kinds(const int* kind, const double* shape, int C, int D, int 
 namespace mogp { double table_diag_points(const mogp_model* m, const SortedX& pts) {
     const int D = m->D, W = m->Wt, C = m->C;
     double s = 0.0;
+    if (W == 2 + 3 * D && m->radial && m->point_kinds) {
+        // dot-product rows: a row's diagonal value at the point x is (A |x|^2 + c)^n (its amplitude for every other row: the profiles are 1 at zero
+        // distance), a group's the product of its rows', the diagonal the sum over groups
+        for (int c = 0; c < C; ++c) {
+            const double* tab = m->table.data() + (size_t)(c * C + c) * m->T * W;
+            const int* kd = m->hkind.data() + (size_t)(c * C + c) * m->T;
+            const double* sh = m->hshape.data() + (size_t)(c * C + c) * m->T;
+            for (int pos = pts.off[c]; pos < pts.off[c + 1]; ++pos) {
+                double x2 = 0.0, prod = 1.0;
+                for (int d = 0; d < D; ++d) { const double x = pts.xs[(size_t)d * pts.Mpad + pos]; x2 += x * x; }
+                for (int t = 0; t < m->T; ++t) {
+                    const double* r = tab + (size_t)t * W;
+                    double v = r[0];
+                    if ((kd[t] & MOGP_KIND_MASK) == MOGP_KIND_DOT) {
+                        const double b = r[0] * x2 + r[1];
+                        v = b;
+                        for (int k = 1; k < (int)sh[t]; ++k) v *= b;
+                    }
+                    prod *= v;
+                    if (t == m->T - 1 || !(kd[t] & MOGP_KIND_TIMES)) { s += prod; prod = 1.0; }
+                }
+            }
+        }
+        return s;
+    }
     if (W == 2 + 3 * D) {
         for (int c = 0; c < C; ++c) s += (double)(pts.off[c + 1] - pts.off[c]) * table_diag(m, c);
         return s;
@@ -779,7 +808,7 @@ int mogp_model_set_terms_ex(mogp_model* m, int T, int width, const double* table
     const size_t n = (size_t)m->C * m->C * T * W;
     for (size_t i = 0; i < n; ++i)
         if (!std::isfinite(table[i])) return fail(MOGP_ENONFINITE, "spectral term table has non-finite entries (kernel parameters diverged)");
-    if (T != m->T) m->radial = false;           // kinds belong to a table shape (mogp_model_set_kinds)
+    if (T != m->T) m->radial = m->point_kinds = false;           // kinds belong to a table shape (mogp_model_set_kinds)
     m->T = T;
     m->Wt = W;
     if (m->tw) m->tw->pred_valid = false;       // mogp_sparse_predict_cov combines the last prediction's panels with the CURRENT table: a new table ends that
@@ -801,10 +830,12 @@ int mogp_model_set_kinds(mogp_model* m, int T, const int* kind, const double* sh
     const size_t n = (size_t)m->C * m->C * T;
     bool any = false;
     if (const char* bad = check_kinds(kind, shape, m->C, m->D, T, &any)) return fail(MOGP_EINVAL, std::string("mogp_model_set_kinds: ") + bad);
-    m->radial = false;
+    m->radial = false; m->point_kinds = false;
     if (!any) return MOGP_OK;                   // all Gaussian: as if never called
     if (m->Wt != 2 + 3 * m->D) return fail(MOGP_EINVAL, "mogp_model_set_kinds: radial profiles do not combine with enveloped term rows");
     m->hkind.assign(kind, kind + n);            // table_diag needs the groups on the host
+    m->hshape.assign(shape, shape + n);
+    for (size_t i = 0; i < n; ++i) m->point_kinds |= (kind[i] & MOGP_KIND_MASK) == MOGP_KIND_DOT;
     int rc;
     if ((rc = use_device(m->ctx))) return rc;
     if ((rc = m->d_kind.ensure(n))) return rc;

@@ -20,6 +20,11 @@
 #ifndef MOGP_KIND_PERIODIC      // (the two new values are public: include/mogp_hip.h)
 #define MOGP_KIND_PERIODIC 5   // exp(V (cos theta - 1)), theta = 2 pi (M u + Psi): the phase is the profile's ARGUMENT, not a cosine factor (D = 1)
 #endif
+#ifndef MOGP_KIND_SINC
+#define MOGP_KIND_SINC 6       // sin(pi r) / (pi r) (D = 1)
+#define MOGP_KIND_DOT 7        // (A <x_a, x_b> + Psi)^shape: the dot-product row -- not a profile of s, and non-stationary (its diagonal follows the point)
+#define MOGP_DOT_DEGREE_MAX 8
+#endif
 // Product groups: a row whose kind carries MOGP_KIND_TIMES multiplies with the next row.  A maximal run of flagged rows plus the row that
 // ends it is a group (at most MOGP_GROUP_MAX rows); the Gram is the sum over groups of the product of their rows' values.
 #ifndef MOGP_KIND_TIMES

@@ -322,6 +322,8 @@ struct mogp_model {
     mogp::DevBuf<int> d_kind;
     std::vector<int> hkind;             // host copy of the kinds while `radial` (table_diag: a product group's diagonal is the product of its amplitudes)
     mogp::DevBuf<double> d_shape;
+    std::vector<double> hshape;         // host copy of the shapes while `radial` (the degree of a dot-product row)
+    bool point_kinds = false;           // some row is a dot-product row (MOGP_KIND_DOT): K(x, x) follows the point, as with an envelope
     hipStream_t st = nullptr;           // critical-path stream (high priority)
     hipStream_t st2 = nullptr;          // bulk trailing updates of the fused schedule (CU-masked: everything but the reserved CUs)
     hipStream_t st2u = nullptr;         // bulk trailing updates over ALL CUs, for flop-bound sizes (MOGP_CHAIN_BOUND_TILES)

@@ -38,6 +38,9 @@ def pad_width(table, width):
 # Product groups: a row whose kind carries KIND_TIMES multiplies with the next row; a maximal run of flagged rows plus the row that
 # ends it is a group of at most GROUP_MAX rows, and the kernel is the sum over groups of the product of their rows.  The low bits stay the profile.
 KIND_TIMES, KIND_MASK, GROUP_MAX = 1 << 8, 0xff, 4
+# The dot-product row (A <x_a, x_b> + c)^n of LinearKernel / PolynomialKernel: A in the amplitude slot, the bias c in the Psi slot, n the shape.
+# It is the one row whose diagonal value follows the point, (A |x|^2 + c)^n, instead of being its amplitude.
+KIND_DOT = 7
 
 
 def group_slices(kind_row):
@@ -196,6 +199,10 @@ class Kernel(ParameterHolder):
         """some term has a non-Gaussian profile: only then do kinds travel to the device"""
         return bool(np.any(self._spectral_kinds(D)[0]))
 
+    def _pointwise(self, D):
+        """some row is a dot-product row: K(x, x) follows the point, as with an envelope, and `_point_diag` stands where `_spectral_diag` stood"""
+        return bool(np.any((self._spectral_kinds(D)[0] & KIND_MASK) == KIND_DOT))
+
     def _spectral_diag(self, D):
         """K_diag value per channel AS THE REFERENCE RETURNS IT (constant per channel for every spectral kernel).
         Default: the true diagonal sum_t A_cct (Delta = Psi = 0 on i == j blocks), over product groups the sum of their amplitudes' products;
@@ -243,7 +250,7 @@ class Kernel(ParameterHolder):
         X1k = self._kernel_format(np.asarray(X1, dtype=np.float64))
         D = X1k.shape[1] - 1
         table = self._spectral_terms(D)
-        if table.shape[3] > term_width(D):
+        if table.shape[3] > term_width(D) or self._pointwise(D):
             return self._point_diag(table, X1k, D)
         return self._spectral_diag(D)[X1k[:, 0].astype(np.int64)]
 
@@ -256,13 +263,42 @@ class Kernel(ParameterHolder):
         a = Xk[:, None, 1:] - cn                                  # (N, T, D)
         return np.exp(-0.5 * np.sum(Lv * a * a, axis=2)), a, rows
 
+    def _point_rows(self, table, Xk, D):
+        """From a table with kinds (no envelope), per point k (channel c) and row t of the diagonal pair (c, c): the row's value v on the
+        diagonal -- its amplitude (every profile is 1 at zero distance, Delta = Psi = 0 there), for a dot-product row (A |x|^2 + c)^n --
+        with dv/dA and dv/dc (c: the bias in a dot-product row's Psi slot), and the groups, which are the same in every pair"""
+        kind, shape = self._spectral_kinds(D)
+        c = Xk[:, 0].astype(np.int64)
+        rows = table[c, c]                                        # (N, T, W)
+        dot = (kind[c, c] & KIND_MASK) == KIND_DOT
+        x2 = np.sum(np.square(Xk[:, 1:]), axis=1)[:, None]
+        n = np.where(dot, shape[c, c], 1.0)
+        b = np.where(dot, rows[..., 0] * x2 + rows[..., 1], 1.0)
+        db = n * b ** (n - 1.0)
+        return np.where(dot, b ** n, rows[..., 0]), np.where(dot, db * x2, 1.0), np.where(dot, db, 0.0), group_slices(kind[0, 0])
+
     def _point_diag(self, table, Xk, D):
-        """K_diag per point from an enveloped term table: sum_t A_cct env_t(x)   (Delta = Psi = 0 on diagonal pairs)"""
+        """K_diag per point.  Enveloped term table: sum_t A_cct env_t(x)   (Delta = Psi = 0 on diagonal pairs); a table with kinds: the sum
+        over groups of the product of the rows' diagonal values at the point (`_point_rows`)"""
+        if table.shape[3] == term_width(D):
+            v, _, _, groups = self._point_rows(table, Xk, D)
+            return sum(np.prod(v[:, a:b], axis=1) for a, b in groups)
         env, _, rows = self._point_env(table, Xk, D)
         return np.sum(rows[..., 0] * env, axis=1)
 
     def _point_diag_table_grad(self, table, Xk, D, weights=None):
         """d [ sum_k w_k K_diag(x_k) ] / d table (w = 1: what the relative jitter, gpr/model.py:244, contributes per unit of d/d mean(diag) * N)"""
+        if table.shape[3] == term_width(D):                     # kinds: the product rule inside a group, amplitude and (dot-product rows) bias
+            v, dA, dc, groups = self._point_rows(table, Xk, D)
+            w = np.ones(len(Xk)) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+            c = Xk[:, 0].astype(np.int64)
+            gt = np.zeros_like(table)
+            for a, b in groups:
+                for t in range(a, b):
+                    others = w * np.prod(np.delete(v[:, a:b], t - a, axis=1), axis=1)
+                    gt[:, :, t, 0][np.diag_indices(table.shape[0])] = np.bincount(c, weights=others * dA[:, t], minlength=table.shape[0])
+                    gt[:, :, t, 1][np.diag_indices(table.shape[0])] = np.bincount(c, weights=others * dc[:, t], minlength=table.shape[0])
+            return gt
         env, a, rows = self._point_env(table, Xk, D)
         if weights is not None:
             env = env * np.asarray(weights, dtype=np.float64).reshape(-1, 1)

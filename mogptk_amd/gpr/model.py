@@ -10,7 +10,7 @@ from math import erf, sqrt
 
 from .config import config
 from .parameter import Parameter, ParameterHolder
-from .kernel import Kernel, MulKernel, terms_cache, KIND_TIMES, group_diag_grad
+from .kernel import Kernel, MulKernel, terms_cache, KIND_TIMES, KIND_MASK, KIND_DOT, group_diag_grad
 from .likelihood import Likelihood, GaussianLikelihood
 from .mean import Mean
 
@@ -66,9 +66,11 @@ def _pair_index(C, lower):
     return _PAIR_INDEX[key]
 
 
-def _gtable_from_moments(table, mom, D, lower=True):
+def _gtable_from_moments(table, mom, D, lower=True, kind=None):
     """d(objective)/d(term table) from the device's gradient moments [m0, m4, m1_d, m2_d, m3_d]:
     dA = m0, dPsi = -2 pi A m4, dV_d = -1/2 A m1_d, dM_d = -2 pi A m3_d, dDelta_d = -V_d A m2_d - 2 pi M_d A m4.
+    `kind` (the table's kinds, when they travelled): a dot-product row's moments are derivatives already -- dA = m0, and the bias in its Psi
+    slot gets m1_0 (an even slot, which the device keeps on diagonal channel blocks); its other columns are not parameters.
     lower=True: mom is indexed by lower channel pairs p = i(i+1)/2 + j (symmetric Gram, double count already
     included); lower=False: mom is indexed by all ordered pairs i*C + j (rectangular Gram)."""
     C, T = table.shape[0], table.shape[2]
@@ -90,6 +92,11 @@ def _gtable_from_moments(table, mom, D, lower=True):
         Lv = tb[..., 2 + 3 * D:2 + 4 * D]
         g[..., 2 + 3 * D:2 + 4 * D] = -0.5 * A[..., None] * mom[..., 2 + 3 * D:2 + 4 * D]
         g[..., 2 + 4 * D:2 + 5 * D] = Lv * A[..., None] * mom[..., 2 + 4 * D:2 + 5 * D]
+    if kind is not None:
+        dot = (kind[ii, jj] & KIND_MASK) == KIND_DOT
+        if np.any(dot):
+            g[dot, 1:] = 0.0
+            g[dot, 1] = mom[..., 2][dot]
     gt[ii, jj] = g
     return gt
 
@@ -234,7 +241,7 @@ class Model(ParameterHolder):
 
     def _kernel_diag(self, table, Xk, D):
         """K_diag as the device takes it: per point of Xk with enveloped terms, else per channel"""
-        return self.kernel._point_diag(table, Xk, D) if _enveloped(table, D) else self.kernel._spectral_diag(D)
+        return self.kernel._point_diag(table, Xk, D) if _enveloped(table, D) or self.kernel._pointwise(D) else self.kernel._spectral_diag(D)
 
     def _train_counts(self):
         """training points per channel.  X does not change under a model (reference gpr/model.py:113-118): counted once per X and number of channels"""
@@ -439,8 +446,13 @@ class Exact(Model):
             h.set_kinds(None, None)               # the kernel was replaced by an all-Gaussian one with the same number of terms
         h.radial_kinds = radial
         h.group_kinds = kind if radial and np.any(kind & KIND_TIMES) else None      # product groups: _loss_impl's jitter term needs them
-        if _enveloped(table, D):              # envelope: the diagonal varies from point to point and enters the relative jitter (:244)
+        h.dot_kinds = kind if radial and self.kernel._pointwise(D) else None      # dot-product rows: _loss_impl's moments and jitter term need them
+        if _enveloped(table, D) or h.dot_kinds is not None:      # envelope, dot-product rows: the diagonal varies from point to point and enters the relative jitter (:244)
             h.set_point_diag(self.kernel._point_diag(table, self.kernel._kernel_format(self.X), D))
+            h.point_diag_set = True
+        elif getattr(h, "point_diag_set", False):                # the kernel was replaced by one with a constant diagonal
+            h.set_point_diag(None)
+            h.point_diag_set = False
         return h, table, D
 
     def _eval(self, grad):
@@ -498,8 +510,9 @@ class Exact(Model):
         jit_rel = self.jitter * res["trG"] / self.X.shape[0]            # d LML / d (mean diag) through the jitter term (:244)
 
         # d LML / d table for the lower channel pairs (i >= j); zero elsewhere
-        gt = _gtable_from_moments(table, res["moments"], D, lower=True)
-        if _enveloped(table, D):
+        dot_kinds = getattr(self._handle, "dot_kinds", None)
+        gt = _gtable_from_moments(table, res["moments"], D, lower=True, kind=dot_kinds)
+        if _enveloped(table, D) or dot_kinds is not None:
             gt += jit_rel * self.kernel._point_diag_table_grad(table, self.kernel._kernel_format(self.X), D)
         else:
             kind = getattr(self._handle, "group_kinds", None)

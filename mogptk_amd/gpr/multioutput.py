@@ -13,7 +13,7 @@ import numpy as np
 
 from .config import config
 from .parameter import Parameter, _STRUCTURE_EPOCH
-from .kernel import Kernel, MultiOutputKernel, term_width, cached_terms, KIND_TIMES, group_slices
+from .kernel import Kernel, MultiOutputKernel, term_width, cached_terms, KIND_TIMES, KIND_MASK, KIND_DOT, GROUP_MAX, group_slices
 
 PI = np.pi
 
@@ -449,12 +449,27 @@ class LinearModelOfCoregionalizationKernel(MultiOutputKernel):
         w = self.weight()                                                   # (C,Q,Rq)
         return np.einsum("iqr,jqr->ijq", w, w)                               # B_q[i,j]  (:493)
 
-    def _lead(self, k, D):
-        """rows of base kernel k that take the coregionalization factor B_q: every row, but only the FIRST of a product group (B once per group)"""
-        kd = k._spectral_kinds(D)[0][0, 0]
-        lead = np.zeros(len(kd), dtype=bool)
-        lead[[a for a, _ in group_slices(kd)]] = True
-        return lead
+    def _rows(self, k, D):
+        """The rows base kernel k puts into every channel pair: (rows (T, W), kinds, shapes, lead, src).  `lead` marks the rows that take the
+        coregionalization factor B_q through their amplitude: every row, but only the FIRST of a product group (B once per group).  An
+        amplitude does not scale a dot-product row, so a group that starts with one gets a leading plain row (V = M = 0, unit amplitude)
+        that carries B_q; it counts towards the rows of the group.  `src`: the base kernel's row behind each row, -1 for such a leading row."""
+        sub = k._spectral_terms(D)[0, 0]                                     # (T_q, W): Psi = Delta = 0 for single-output kernels
+        kd, sh = (a[0, 0] for a in k._spectral_kinds(D))
+        rows, kinds, shapes, lead, src = [], [], [], [], []
+        for a, b in group_slices(kd):
+            dot_first = (int(kd[a]) & KIND_MASK) == KIND_DOT
+            if dot_first:
+                if b - a + 1 > GROUP_MAX:
+                    raise NotImplementedError("a product of %d table rows with a dot-product row first needs one more row for the coregionalization "
+                                              "factor under %s: the device multiplies groups of at most %d rows" % (b - a, self.name(), GROUP_MAX))
+                plain = np.zeros(sub.shape[1])
+                plain[0] = 1.0
+                rows.append(plain); kinds.append(KIND_TIMES); shapes.append(0.0); lead.append(True); src.append(-1)
+            for t in range(a, b):
+                rows.append(sub[t]); kinds.append(int(kd[t])); shapes.append(sh[t]); src.append(t)
+                lead.append(t == a and not dot_first)
+        return np.array(rows), np.array(kinds, dtype=np.int32), np.array(shapes, dtype=np.float64), np.array(lead, dtype=bool), src
 
     @cached_terms
     def _spectral_terms(self, D):
@@ -462,19 +477,18 @@ class LinearModelOfCoregionalizationKernel(MultiOutputKernel):
         C = self.output_dims
         parts = []
         for q, k in enumerate(self.kernels):
-            sub = k._spectral_terms(D)[0, 0]                                 # (T_q, W): Psi = Delta = 0 for single-output kernels
-            part = np.broadcast_to(sub, (C, C) + sub.shape).copy()
-            lead = self._lead(k, D)
-            part[..., lead, 0] = B[:, :, q, None] * sub[None, None, lead, 0]
+            rows, _, _, lead, _ = self._rows(k, D)
+            part = np.broadcast_to(rows, (C, C) + rows.shape).copy()
+            part[..., lead, 0] = B[:, :, q, None] * rows[None, None, lead, 0]
             parts.append(part)
         return np.concatenate(parts, axis=2)
 
     @cached_terms
     def _spectral_kinds(self, D):
         C = self.output_dims
-        subs = [k._spectral_kinds(D) for k in self.kernels]            # every channel pair carries the base kernels' terms, along T
-        kind = np.concatenate([np.broadcast_to(kd[0, 0], (C, C) + kd.shape[2:]) for kd, _ in subs], axis=2)
-        shape = np.concatenate([np.broadcast_to(sh[0, 0], (C, C) + sh.shape[2:]) for _, sh in subs], axis=2)
+        subs = [self._rows(k, D)[1:3] for k in self.kernels]           # every channel pair carries the base kernels' terms, along T
+        kind = np.concatenate([np.broadcast_to(kd, (C, C) + kd.shape) for kd, _ in subs], axis=2)
+        shape = np.concatenate([np.broadcast_to(sh, (C, C) + sh.shape) for _, sh in subs], axis=2)
         return np.ascontiguousarray(kind, dtype=np.int32), np.ascontiguousarray(shape)
 
     def _spectral_diag(self, D):
@@ -505,14 +519,17 @@ class LinearModelOfCoregionalizationKernel(MultiOutputKernel):
         gB = np.zeros_like(B)
         t0 = 0
         for q, k in enumerate(self.kernels):
-            sub = k._spectral_terms(D)[0, 0]
+            sub, _, _, lead, src = self._rows(k, D)
             T = sub.shape[0]
             g = gtable[:, :, t0:t0 + T, :]                                   # zero above the diagonal, double count included
-            lead = self._lead(k, D)
             gB[:, :, q] = np.sum(g[..., lead, 0] * sub[None, None, lead, 0], axis=2)
-            gsub = np.sum(g, axis=(0, 1))                                    # V, M columns: the same base value in every pair
+            gsub = np.sum(g, axis=(0, 1))                                    # V, M columns (a dot-product row: A, c): the same base value in every pair
             gsub[lead, 0] = np.einsum("ijt,ij->t", g[..., lead, 0], B[:, :, q])
-            k._spectral_backward(gsub[None, None])
+            gbase = np.zeros((max(src) + 1, gsub.shape[1]))                  # (a leading coregionalization row belongs to no base row)
+            for r, t in enumerate(src):
+                if t >= 0:
+                    gbase[t] = gsub[r]
+            k._spectral_backward(gbase[None, None])
             t0 += T
         self._weight_backward(gB)
 

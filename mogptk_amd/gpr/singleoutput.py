@@ -9,7 +9,7 @@ import numpy as np
 
 from .config import config
 from .parameter import Parameter
-from .kernel import Kernel, term_width, cached_terms, KIND_TIMES
+from .kernel import Kernel, term_width, cached_terms, KIND_TIMES, KIND_DOT
 from .multioutput import _accumulate
 
 FOUR_PI2 = 4.0 * np.pi ** 2
@@ -96,7 +96,7 @@ class SpectralKernel(Kernel):
 
 
 # radial profile of a term (include/mogp_hip.h: mogp_model_set_kinds)
-KIND_GAUSS, KIND_RQ, KIND_MATERN12, KIND_MATERN32, KIND_MATERN52, KIND_PERIODIC = 0, 1, 2, 3, 4, 5
+KIND_GAUSS, KIND_RQ, KIND_MATERN12, KIND_MATERN32, KIND_MATERN52, KIND_PERIODIC, KIND_SINC = 0, 1, 2, 3, 4, 5, 6      # (KIND_DOT = 7: gpr/kernel.py)
 
 
 class _RadialKernel(Kernel):
@@ -340,3 +340,87 @@ class LocallyPeriodicKernel(PeriodicKernel):
     def _spectral_backward(self, gtable):
         g = gtable[0, 0]
         self._periodic_backward(g[0], g[0, 2] + g[1, 2])
+
+
+class SincKernel(_MagnitudeKernel):
+    """K = mag sinc(bandwidth tau) cos(2 pi frequency tau), sinc(r) = sin(pi r) / (pi r) (reference :475-518): one row of kind 6 with
+    V = bandwidth^2 and M = frequency -- an ordinary radial profile with its cosine beside it.  One input dimension."""
+
+    def __init__(self, input_dims=1, active_dims=None):
+        super().__init__(input_dims, active_dims)
+        _check_one_dim(input_dims, "SincKernel", "sum_d tau_d bandwidth_d inside the sinc")
+        self.magnitude = Parameter(1.0, lower=config.positive_minimum)
+        self.frequency = Parameter(np.ones(input_dims), lower=config.positive_minimum)
+        self.bandwidth = Parameter(np.ones(input_dims), lower=config.positive_minimum)
+
+    @cached_terms
+    def _spectral_terms(self, D):
+        self._check_dims(D)
+        table = np.zeros((1, 1, 1, term_width(D)))
+        table[0, 0, 0, 0] = self.magnitude()
+        table[0, 0, 0, 2] = float(self.bandwidth()[0]) ** 2
+        table[0, 0, 0, 3] = float(self.frequency()[0])
+        return table
+
+    @cached_terms
+    def _spectral_kinds(self, D):
+        return np.full((1, 1, 1), KIND_SINC, dtype=np.int32), np.zeros((1, 1, 1))
+
+    def _spectral_backward(self, gtable):
+        g = gtable[0, 0, 0]
+        _accumulate(self.magnitude, np.reshape(g[0], self.magnitude.shape))
+        _accumulate(self.frequency, np.reshape(g[3], self.frequency.shape))
+        _accumulate(self.bandwidth, np.reshape(2.0 * float(self.bandwidth()[0]) * g[2], self.bandwidth.shape))      # d V / d bandwidth
+
+
+DOT_DEGREE_MAX = 8
+
+
+class LinearKernel(Kernel):
+    """K = mag <x, x'> + bias (reference :69-101): one dot-product row (kind 7) of degree 1 -- the magnitude in the amplitude slot, the
+    bias in the Psi slot, which no cosine reads there.  Not stationary: K_diag = mag |x|^2 + bias follows the point."""
+    _degree = 1
+
+    def __init__(self, input_dims=1, active_dims=None):
+        super().__init__(input_dims, active_dims)
+        self.bias = Parameter(0.0, lower=0.0)
+        self.magnitude = Parameter(1.0, lower=config.positive_minimum)
+
+    @cached_terms
+    def _spectral_terms(self, D):
+        if D != self.input_dims:
+            raise ValueError("X must have %d input dimensions" % self.input_dims)
+        table = np.zeros((1, 1, 1, term_width(D)))
+        table[0, 0, 0, 0] = self.magnitude()
+        table[0, 0, 0, 1] = self.bias()
+        return table
+
+    @cached_terms
+    def _spectral_kinds(self, D):
+        return np.full((1, 1, 1), KIND_DOT, dtype=np.int32), np.full((1, 1, 1), float(self._degree))
+
+    def _spectral_diag(self, D):
+        raise NotImplementedError("%s has no diagonal value per channel: K(x, x) follows the point (Kernel._point_diag)" % self.name())
+
+    def _spectral_backward(self, gtable):
+        g = gtable[0, 0, 0]
+        _accumulate(self.bias, np.reshape(g[1], self.bias.shape))
+        _accumulate(self.magnitude, np.reshape(g[0], self.magnitude.shape))
+
+
+class PolynomialKernel(LinearKernel):
+    """K = (mag <x, x'> + bias)^degree (reference :103-138): the dot-product row of degree `degree`, a plain integer from 1 to 8 (the device
+    multiplies it out)."""
+
+    def __init__(self, degree, input_dims=1, active_dims=None):
+        Kernel.__init__(self, input_dims, active_dims)
+        if int(degree) != degree or not 1 <= degree <= DOT_DEGREE_MAX:
+            raise NotImplementedError("PolynomialKernel with degree %r is not on the HIP path: the device multiplies the power out, an integer "
+                                      "degree from 1 to %d" % (degree, DOT_DEGREE_MAX))
+        self.degree = degree
+        self.bias = Parameter(0.0, lower=0.0)
+        self.magnitude = Parameter(1.0, lower=config.positive_minimum)
+
+    @property
+    def _degree(self):
+        return int(self.degree)
