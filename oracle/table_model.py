@@ -31,7 +31,99 @@ def table_block(tab, x1, x2, sin=False, with_mid=False):
     return E * np.cos(ph), E * np.sin(ph), u
 
 
-def gram_from_table(table, X1, X2=None):
+# ----------------------------------------------------------------------------------------------------------------
+# Kinds and product groups (include/mogp_hip.h: mogp_model_set_kinds).  The low bits of a row's kind are its
+# profile, KIND_TIMES multiplies the row with the next one: a maximal run of flagged rows plus the row that ends it is
+# a group, and the kernel is the sum over groups of the product of their rows.  The twin keeps its own constants.
+# ----------------------------------------------------------------------------------------------------------------
+KIND_TIMES, KIND_MASK = 1 << 8, 0xff
+KIND_RQ, KIND_MATERN12, KIND_MATERN32, KIND_MATERN52, KIND_PERIODIC, KIND_SINC, KIND_DOT = 1, 2, 3, 4, 5, 6, 7
+SQ3, SQ5 = np.sqrt(3.0), np.sqrt(5.0)
+
+
+def _kinds(kind, shape):
+    """(kind, shape) as integer / float arrays, or (None, None) for a table that is all Gaussian rows without a group"""
+    if kind is None or not np.any(kind):
+        return None, None
+    return np.asarray(kind, dtype=np.int64), np.asarray(shape, dtype=np.float64)
+
+
+def profiles(kind, shape, s):
+    """phi(s) and psi(s) = -2 dphi/ds of DESIGN 1b; u psi and u^2 psi are 0 where Matern 1/2 has r = 0, so psi is returned as 0 there"""
+    r = np.sqrt(s)
+    if kind == KIND_RQ:
+        b = 1.0 + s / (2.0 * shape)
+        return b ** -shape, b ** (-shape - 1.0)
+    if kind == KIND_MATERN12:
+        return np.exp(-r), np.where(r > 0, np.exp(-r) / np.where(r > 0, r, 1.0), 0.0)
+    if kind == KIND_MATERN32:
+        return (1.0 + SQ3 * r) * np.exp(-SQ3 * r), 3.0 * np.exp(-SQ3 * r)
+    if kind == KIND_MATERN52:
+        return (1.0 + SQ5 * r + 5.0 * s / 3.0) * np.exp(-SQ5 * r), (5.0 / 3.0) * (1.0 + SQ5 * r) * np.exp(-SQ5 * r)
+    if kind == KIND_SINC:                                   # psi by its series where the closed form cancels
+        phi = np.sinc(r)
+        return phi, np.where(s > 1e-8, (phi - np.cos(np.pi * r)) / np.where(s > 1e-8, s, 1.0), np.pi ** 2 * (1.0 / 3.0 - np.pi ** 2 * s / 30.0))
+    return np.exp(-0.5 * s), np.exp(-0.5 * s)
+
+
+def row_parts(row, kind, shape, x1, x2):
+    """(value of one table row WITHOUT its amplitude -- a dot-product row: its full value --, the integrands of its moments
+    [m0, m4, m1_d, m2_d, m3_d]) at the inputs x1 (n1, D), x2 (n2, D)"""
+    D = x1.shape[1]
+    if kind == KIND_DOT:                                    # k = b^n, b = A <x_a, x_b> + c: m0 = d/dA, slot 2 = d/dc, nothing else
+        ip = x1 @ x2.T
+        n = int(shape)
+        b = row[0] * ip + row[1]
+        db = n * b ** (n - 1)
+        zero = np.zeros_like(ip)
+        return b ** n, [db * ip, zero, db] + [zero] * (3 * D - 1)
+    Psi, V, M = row[1], row[2:2 + D], row[2 + D:2 + 2 * D]
+    u = x1[:, None, :] - x2[None, :, :] + row[2 + 2 * D:2 + 3 * D]
+    th = TWO_PI * (np.sum(M * u, axis=2) + Psi)
+    if kind == KIND_PERIODIC:                               # E = exp(V (cos - 1)): the phase is the profile's argument
+        E = np.exp(V[0] * (np.cos(th) - 1.0))
+        return E, [E, E * V[0] * np.sin(th), E * 2.0 * (1.0 - np.cos(th)), 0.0 * E, E * V[0] * u[..., 0] * np.sin(th)]
+    phi, psi = profiles(kind, shape, np.sum(V * u * u, axis=2))
+    parts = [phi * np.cos(th), phi * np.sin(th)]
+    parts += [u[..., d] ** 2 * psi * np.cos(th) for d in range(D)] + [u[..., d] * psi * np.cos(th) for d in range(D)]
+    parts += [u[..., d] * phi * np.sin(th) for d in range(D)]
+    return phi * np.cos(th), parts
+
+
+def kinds_block(tab, kind, shape, x1, x2, g=None):
+    """one channel-pair block of a table with kinds: its value (n1, n2) and, with an adjoint g (n1, n2), its moments (T, 2 + 3 D): row t of
+    a group sees g weighted by the product of the group's other rows"""
+    T, D = tab.shape[0], x1.shape[1]
+    if tab.shape[1] > 2 + 3 * D:
+        raise ValueError("kinds and enveloped rows do not go together")
+    kd = kind & KIND_MASK
+    rows = [row_parts(tab[t], int(kd[t]), shape[t], x1, x2) for t in range(T)]
+    K = np.zeros((x1.shape[0], x2.shape[0]))
+    mom = None if g is None else np.zeros((T, 2 + 3 * D))
+    t0 = 0
+    for t in range(T):
+        if (int(kind[t]) & KIND_TIMES) and t < T - 1:       # the group goes on
+            continue
+        vals = [rows[h][0] if kd[h] == KIND_DOT else tab[h, 0] * rows[h][0] for h in range(t0, t + 1)]
+        K += np.prod(vals, axis=0)
+        if g is not None:
+            for h in range(t0, t + 1):
+                w = g * np.prod([v for q, v in enumerate(vals) if q != h - t0] + [np.ones_like(vals[0])], axis=0)
+                mom[h] = [np.sum(w * part) for part in rows[h][1]]
+        t0 = t + 1
+    return K, mom
+
+
+def _gram_block(table, kind, shape, i, j, x1, x2):
+    tab = table[i, j]
+    if kind is not None:
+        return kinds_block(tab, kind[i, j], shape[i, j], x1, x2)[0]
+    Ec, _, _ = table_block(tab, x1, x2)
+    return np.einsum("t,tnm->nm", tab[:, 0], Ec)
+
+
+def gram_from_table(table, X1, X2=None, kind=None, shape=None):
+    kind, shape = _kinds(kind, shape)
     C = table.shape[0]
     c1 = X1[:, 0].astype(np.int64)
     X2_ = X1 if X2 is None else X2
@@ -43,13 +135,10 @@ def gram_from_table(table, X1, X2=None):
             r2 = np.nonzero(c2 == j)[0]
             if len(r1) == 0 or len(r2) == 0:
                 continue
-            tab = table[i, j] if (X2 is not None or i >= j) else None
-            if tab is None:       # symmetric case: mirror of the lower block (kernel.py:466-467)
-                Ec, _, _ = table_block(table[j, i], X1[r2, 1:], X1[r1, 1:])
-                K[np.ix_(r1, r2)] = np.einsum("t,tnm->nm", table[j, i][:, 0], Ec).T
-            else:
-                Ec, _, _ = table_block(tab, X1[r1, 1:], X2_[r2, 1:])
-                K[np.ix_(r1, r2)] = np.einsum("t,tnm->nm", tab[:, 0], Ec)
+            if X2 is not None or i >= j:
+                K[np.ix_(r1, r2)] = _gram_block(table, kind, shape, i, j, X1[r1, 1:], X2_[r2, 1:])
+            else:                 # symmetric case: mirror of the lower block (kernel.py:466-467)
+                K[np.ix_(r1, r2)] = _gram_block(table, kind, shape, j, i, X1[r2, 1:], X1[r1, 1:]).T
     return K
 
 
@@ -60,6 +149,7 @@ class TableDevice:
         self.X = np.array(X, dtype=np.float64)
         self.y = np.array(y, dtype=np.float64).reshape(-1, 1)
         self.N, self.D, self.C = X.shape[0], X.shape[1] - 1, C
+        self.kind = self.shape = self.point_diag = None
 
     def set_y(self, y):
         self.y = np.array(y, dtype=np.float64).reshape(-1, 1)
@@ -67,12 +157,22 @@ class TableDevice:
     def set_terms(self, table):
         self.table = np.array(table, dtype=np.float64)
         self.T = table.shape[2]
+        self.kind = self.shape = None
+
+    def set_kinds(self, kind, shape):
+        self.kind, self.shape = kind, shape
 
     def set_point_diag(self, kdiag):
-        pass                         # the twin takes the diagonal from its own Gram matrix
+        self.point_diag = None if kdiag is None else np.array(kdiag)      # only checked: the twin takes the diagonal from its own Gram matrix
 
-    def _Kj(self, noise_var, jitter, data_var):
-        K = gram_from_table(self.table, self.X)
+    def _gram(self, X1, X2=None):
+        return gram_from_table(self.table, X1, X2, self.kind, self.shape)
+
+    def _Kj(self, noise_var, jitter, data_var, check_diag=False):
+        K = self._gram(self.X)
+        if check_diag and self.point_diag is not None:
+            kd = np.diagonal(K)
+            assert np.max(np.abs(kd - self.point_diag)) <= 1e-13 * max(1.0, np.max(kd)), "the per-point diagonal is not the Gram matrix's"
         c = self.X[:, 0].astype(np.int64)
         d = np.diagonal(K) + np.asarray(noise_var)[c] + (0.0 if data_var is None else data_var)
         jit = jitter * np.mean(d)
@@ -81,7 +181,7 @@ class TableDevice:
 
     def eval(self, noise_var, jitter, grad=True, data_var=None):
         from scipy.linalg import solve_triangular
-        K, jit = self._Kj(noise_var, jitter, data_var)
+        K, jit = self._Kj(noise_var, jitter, data_var, check_diag=True)
         L = np.linalg.cholesky(K)
         z = solve_triangular(L, self.y, lower=True)
         alpha = solve_triangular(L.T, z, lower=False)
@@ -94,6 +194,11 @@ class TableDevice:
         C, T, D = self.C, self.T, self.D
         c = self.X[:, 0].astype(np.int64)
         W = self.table.shape[3]
+        dG = np.diagonal(G)
+        diagG = np.array([np.sum(dG[c == k]) for k in range(C)])
+        if _kinds(self.kind, self.shape)[0] is not None:
+            return dict(lml=lml, moments=moments_dense(self.table, G, self.X, self.X, sym=True, kind=self.kind, shape=self.shape),
+                        diagG=diagG, trG=float(np.sum(dG)), jitter_abs=jit)
         mom = np.zeros((C * (C + 1) // 2, T, W))
         for i in range(C):
             ri = np.nonzero(c == i)[0]
@@ -112,8 +217,6 @@ class TableDevice:
                 if a is not None:
                     m[:, 2 + 3 * D:2 + 4 * D] = np.einsum("nm,tnm,tnmd->td", g, Ec, a * a)
                     m[:, 2 + 4 * D:2 + 5 * D] = np.einsum("nm,tnm,tnmd->td", g, Ec, a)
-        dG = np.diagonal(G)
-        diagG = np.array([np.sum(dG[c == k]) for k in range(C)])
         return dict(lml=lml, moments=mom, diagG=diagG, trG=float(np.sum(dG)), jitter_abs=jit)
 
     def fetch(self, which):
@@ -132,14 +235,15 @@ class TableDevice:
         from scipy.linalg import solve_triangular
         K, _ = self._Kj(noise_var, jitter, data_var)
         L = np.linalg.cholesky(K)
-        Kfs = gram_from_table(self.table, self.X, Xs)
+        Kfs = self._gram(self.X, Xs)
         alpha = solve_triangular(L.T, solve_triangular(L, self.y, lower=True), lower=False)
         v = solve_triangular(L, Kfs, lower=True)
         mu = Kfs.T @ alpha
         if full:
-            return mu, gram_from_table(self.table, Xs) - v.T @ v
+            return mu, self._gram(Xs) - v.T @ v
         cs = Xs[:, 0].astype(np.int64)
-        kdiag = np.asarray(kss_diag) if self.table.shape[3] > 2 + 3 * self.D else np.asarray(kss_diag)[cs]      # enveloped terms: per test point
+        per_point = self.table.shape[3] > 2 + 3 * self.D or (self.kind is not None and np.any((self.kind & KIND_MASK) == KIND_DOT))
+        kdiag = np.asarray(kss_diag) if per_point else np.asarray(kss_diag)[cs]      # enveloped terms, dot-product rows: per test point
         return mu, (kdiag - np.sum(v * v, axis=0)).reshape(-1, 1)
 
 
@@ -172,9 +276,10 @@ def _jc_block(tab, x1, x2):
     return J
 
 
-def moments_dense(table, G, X1, X2, sym):
+def moments_dense(table, G, X1, X2, sym, kind=None, shape=None):
     """moments of a dense adjoint G (rows X1, cols X2).  sym: lower channel pairs with the symmetric double count
     (G symmetric, X2 is X1) -> (P, T, W); otherwise all ordered pairs -> (C*C, T, W)."""
+    kind, shape = _kinds(kind, shape)
     C, T = table.shape[0], table.shape[2]
     D = X1.shape[1] - 1
     c1, c2 = X1[:, 0].astype(np.int64), X2[:, 0].astype(np.int64)
@@ -186,14 +291,17 @@ def moments_dense(table, G, X1, X2, sym):
             rj = np.nonzero(c2 == j)[0]
             if len(ri) == 0 or len(rj) == 0:
                 continue
-            Ec, Es, u, amid = table_block(table[i, j], X1[ri, 1:], X2[rj, 1:], with_mid=True)
             g = G[np.ix_(ri, rj)] * (2.0 if (sym and i != j) else 1.0)
             m = out[i * (i + 1) // 2 + j] if sym else out[i * C + j]
-            m[:, 0] = np.einsum("nm,tnm->t", g, Ec)
-            m[:, 1] = np.einsum("nm,tnm->t", g, Es)
-            m[:, 2:2 + D] = np.einsum("nm,tnm,tnmd->td", g, Ec, u * u)
-            m[:, 2 + D:2 + 2 * D] = np.einsum("nm,tnm,tnmd->td", g, Ec, u)
-            m[:, 2 + 2 * D:2 + 3 * D] = np.einsum("nm,tnm,tnmd->td", g, Es, u)
+            if kind is not None:
+                m[:] = kinds_block(table[i, j], kind[i, j], shape[i, j], X1[ri, 1:], X2[rj, 1:], g)[1]
+            else:
+                Ec, Es, u, amid = table_block(table[i, j], X1[ri, 1:], X2[rj, 1:], with_mid=True)
+                m[:, 0] = np.einsum("nm,tnm->t", g, Ec)
+                m[:, 1] = np.einsum("nm,tnm->t", g, Es)
+                m[:, 2:2 + D] = np.einsum("nm,tnm,tnmd->td", g, Ec, u * u)
+                m[:, 2 + D:2 + 2 * D] = np.einsum("nm,tnm,tnmd->td", g, Ec, u)
+                m[:, 2 + 2 * D:2 + 3 * D] = np.einsum("nm,tnm,tnmd->td", g, Es, u)
             if env:
                 m[:, 2 + 3 * D:2 + 4 * D] = np.einsum("nm,tnm,tnmd->td", g, Ec, amid * amid)
                 m[:, 2 + 4 * D:2 + 5 * D] = np.einsum("nm,tnm,tnmd->td", g, Ec, amid)

@@ -1,10 +1,11 @@
 """
-Golden vectors of the product, cosine, constant and periodic kernels (tests/golden/product.npz, product_gram_[ab].npz,
-product_checkpoints.npz).  Runs only where the reference (GAMES-UChile/mogptk) is importable, like gen_stationary.py; the fixtures are data
-only.  The models come from tests/product_cases.py, built with the reference's `mogptk.gpr`.  Per case: inputs, targets, parameter names and constrained / raw values,
-K(X) (its packed lower triangle, in two files of their own: a committed file stays under 1 MiB), K(X, Xs), K_diag, LML, loss, the autograd
-gradient of every raw parameter, predict_f (diagonal and full), predict_y, and cond(K + s2 I) -- asserted below 1e5.  One case also records
-the loss trace of 20 Adam steps through Model.train.  Everything float64.  Re-run:  python tests/golden/gen_product.py [path to the reference]
+Golden vectors of a kernel family -- stationary, product or trend (tests/family_cases.py) -- in tests/golden/<family>.npz,
+<family>_gram_[ab].npz and <family>_checkpoints.npz.  Runs only where the reference (GAMES-UChile/mogptk) is importable, like gen_mean.py; the
+fixtures are data only.  The models come from tests/<family>_cases.py, built with the reference's `mogptk.gpr`.  Per case: inputs, targets,
+parameter names and constrained / raw values, K(X) (its packed lower triangle, in two files of their own: a committed file stays under
+1 MiB), K(X, Xs), K_diag, LML, loss, the autograd gradient of every raw parameter, predict_f (diagonal and full), predict_y, and
+cond(K + s2 I) -- asserted below 1e5.  One case also records the loss trace of 20 Adam steps through Model.train.  Everything float64.
+Re-run:  python tests/golden/gen_family.py <family> [path to the reference]
 """
 import os
 import sys
@@ -19,16 +20,17 @@ disp.HTML = lambda s: s
 ip.display = disp
 sys.modules["IPython"] = ip
 sys.modules["IPython.display"] = disp
-sys.path.insert(0, sys.argv[1] if len(sys.argv) > 1 else os.environ.get("MOGPTK_REFERENCE", "reference"))
+FAMILY = sys.argv[1]
+sys.path.insert(0, sys.argv[2] if len(sys.argv) > 2 else os.environ.get("MOGPTK_REFERENCE", "reference"))
 import torch                  # noqa: E402
 import mogptk                 # noqa: E402
-import product_cases as sc  # noqa: E402
+import family_cases           # noqa: E402
 
+sc = family_cases.cases(FAMILY)
 G = mogptk.gpr
 torch.set_default_dtype(torch.float64)
 N_ = lambda t: t.detach().cpu().numpy().astype(np.float64)
 T_ = lambda a: torch.tensor(np.asarray(a, dtype=np.float64))
-ADAM_CASE, ADAM_ITERS, ADAM_LR = sc.ADAM_CASE, sc.ADAM_ITERS, sc.ADAM_LR
 
 
 def main():
@@ -36,7 +38,7 @@ def main():
     for n, case in enumerate(sc.CASES):
         pre = case + "__"
         light = sc.CASES[case].get("light", False)
-        m = sc.exact(G, case)
+        m = family_cases.exact(FAMILY, G, case)
         X, y, Xs = sc.data(case)
         ps = list(m.parameters())
         out[pre + "names"] = np.array([p._name for p in ps])
@@ -50,6 +52,7 @@ def main():
         s2 = sc.NOISE
         cond = float(np.linalg.cond(K + s2 * np.eye(K.shape[0])))
         assert cond < 1e5, (case, cond)
+        assert all(np.all(np.isfinite(N_(p.grad))) for p in ps), case
         out[pre + "cond"] = np.array(cond)
         print("%-12s N = %4d  cond(K + s2 I) = %.3g  lml = %.6f" % (case, K.shape[0], cond, float(out[pre + "lml"])))
         if light:
@@ -66,16 +69,16 @@ def main():
         res = m.predict_y(Xs)
         out[pre + "ymu"], out[pre + "yvar"] = N_(res[0]), N_(res[1])
     # Model.train('Adam') on a case-1 model: the losses it records
-    X, y, _ = sc.data(ADAM_CASE)
-    mm = mogptk.Model(mogptk.DataSet(mogptk.Data(X[:, 0], y, name="a")), G.IndependentMultiOutputKernel(sc.kernel(G, ADAM_CASE), output_dims=1),
+    X, y, _ = sc.data(sc.ADAM_CASE)
+    mm = mogptk.Model(mogptk.DataSet(mogptk.Data(X[:, 0], y, name="a")), G.IndependentMultiOutputKernel(sc.kernel(G, sc.ADAM_CASE), output_dims=1),
                       inference=mogptk.Exact(variance=sc.NOISE))
-    losses, _ = mm.train(method="Adam", iters=ADAM_ITERS, lr=ADAM_LR, verbose=False)
+    losses, _ = mm.train(method="Adam", iters=sc.ADAM_ITERS, lr=sc.ADAM_LR, verbose=False)
     out["adam__losses"] = np.array(losses, dtype=np.float64)
     out["adam__final"] = np.concatenate([N_(p.data).reshape(-1) for p in mm.gpr.parameters()])
-    np.savez_compressed(os.path.join(HERE, "product.npz"), **out)
+    np.savez_compressed(os.path.join(HERE, FAMILY + ".npz"), **out)
     for tag, g in zip("ab", grams):
-        np.savez_compressed(os.path.join(HERE, "product_gram_%s.npz" % tag), **g)
-    for f in ("product.npz", "product_gram_a.npz", "product_gram_b.npz"):
+        np.savez_compressed(os.path.join(HERE, "%s_gram_%s.npz" % (FAMILY, tag)), **g)
+    for f in (FAMILY + ".npz", FAMILY + "_gram_a.npz", FAMILY + "_gram_b.npz"):
         size = os.path.getsize(os.path.join(HERE, f))
         assert size < 1 << 20, (f, size)
         print("wrote", f, size, "bytes")
@@ -83,7 +86,7 @@ def main():
 
 
 def gen_checkpoints():
-    """Files written by the reference's Model.save() with product, cosine, constant and periodic kernels inside AddKernel and LMC, stored as
+    """Files written by the reference's Model.save() with the family's kernels inside the compositions of `checkpoint_kernels`, stored as
     bytes next to what the reference computes on the loaded object (constrained values, loss, gradients, predictions)."""
     import tempfile
     rng = np.random.default_rng(91)
@@ -99,8 +102,10 @@ def gen_checkpoints():
         return ds
 
     def shake(k):
-        for p in k.parameters():
-            p.assign(rng.uniform(0.4, 1.2, tuple(p().shape)) if p().ndim else rng.uniform(0.4, 1.2))
+        for m in k.modules():                               # (torch modules: every kernel of the composition, each parameter once)
+            for name, p in m._parameters.items():
+                lo, hi = sc.shake_range(G, m, name)
+                p.assign(rng.uniform(lo, hi, tuple(p().shape)) if p().ndim else rng.uniform(lo, hi))
         return k
 
     def record(tag, model):
@@ -119,13 +124,12 @@ def gen_checkpoints():
         _, mu, _, _ = loaded.predict(transformed=False)
         out[tag + "_mu"] = np.concatenate([np.asarray(m).reshape(-1) for m in mu])
 
-    add = G.AddKernel(G.MulKernel(G.SquaredExponentialKernel(order=-1), G.CosineKernel()), G.LocallyPeriodicKernel(order=-1),
-                      G.MulKernel(G.ConstantKernel(), G.PeriodicKernel()))
-    record("mul", mogptk.Model(dataset(1, 40), G.IndependentMultiOutputKernel(shake(add), output_dims=1), inference=mogptk.Exact()))
-    lmc = G.LinearModelOfCoregionalizationKernel(G.MulKernel(G.MaternKernel(nu=1.5), G.CosineKernel()), G.ConstantKernel(), output_dims=2, Rq=2)
-    record("lmc", mogptk.Model(dataset(2, 30), shake(lmc), inference=mogptk.Exact()))
-    np.savez_compressed(os.path.join(HERE, "product_checkpoints.npz"), **out)
-    print("wrote product_checkpoints.npz", len(out), "arrays")
+    for tag, C, n, k in sc.checkpoint_kernels(G):           # data first, then the parameters: the order of the draws
+        ds = dataset(C, n)
+        k = shake(k)
+        record(tag, mogptk.Model(ds, G.IndependentMultiOutputKernel(k, output_dims=1) if C == 1 else k, inference=mogptk.Exact()))
+    np.savez_compressed(os.path.join(HERE, FAMILY + "_checkpoints.npz"), **out)
+    print("wrote %s_checkpoints.npz" % FAMILY, len(out), "arrays")
 
 
 if __name__ == "__main__":

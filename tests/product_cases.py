@@ -1,12 +1,15 @@
 """
-The models of tests/golden/product.npz, built the same way on either side: `G` is the reference's `mogptk.gpr` (tests/golden/gen_product.py)
-or this package's `mogptk_amd.gpr` (tests/test_product_*.py).  Only seeded numpy inputs go in.
+The models of tests/golden/product.npz, built the same way on either side: `G` is the reference's `mogptk.gpr` (tests/golden/gen_family.py)
+or this package's `mogptk_amd.gpr` (tests/test_product_*.py, tests/kernel_family.py).  Only seeded numpy inputs go in.
 
 Shapes as in stationary_cases.py: N = 150 is three 64-point tile rows with a ragged last one; two channels of 70 and 45 points give tiles
 that stop at a channel boundary; N = 1100 is the smallest size that takes the dataflow schedule.  Inputs over [0, 10], noise variance 0.1,
 magnitudes <= 1.4: the generator asserts cond(K + s2 I) < 1e5, so the exact model's accurate-mode repeat never engages.
 """
+from functools import partial
 import numpy as np
+import family_cases
+from family_cases import top
 
 NOISE = 0.1
 ADAM_CASE, ADAM_ITERS, ADAM_LR = "m32_cos", 20, 0.05
@@ -33,7 +36,6 @@ CASES = {
     # 4. the dataflow schedule: LML and gradients only
     "big": dict(kern="big", N=1100, light=True),
 }
-FULL_CASES = [c for c in CASES if not CASES[c].get("light")]
 PRODUCT_CASES = [c for c in CASES if c not in ("per", "cos", "const_se")]      # MulKernel or LocallyPeriodicKernel inside: product groups
 
 
@@ -87,34 +89,7 @@ def single(G, kern, D, rng):
     return k
 
 
-def parse(G, expr, D, rng):
-    """'a*b', 'a+b', '(a+b)*c' over the names of single()"""
-    def product(s):
-        fs, depth, cur = [], 0, ""
-        for chr_ in s:
-            depth += chr_ == "("
-            depth -= chr_ == ")"
-            if chr_ == "*" and depth == 0:
-                fs.append(cur); cur = ""
-            else:
-                cur += chr_
-        fs.append(cur)
-        ks = [total(f[1:-1]) if f.startswith("(") else single(G, f, D, rng) for f in fs]
-        return ks[0] if len(ks) == 1 else G.MulKernel(*ks)
-
-    def total(s):
-        parts, depth, cur = [], 0, ""
-        for chr_ in s:
-            depth += chr_ == "("
-            depth -= chr_ == ")"
-            if chr_ == "+" and depth == 0:
-                parts.append(cur); cur = ""
-            else:
-                cur += chr_
-        parts.append(cur)
-        ks = [product(p) for p in parts]
-        return ks[0] if len(ks) == 1 else G.AddKernel(*ks)
-    return total(expr)
+parse = partial(family_cases.parse, single)
 
 
 def kernel(G, case, seed=29):
@@ -140,12 +115,14 @@ def kernel(G, case, seed=29):
     return top(G, parse(G, kern, D, rng))
 
 
-def top(G, k):
-    """The reference's Exact adds the noise IN PLACE to what the kernel returns, and autograd needs the output of a product to differentiate
-    it: a MulKernel at the top of a model is wrapped in an AddKernel of one (same kernel, a fresh tensor) on both sides."""
-    return G.AddKernel(k) if isinstance(k, G.MulKernel) else k
+def checkpoint_kernels(G):
+    """(tag, channels, points per channel, kernel) of product_checkpoints.npz: product, cosine, constant and periodic kernels inside
+    AddKernel and LMC"""
+    return [("mul", 1, 40, G.AddKernel(G.MulKernel(G.SquaredExponentialKernel(order=-1), G.CosineKernel()), G.LocallyPeriodicKernel(order=-1),
+                                       G.MulKernel(G.ConstantKernel(), G.PeriodicKernel()))),
+            ("lmc", 2, 30, G.LinearModelOfCoregionalizationKernel(G.MulKernel(G.MaternKernel(nu=1.5), G.CosineKernel()), G.ConstantKernel(), output_dims=2, Rq=2))]
 
 
-def exact(G, case, **kw):
-    X, y, _ = data(case)
-    return G.Exact(kernel(G, case), X, y, variance=NOISE, **kw)
+def shake_range(G, module, name):
+    """the range a checkpoint model's parameter `name` of `module` is drawn from"""
+    return 0.4, 1.2

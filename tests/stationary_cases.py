@@ -1,6 +1,6 @@
 """
 The models of tests/golden/stationary.npz, built the same way on either side: `G` is the reference's `mogptk.gpr`
-(tests/golden/gen_stationary.py) or this package's `mogptk_amd.gpr` (tests/test_stationary_*.py).  Only seeded numpy inputs go in.
+(tests/golden/gen_family.py) or this package's `mogptk_amd.gpr` (tests/test_stationary_*.py, tests/kernel_family.py).  Only seeded numpy inputs go in.
 
 Shapes: N = 150 is three 64-point tile rows with a ragged last one (diagonal and off-diagonal tiles); two channels of 70 and 45 points give
 tiles that stop at a channel boundary; N = 1100 is the smallest size that takes the dataflow schedule.  Inputs over [0, 10], lengthscales
@@ -30,7 +30,6 @@ CASES = {
     # 4. the dataflow schedule: LML and gradients only
     "big":   dict(kern="big", N=1100, light=True),
 }
-FULL_CASES = [c for c in CASES if not CASES[c].get("light")]
 
 
 def data(case, seed=5):
@@ -98,6 +97,14 @@ def kernel(G, case, seed=23):
     return _single(G, kern, D, rng)
 
 
-def exact(G, case, **kw):
-    X, y, _ = data(case)
-    return G.Exact(kernel(G, case), X, y, variance=NOISE, **kw)
+def checkpoint_kernels(G):
+    """(tag, channels, points per channel, kernel) of stationary_checkpoints.npz: the four kernels inside AddKernel,
+    IndependentMultiOutputKernel and LMC"""
+    return [("add", 1, 40, G.AddKernel(G.SquaredExponentialKernel(order=-1), G.MaternKernel(nu=1.5), G.RationalQuadraticKernel(alpha=0.7), G.ExponentialKernel())),
+            ("imo", 2, 30, G.IndependentMultiOutputKernel(G.RationalQuadraticKernel(alpha=1.3), G.MaternKernel(nu=2.5), output_dims=2)),
+            ("lmc", 2, 30, G.LinearModelOfCoregionalizationKernel(G.SquaredExponentialKernel(), G.ExponentialKernel(), G.MaternKernel(nu=0.5), output_dims=2, Rq=2))]
+
+
+def shake_range(G, module, name):
+    """the range a checkpoint model's parameter `name` of `module` is drawn from"""
+    return 0.4, 1.2

@@ -1,87 +1,25 @@
 """
 Host side of the product kernels and of ConstantKernel, CosineKernel, PeriodicKernel and LocallyPeriodicKernel, without a device:
-tables, kinds and group flags of every case of tests/product_cases.py against hand-written expectations; a numpy evaluator of the grouped
-table form against the reference's K / K_diag (tests/golden/product.npz, written by tests/golden/gen_product.py); the chain rule through
-MulKernel against finite differences of that evaluator and against the reference's autograd; the refusals; checkpoints.
+tables, kinds and group flags of every case of tests/product_cases.py against hand-written expectations; the grouped table form through
+the numpy twin of the device handle (oracle/table_model.py) against the reference's K / K_diag (tests/golden/product.npz, written by
+tests/golden/gen_family.py); the chain rule through MulKernel against finite differences of the twin's Gram and against the reference's
+autograd; the refusals; checkpoints.  The bodies shared with the other kernel families are in tests/kernel_family.py.
 """
-import io
 import os
 import numpy as np
 import pytest
 
-import mogptk_amd
 from mogptk_amd import gpr, _lib
-from mogptk_amd.gpr.kernel import KIND_TIMES, KIND_MASK, group_slices
+from mogptk_amd.gpr.kernel import KIND_TIMES
 from mogptk_amd.gpr.model import _gtable_from_moments
 import product_cases as pc
-from helpers import load
-from test_stationary_cpu import profiles, with_reference_raw, NumpyDevice
+import kernel_family as kf
+from family_cases import exact, full_cases
+from oracle.table_model import gram_from_table, moments_dense
 
+FAMILY = "product"
 X_ = KIND_TIMES
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def golden_K(case):
-    for tag in "ab":
-        fx = load("product_gram_%s.npz" % tag)
-        if case + "__K_tril" in fx:
-            tril = fx[case + "__K_tril"]
-            n = int(round((np.sqrt(8 * len(tril) + 1) - 1) / 2))
-            K = np.zeros((n, n))
-            K[np.tril_indices(n)] = tril
-            return K + np.tril(K, -1).T
-    raise KeyError(case)
-
-
-def row_parts(row, kind, shape, u):
-    """value k (unit amplitude) of one table row at the lags u (na, nb, D), and the integrands of its moments [m0, m4, m1_d, m2_d, m3_d]"""
-    D = u.shape[2]
-    Psi, V, M = row[1], row[2:2 + D], row[2 + D:2 + 2 * D]
-    th = 2.0 * np.pi * (np.sum(M * u, axis=2) + Psi)
-    if kind == 5:                                           # E = exp(V (cos - 1)): the phase is the profile's argument
-        E = np.exp(V[0] * (np.cos(th) - 1.0))
-        return E, [E, E * V[0] * np.sin(th), E * 2.0 * (1.0 - np.cos(th)), 0.0 * E, E * V[0] * u[..., 0] * np.sin(th)]
-    phi, psi = profiles(kind, shape, np.sum(V * u * u, axis=2))
-    parts = [phi * np.cos(th), phi * np.sin(th)]
-    parts += [u[..., d] ** 2 * psi * np.cos(th) for d in range(D)] + [u[..., d] * psi * np.cos(th) for d in range(D)]
-    parts += [u[..., d] * phi * np.sin(th) for d in range(D)]
-    return phi * np.cos(th), parts
-
-
-def evaluate(table, kind, shape, Xa, Xb, G=None):
-    """K(Xa, Xb) of a term table with kinds and product groups; with an adjoint G also the moments of every ordered channel pair: row f of a
-    group sees G weighted by the product of the group's other rows"""
-    C, T, D = table.shape[0], table.shape[2], Xa.shape[1] - 1
-    ca, cb = Xa[:, 0].astype(int), Xb[:, 0].astype(int)
-    K = np.zeros((len(Xa), len(Xb)))
-    mom = np.zeros((C, C, T, 2 + 3 * D))
-    for i in range(C):
-        for j in range(C):
-            ia, ib = np.where(ca == i)[0], np.where(cb == j)[0]
-            rows = []
-            for t in range(T):
-                u = Xa[ia, None, 1:] - Xb[None, ib, 1:] + table[i, j, t, 2 + 2 * D:2 + 3 * D]
-                rows.append(row_parts(table[i, j, t], int(kind[i, j, t]) & KIND_MASK, shape[i, j, t], u))
-            for a, b in group_slices(kind[i, j]):
-                vals = [table[i, j, t, 0] * rows[t][0] for t in range(a, b)]
-                K[np.ix_(ia, ib)] += np.prod(vals, axis=0)
-                if G is not None:
-                    for t in range(a, b):
-                        w = G[np.ix_(ia, ib)] * np.prod([v for h, v in enumerate(vals) if h != t - a] + [np.ones_like(vals[0])], axis=0)
-                        mom[i, j, t] = [np.sum(w * part) for part in rows[t][1]]
-    return K, mom
-
-
-class GroupDevice(NumpyDevice):
-    """test_stationary_cpu.NumpyDevice over the grouped evaluator"""
-
-    def eval(self, noise_var, jitter, grad=True, data_var=None):
-        import test_stationary_cpu as ts
-        saved, ts.evaluate = ts.evaluate, evaluate
-        try:
-            return super().eval(noise_var, jitter, grad=grad, data_var=data_var)
-        finally:
-            ts.evaluate = saved
 
 
 def kinds_of(case):
@@ -160,46 +98,19 @@ def test_independent_kernels_with_different_groups_get_rows_of_their_own():
     assert k.kernels[1].magnitude.grad is not None and k.kernels[0].kernels[1].magnitude.grad is not None
 
 
-@pytest.mark.parametrize("case", pc.FULL_CASES)
+@pytest.mark.parametrize("case", full_cases(FAMILY))
 def test_table_and_kinds_reproduce_the_reference_gram(case):
-    fx = load("product.npz")
-    m = pc.exact(gpr, case)
-    with_reference_raw(m, fx, case + "__")
-    k = m.kernel
-    X, Xs = k._kernel_format(fx[case + "__X"]), k._kernel_format(fx[case + "__Xs"])
-    D = X.shape[1] - 1
-    table = k._spectral_terms(D)
-    kind, shape = k._spectral_kinds(D)
-    assert kind.shape == table.shape[:3] == shape.shape and shape.dtype == np.float64
-    want = golden_K(case)
-    K, _ = evaluate(table, kind, shape, X, X)
-    assert np.max(np.abs(K - want)) <= 1e-12 * max(1.0, np.max(np.abs(want)))
-    K12, _ = evaluate(table, kind, shape, X, Xs)
-    assert np.max(np.abs(K12 - fx[case + "__K12"])) <= 1e-12 * max(1.0, np.max(np.abs(want)))
-    kd = k.K_diag(fx[case + "__X"])
-    assert np.max(np.abs(kd - fx[case + "__Kdiag"])) <= 1e-12 * max(1.0, np.max(np.abs(want)))
-    assert np.max(np.abs(np.diag(K) - kd)) <= 1e-12 * max(1.0, np.max(np.abs(want)))      # what the library's relative jitter takes: sum over groups of prod A
+    kf.check_table_and_kinds(FAMILY, case)
 
 
-@pytest.mark.parametrize("case", pc.FULL_CASES)
+@pytest.mark.parametrize("case", full_cases(FAMILY))
 def test_chain_rule_reproduces_reference_gradients(case, monkeypatch):
-    """gpr.Exact's own loss path (table push, kinds, moments -> table gradient -> _spectral_backward, the jitter term over groups) over the
-    numpy device"""
-    fx = load("product.npz")
-    monkeypatch.setattr(_lib, "ExactHandle", GroupDevice)
-    m = pc.exact(gpr, case)
-    ps = with_reference_raw(m, fx, case + "__")
-    loss = float(m.loss())
-    assert abs(loss - float(fx[case + "__loss"])) <= 1e-9 * max(1.0, abs(float(fx[case + "__loss"])))
-    assert (m._handle.kind is not None) == m.kernel._radial(m._handle.D)
-    for i, p in enumerate(ps):
-        g = fx["%s__p%d_grad" % (case, i)]
-        assert np.max(np.abs(p.grad - g)) <= 1e-9 * max(1.0, np.max(np.abs(g))), (p._name, p.grad, g)
+    kf.check_chain_rule(FAMILY, case, monkeypatch)
 
 
 @pytest.mark.parametrize("expr", ["(se+m52)*cos", "se*cos*per", "locper*const", "(se+rq)*(cos+per)"])
 def test_mulkernel_backward_against_finite_differences(expr):
-    """f(raw parameters) = sum_ab G_ab K_ab with K evaluated from the table form in numpy; its gradient through the moments, the host formulas
+    """f(raw parameters) = sum_ab G_ab K_ab with K evaluated from the table form by the twin; its gradient through the moments, the host formulas
     and MulKernel._spectral_backward against central differences"""
     rng = np.random.default_rng(11)
     k = pc.parse(gpr, expr, 1, rng)
@@ -207,10 +118,10 @@ def test_mulkernel_backward_against_finite_differences(expr):
     G = rng.standard_normal((25, 25))
 
     def f():
-        return float(np.sum(G * evaluate(k._spectral_terms(1), *k._spectral_kinds(1), X, X)[0]))
+        return float(np.sum(G * gram_from_table(k._spectral_terms(1), X, X, *k._spectral_kinds(1))))
 
     table = k._spectral_terms(1)
-    _, mom = evaluate(table, *k._spectral_kinds(1), X, X, G)
+    mom = moments_dense(table, G, X, X, False, *k._spectral_kinds(1))      # one channel: its one ordered pair is its one lower pair
     for p in k.parameters():
         p.grad = None
     k._spectral_backward(_gtable_from_moments(table, mom.reshape(1, -1, 5), 1, lower=True))
@@ -284,7 +195,7 @@ def test_refusals_come_before_any_device_call(monkeypatch):
     saved = getattr(gpr.config, "comm", None)
     gpr.config.comm = Comm()
     try:
-        m = pc.exact(gpr, "m32_cos")
+        m = exact(FAMILY, gpr, "m32_cos")
         with pytest.raises(NotImplementedError, match="product kernels.*use_distributed"):
             m.loss()
         assert m._handle is None
@@ -309,28 +220,9 @@ CHECKPOINTS = ("mul", "lmc")
 @pytest.mark.parametrize("tag", CHECKPOINTS)
 def test_reference_checkpoint_round_trip(tag, tmp_path):
     pytest.importorskip("torch")
-    from mogptk_amd import compat
-    from test_host_logic import _checkpoint_tree, _tree_differences
-    fx = load("product_checkpoints.npz")
-    raw = fx[tag + "_file"].tobytes()
-    (tmp_path / "ref.npy").write_bytes(raw)
-    m = mogptk_amd.LoadModel(str(tmp_path / "ref"))
-    ps = list(m.gpr.parameters())
-    assert [p._name for p in ps] == [str(n) for n in fx[tag + "_names"]]
-    for i, p in enumerate(ps):
-        ref = fx["%s_p%d" % (tag, i)]
-        assert np.asarray(p()).shape == ref.shape and np.max(np.abs(np.asarray(p()) - ref)) <= 1e-12 * max(1.0, np.max(np.abs(ref))), p._name
-
-    def leaves_of(k):
-        return [n for s in k.kernels for n in leaves_of(s)] + [type(k).__name__] if getattr(k, "kernels", None) else [type(k).__name__]
+    k = kf.check_checkpoint_loads(FAMILY, tag, tmp_path)
     want = dict(mul={"MulKernel", "CosineKernel", "LocallyPeriodicKernel", "ConstantKernel", "PeriodicKernel"}, lmc={"MulKernel", "CosineKernel", "ConstantKernel"})[tag]
-    assert want <= set(leaves_of(m.gpr.kernel))
+    assert want <= set(kf.kernel_names(k))
     if tag == "mul":
-        assert m.gpr.kernel.kernels[0].kernels[1].order == -1
-    written = compat.dump_reference_model(compat.load_reference_model(raw))
-    assert compat.is_reference_checkpoint(written)
-    theirs = _checkpoint_tree(compat._Unpickler(io.BytesIO(raw)).load(), {})
-    ours = _checkpoint_tree(compat._Unpickler(io.BytesIO(written)).load(), {})
-    out = []
-    _tree_differences(theirs, ours, tag, out)
-    assert not out, out[:5]
+        assert k.kernels[0].kernels[1].order == -1
+    kf.check_checkpoint_is_written_as_the_reference_writes_it(FAMILY, tag)

@@ -1,121 +1,20 @@
 """
 Host side of the stationary kernels (SquaredExponential, RationalQuadratic, Matern, Exponential), without a device: the class
-surface against the reference's, the term table and kinds against a numpy evaluator of the radial form and the reference's K / K_diag
-(tests/golden/stationary.npz, written by tests/golden/gen_stationary.py from the models of tests/stationary_cases.py), the chain rule
-against the reference's autograd with the moments taken from that evaluator, the combinations that are refused, and checkpoints.
+surface against the reference's, the term table and kinds through the numpy twin of the device handle (oracle/table_model.py) against the
+reference's K / K_diag (tests/golden/stationary.npz, written by tests/golden/gen_family.py from the models of tests/stationary_cases.py),
+the chain rule against the reference's autograd with the moments taken from that twin, the combinations that are refused, and checkpoints.
+The bodies shared with the other kernel families are in tests/kernel_family.py.
 """
-import io
 import numpy as np
 import pytest
 
-import mogptk_amd
 from mogptk_amd import gpr, _lib
 import stationary_cases as sc
+import kernel_family as kf
+from family_cases import exact, full_cases
 from helpers import load
 
-SQ3, SQ5 = np.sqrt(3.0), np.sqrt(5.0)
-
-
-def golden_K(case):
-    for tag in "ab":
-        fx = load("stationary_gram_%s.npz" % tag)
-        if case + "__K_tril" in fx:
-            tril = fx[case + "__K_tril"]
-            n = int(round((np.sqrt(8 * len(tril) + 1) - 1) / 2))
-            K = np.zeros((n, n))
-            K[np.tril_indices(n)] = tril
-            return K + np.tril(K, -1).T
-    raise KeyError(case)
-
-
-def profiles(kind, shape, s):
-    """phi(s) and psi(s) = -2 dphi/ds of DESIGN 1b; u psi and u^2 psi are 0 where Matern 1/2 has r = 0, so psi is returned as 0 there"""
-    r = np.sqrt(s)
-    if kind == 1:
-        b = 1.0 + s / (2.0 * shape)
-        return b ** -shape, b ** (-shape - 1.0)
-    if kind == 2:
-        return np.exp(-r), np.where(r > 0, np.exp(-r) / np.where(r > 0, r, 1.0), 0.0)
-    if kind == 3:
-        return (1.0 + SQ3 * r) * np.exp(-SQ3 * r), 3.0 * np.exp(-SQ3 * r)
-    if kind == 4:
-        return (1.0 + SQ5 * r + 5.0 * s / 3.0) * np.exp(-SQ5 * r), (5.0 / 3.0) * (1.0 + SQ5 * r) * np.exp(-SQ5 * r)
-    return np.exp(-0.5 * s), np.exp(-0.5 * s)
-
-
-def evaluate(table, kind, shape, Xa, Xb, G=None):
-    """K(Xa, Xb) of a term table with kinds (inputs with the channel in column 0); with an adjoint G also the moments
-    [m0, m4, m1_d, m2_d, m3_d] of every ordered channel pair, (C, C, T, 2 + 3 D)"""
-    C, T, D = table.shape[0], table.shape[2], Xa.shape[1] - 1
-    ca, cb = Xa[:, 0].astype(int), Xb[:, 0].astype(int)
-    K = np.zeros((len(Xa), len(Xb)))
-    mom = np.zeros((C, C, T, 2 + 3 * D))
-    for i in range(C):
-        for j in range(C):
-            ia, ib = np.where(ca == i)[0], np.where(cb == j)[0]
-            for t in range(T):
-                A, Psi = table[i, j, t, 0], table[i, j, t, 1]
-                V, M, Dl = table[i, j, t, 2:2 + D], table[i, j, t, 2 + D:2 + 2 * D], table[i, j, t, 2 + 2 * D:2 + 3 * D]
-                u = Xa[ia, None, 1:] - Xb[None, ib, 1:] + Dl
-                phi, psi = profiles(kind[i, j, t], shape[i, j, t], np.sum(V * u * u, axis=2))
-                ph = 2.0 * np.pi * (np.sum(M * u, axis=2) + Psi)
-                K[np.ix_(ia, ib)] += A * phi * np.cos(ph)
-                if G is not None:
-                    g = G[np.ix_(ia, ib)]
-                    mom[i, j, t, 0], mom[i, j, t, 1] = np.sum(g * phi * np.cos(ph)), np.sum(g * phi * np.sin(ph))
-                    for d in range(D):
-                        mom[i, j, t, 2 + d] = np.sum(g * u[..., d] ** 2 * psi * np.cos(ph))
-                        mom[i, j, t, 2 + D + d] = np.sum(g * u[..., d] * psi * np.cos(ph))
-                        mom[i, j, t, 2 + 2 * D + d] = np.sum(g * u[..., d] * phi * np.sin(ph))
-    return K, mom
-
-
-class NumpyDevice:
-    """what gpr.Exact asks of its device handle for a loss evaluation, answered by the evaluator above (symmetric sums over the full matrix:
-    off-diagonal channel blocks count twice, the odd moments of a diagonal block are zero)"""
-
-    def __init__(self, device, X, y, C):
-        self.X, self.y, self.C, self.D = np.asarray(X, dtype=np.float64), np.asarray(y, dtype=np.float64).reshape(-1), C, X.shape[1] - 1
-        self.kind = None
-
-    def set_terms(self, table):
-        self.table, self.T, self.W, self.kind = np.array(table), table.shape[2], table.shape[3], None
-
-    def set_kinds(self, kind, shape):
-        self.kind, self.shape = kind, shape
-
-    def eval(self, noise_var, jitter, grad=True, data_var=None):
-        C, N = self.C, len(self.y)
-        kind = np.zeros(self.table.shape[:3], dtype=int) if self.kind is None else self.kind
-        shape = np.zeros(self.table.shape[:3]) if self.kind is None else self.shape
-        K, _ = evaluate(self.table, kind, shape, self.X, self.X)
-        ch = self.X[:, 0].astype(int)
-        jabs = jitter * np.mean(np.diag(K) + noise_var[ch])
-        Kj = K + np.diag(noise_var[ch]) + jabs * np.eye(N)
-        L = np.linalg.cholesky(Kj)
-        alpha = np.linalg.solve(Kj, self.y)
-        lml = -0.5 * N * np.log(2.0 * np.pi) - np.sum(np.log(np.diag(L))) - 0.5 * self.y @ alpha
-        Gm = 0.5 * (np.outer(alpha, alpha) - np.linalg.inv(Kj))
-        _, full = evaluate(self.table, kind, shape, self.X, self.X, Gm)
-        D = self.D
-        mom = np.zeros((C * (C + 1) // 2, self.T, self.W))
-        for i in range(C):
-            for j in range(i + 1):
-                mom[i * (i + 1) // 2 + j] = full[i, j] if i == j else 2.0 * full[i, j]
-                if i == j:
-                    mom[i * (i + 1) // 2 + j][:, 1] = 0.0
-                    mom[i * (i + 1) // 2 + j][:, 2 + D:2 + 2 * D] = 0.0
-        diagG = np.array([np.sum(np.diag(Gm)[ch == c]) for c in range(C)])
-        return dict(lml=lml, moments=mom, diagG=diagG, trG=float(np.sum(diagG)), jitter_abs=jabs)
-
-
-def with_reference_raw(m, fx, pre):
-    ps = list(m.parameters())
-    assert [p._name for p in ps] == [str(n) for n in fx[pre + "names"]]
-    for i, p in enumerate(ps):
-        assert p.data.shape == fx["%sp%d_raw" % (pre, i)].shape, p._name
-        p.data = np.array(fx["%sp%d_raw" % (pre, i)], dtype=p.data.dtype)
-    return ps
+FAMILY = "stationary"
 
 
 def test_class_surface_matches_the_reference():
@@ -144,8 +43,8 @@ def test_class_surface_matches_the_reference():
 @pytest.mark.parametrize("case", list(sc.CASES))
 def test_parameter_order_and_printing_match_the_reference(case, capsys):
     fx = load("stationary.npz")
-    m = sc.exact(gpr, case)
-    ps = with_reference_raw(m, fx, case + "__")
+    m = exact(FAMILY, gpr, case)
+    ps = kf.with_reference_raw(m, fx, case + "__")
     for i, p in enumerate(ps):
         ref = fx["%s__p%d_cons" % (case, i)]
         assert np.max(np.abs(np.asarray(p()) - ref)) <= 1e-14 * max(1.0, np.max(np.abs(ref))), p._name
@@ -154,25 +53,11 @@ def test_parameter_order_and_printing_match_the_reference(case, capsys):
     assert [ln.split()[0] for ln in lines] == [str(n) for n in fx[case + "__names"]]
 
 
-@pytest.mark.parametrize("case", sc.FULL_CASES)
+@pytest.mark.parametrize("case", full_cases(FAMILY))
 def test_table_and_kinds_reproduce_the_reference_gram(case):
-    fx = load("stationary.npz")
-    m = sc.exact(gpr, case)
-    with_reference_raw(m, fx, case + "__")
-    k = m.kernel
-    X, Xs = k._kernel_format(fx[case + "__X"]), k._kernel_format(fx[case + "__Xs"])
-    D = X.shape[1] - 1
-    table = k._spectral_terms(D)
-    kind, shape = k._spectral_kinds(D)
-    assert kind.shape == table.shape[:3] == shape.shape and kind.dtype == np.int32 and shape.dtype == np.float64
+    _, table, kind, _, _, _, _, _ = kf.check_table_and_kinds(FAMILY, case)
+    assert kind.dtype == np.int32
     assert np.all(kind[table[..., 0] == 0.0] == 0)             # padding rows are Gaussian
-    want = golden_K(case)
-    K, _ = evaluate(table, kind, shape, X, X)
-    assert np.max(np.abs(K - want)) <= 1e-12 * max(1.0, np.max(np.abs(want)))
-    K12, _ = evaluate(table, kind, shape, X, Xs)
-    assert np.max(np.abs(K12 - fx[case + "__K12"])) <= 1e-12 * max(1.0, np.max(np.abs(want)))
-    kd = k.K_diag(fx[case + "__X"])
-    assert np.max(np.abs(kd - fx[case + "__Kdiag"])) <= 1e-12 * max(1.0, np.max(np.abs(want)))
 
 
 def test_kinds_of_the_cases():
@@ -189,19 +74,9 @@ def test_kinds_of_the_cases():
     assert mix._spectral_kinds(1)[0][0, 0].tolist() == [4, 4, 4]
 
 
-@pytest.mark.parametrize("case", sc.FULL_CASES)
+@pytest.mark.parametrize("case", full_cases(FAMILY))
 def test_chain_rule_reproduces_reference_gradients(case, monkeypatch):
-    """gpr.Exact's own loss path (table push, kinds, moments -> table gradient -> _spectral_backward) over the numpy device"""
-    fx = load("stationary.npz")
-    monkeypatch.setattr(_lib, "ExactHandle", NumpyDevice)
-    m = sc.exact(gpr, case)
-    ps = with_reference_raw(m, fx, case + "__")
-    loss = float(m.loss())
-    assert abs(loss - float(fx[case + "__loss"])) <= 1e-9 * max(1.0, abs(float(fx[case + "__loss"])))
-    assert (m._handle.kind is not None) == m.kernel._radial(m._handle.D)      # kinds travel only when some kind is non-zero
-    for i, p in enumerate(ps):
-        g = fx["%s__p%d_grad" % (case, i)]
-        assert np.max(np.abs(p.grad - g)) <= 1e-9 * max(1.0, np.max(np.abs(g))), (p._name, p.grad, g)
+    kf.check_chain_rule(FAMILY, case, monkeypatch)
 
 
 def test_refusals_come_before_any_device_call(monkeypatch):
@@ -235,7 +110,7 @@ def test_refusals_come_before_any_device_call(monkeypatch):
     saved = getattr(gpr.config, "comm", None)
     gpr.config.comm = Comm()
     try:
-        m = sc.exact(gpr, "m32")
+        m = exact(FAMILY, gpr, "m32")
         with pytest.raises(NotImplementedError, match="use_distributed"):
             m.loss()
         with pytest.raises(NotImplementedError, match="use_distributed"):
@@ -251,42 +126,22 @@ CHECKPOINTS = ("add", "imo", "lmc")
 @pytest.mark.parametrize("tag", CHECKPOINTS)
 def test_reference_checkpoint_loads(tag, tmp_path):
     pytest.importorskip("torch")
-    fx = load("stationary_checkpoints.npz")
-    (tmp_path / "ref.npy").write_bytes(fx[tag + "_file"].tobytes())
-    m = mogptk_amd.LoadModel(str(tmp_path / "ref"))
-    ps = list(m.gpr.parameters())
-    assert [p._name for p in ps] == [str(n) for n in fx[tag + "_names"]]
-    for i, p in enumerate(ps):
-        ref = fx["%s_p%d" % (tag, i)]
-        assert np.asarray(p()).shape == ref.shape
-        assert np.max(np.abs(np.asarray(p()) - ref)) <= 1e-12 * max(1.0, np.max(np.abs(ref))), p._name
-    def leaves_of(k):
-        return [n for s in k.kernels for n in leaves_of(s)] if getattr(k, "kernels", None) else [type(k).__name__]
-    leaves = leaves_of(m.gpr.kernel)
+    k = kf.check_checkpoint_loads(FAMILY, tag, tmp_path)
     want = dict(add={"SquaredExponentialKernel", "MaternKernel", "RationalQuadraticKernel", "ExponentialKernel"},
                 imo={"RationalQuadraticKernel", "MaternKernel"}, lmc={"SquaredExponentialKernel", "ExponentialKernel", "MaternKernel"})[tag]
-    assert want <= set(leaves), leaves
+    assert want <= set(kf.kernel_names(k))
     if tag == "add":
-        add = m.gpr.kernel.kernels[0]
+        add = k.kernels[0]
         assert add.kernels[0].order == -1 and add.kernels[1].nu == 1.5 and add.kernels[2].alpha == 0.7
     if tag == "imo":
-        assert m.gpr.kernel.kernels[0].alpha == 1.3 and m.gpr.kernel.kernels[1].nu == 2.5
+        assert k.kernels[0].alpha == 1.3 and k.kernels[1].nu == 2.5
 
 
 @pytest.mark.parametrize("tag", CHECKPOINTS)
 def test_reference_checkpoint_is_written_as_the_reference_writes_it(tag):
     pytest.importorskip("torch")
     from mogptk_amd import compat
-    from test_host_logic import _checkpoint_tree, _tree_differences
-    fx = load("stationary_checkpoints.npz")
-    raw = fx[tag + "_file"].tobytes()
-    written = compat.dump_reference_model(compat.load_reference_model(raw))
-    assert compat.is_reference_checkpoint(written)
-    theirs = _checkpoint_tree(compat._Unpickler(io.BytesIO(raw)).load(), {})
-    ours = _checkpoint_tree(compat._Unpickler(io.BytesIO(written)).load(), {})
-    out = []
-    _tree_differences(theirs, ours, tag, out)
-    assert not out, out[:5]
+    written, fx = kf.check_checkpoint_is_written_as_the_reference_writes_it(FAMILY, tag)
     m = compat.load_reference_model(written)
     for i, p in enumerate(m.gpr.parameters()):
         assert np.max(np.abs(np.asarray(p()) - fx["%s_p%d" % (tag, i)])) <= 1e-12 * max(1.0, np.max(np.abs(fx["%s_p%d" % (tag, i)])))

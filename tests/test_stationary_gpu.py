@@ -1,124 +1,49 @@
 """
 The stationary kernels on the device (csrc/gram.hip: the radial instantiations of the general Gram and moment kernels) against the
-reference (tests/golden/stationary.npz, written by tests/golden/gen_stationary.py from the models of tests/stationary_cases.py): Gram
+reference (tests/golden/stationary.npz, written by tests/golden/gen_family.py from the models of tests/stationary_cases.py): Gram
 matrices, LML, loss, every raw gradient, predictions, both schedules of the smallest dataflow size, bitwise repeatability, a short Adam
-trace, and bitwise neutrality of an all-Gaussian kinds call.  Tolerances: DESIGN 8, relative to max(1, max |want|).
+trace, and bitwise neutrality of an all-Gaussian kinds call.  The bodies, shared with the other kernel families, and the tolerances are in
+tests/kernel_family.py.
 """
-import os
 import numpy as np
 import pytest
 
 import mogptk_amd
 from mogptk_amd import gpr
-import stationary_cases as sc
+import kernel_family as kf
+from family_cases import exact, full_cases
 from helpers import load
-from test_stationary_cpu import golden_K, with_reference_raw
 
 pytestmark = pytest.mark.gpu
+FAMILY = "stationary"
 
 
-def err(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    assert a.shape == b.shape, (a.shape, b.shape)
-    return np.max(np.abs(a - b)) / max(1.0, np.max(np.abs(b)))
-
-
-def check_value_and_gradients(m, fx, pre):
-    ps = with_reference_raw(m, fx, pre)
-    lml = float(m.log_marginal_likelihood())
-    e = err(lml, float(fx[pre + "lml"]))
-    print(pre, "lml", e)
-    assert e <= 1e-9, (lml, float(fx[pre + "lml"]))
-    loss = float(m.loss())
-    e = err(loss, float(fx[pre + "loss"]))
-    print(pre, "loss", e)
-    assert e <= 1e-9
-    for i, p in enumerate(ps):
-        e = err(p.grad, fx["%sp%d_grad" % (pre, i)])
-        print(pre, p._name, "grad", e)
-        assert e <= 1e-7, (p._name, p.grad, fx["%sp%d_grad" % (pre, i)])
-
-
-@pytest.mark.parametrize("case", sc.FULL_CASES)
+@pytest.mark.parametrize("case", full_cases(FAMILY))
 def test_gram_matrices_match_the_reference(case):
-    fx = load("stationary.npz")
-    pre = case + "__"
-    m = sc.exact(gpr, case)
-    with_reference_raw(m, fx, pre)
-    X, Xs = fx[pre + "X"], fx[pre + "Xs"]
-    for name, got, want in (("K", m.kernel(X), golden_K(case)), ("K12", m.kernel(X, Xs), fx[pre + "K12"]), ("Kdiag", m.kernel.K_diag(X), fx[pre + "Kdiag"])):
-        e = err(got, want)
-        print(pre, name, e)
-        assert e <= 1e-12, name
+    kf.check_gram_matrices(FAMILY, case)
 
 
-@pytest.mark.parametrize("case", sc.FULL_CASES)
+@pytest.mark.parametrize("case", full_cases(FAMILY))
 def test_lml_loss_and_every_gradient_match_reference_autograd(case):
-    check_value_and_gradients(sc.exact(gpr, case), load("stationary.npz"), case + "__")
+    kf.check_value_and_gradients(exact(FAMILY, gpr, case), load(FAMILY + ".npz"), case + "__")
 
 
-@pytest.mark.parametrize("case", sc.FULL_CASES)
+@pytest.mark.parametrize("case", full_cases(FAMILY))
 def test_predictions_match_the_reference(case):
-    fx = load("stationary.npz")
-    pre = case + "__"
-    m = sc.exact(gpr, case)
-    with_reference_raw(m, fx, pre)
-    Xs = fx[pre + "Xs"]
-    mu, var = m.predict_f(Xs)
-    mu2, cov = m.predict_f(Xs, full=True)
-    ymu, yvar = m.predict_y(Xs)[:2]
-    for name, got, want in (("mu", mu, fx[pre + "mu"]), ("var", var, fx[pre + "var"]), ("mu(full)", mu2, fx[pre + "mu"]), ("cov", cov, fx[pre + "cov"]),
-                            ("ymu", ymu, fx[pre + "ymu"]), ("yvar", yvar, fx[pre + "yvar"])):
-        e = err(np.asarray(got).reshape(np.shape(want)), want)
-        print(pre, name, e)
-        assert e <= 1e-9, name
+    kf.check_predictions(FAMILY, case)
 
 
 def test_dataflow_size_under_both_schedules():
-    """N = 1100: nine 128-row tiles, the Gram build split into its head and tail launches; MOGP_FLOW is read per evaluation"""
-    fx = load("stationary.npz")
-    old = {k: os.environ.get(k) for k in ("MOGP_FLOW", "MOGP_FLOW_MIN")}
-    try:
-        os.environ.pop("MOGP_FLOW", None); os.environ.pop("MOGP_FLOW_MIN", None)
-        m = sc.exact(gpr, "big")
-        check_value_and_gradients(m, fx, "big__")
-        assert m._handle.schedule()["dataflow"], m._handle.schedule()
-        os.environ["MOGP_FLOW"] = "0"
-        m = sc.exact(gpr, "big")
-        check_value_and_gradients(m, fx, "big__")
-        assert not m._handle.schedule()["dataflow"]
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
+    kf.check_both_schedules(FAMILY)
 
 
 @pytest.mark.parametrize("case", ["imo", "lmc"])
 def test_repeated_gradient_evaluations_are_bit_identical(case):
-    fx = load("stationary.npz")
-    m = sc.exact(gpr, case)
-    ps = with_reference_raw(m, fx, case + "__")
-    first = None
-    for _ in range(30):
-        loss = float(m.loss())
-        got = [np.float64(loss).tobytes()] + [p.grad.tobytes() for p in ps]
-        if first is None:
-            first = got
-        assert got == first
+    kf.check_bit_identical_repeats(FAMILY, case)
 
 
 def test_adam_trace_through_model_train():
-    fx = load("stationary.npz")
-    ADAM_CASE, ADAM_ITERS, ADAM_LR = sc.ADAM_CASE, sc.ADAM_ITERS, sc.ADAM_LR
-    X, y, _ = sc.data(ADAM_CASE)
-    mm = mogptk_amd.Model(mogptk_amd.DataSet(mogptk_amd.Data(X[:, 0], y, name="a")),
-                          gpr.IndependentMultiOutputKernel(sc.kernel(gpr, ADAM_CASE), output_dims=1), inference=mogptk_amd.Exact(variance=sc.NOISE))
-    losses, _ = mm.train(method="Adam", iters=ADAM_ITERS, lr=ADAM_LR, verbose=False)
-    want = fx["adam__losses"]
-    e = err(np.asarray(losses, dtype=np.float64), want)
-    print("adam trace", e)
-    assert e <= 1e-7
-    final = np.concatenate([np.asarray(p.data, dtype=np.float64).reshape(-1) for p in mm.gpr.parameters()])
-    assert err(final, fx["adam__final"]) <= 1e-7
+    kf.check_adam_trace(FAMILY)
 
 
 def test_all_gaussian_kinds_call_changes_nothing():

@@ -1,107 +1,27 @@
 """
 Host side of LinearKernel, PolynomialKernel and SincKernel (kinds 6 and 7), without a device: the class surface; the term tables
-and kinds they emit alone and under MulKernel, IndependentMultiOutputKernel and LMC (the leading coregionalization row included); a numpy
-evaluator of the table form -- dot-product rows and the sinc profile added to test_product_cpu's -- against closed-form numpy kernels
-written here and against the reference's K / K_diag (tests/golden/trend.npz, written by tests/golden/gen_trend.py from the models of
-tests/trend_cases.py); the chain rule and the per-point diagonal's backward against finite differences of those closed forms and against the
-reference's autograd; the refusals; checkpoints.
+and kinds they emit alone and under MulKernel, IndependentMultiOutputKernel and LMC (the leading coregionalization row included); the
+table form through the numpy twin of the device handle (oracle/table_model.py: dot-product rows and the sinc profile) against closed-form
+numpy kernels written here and against the reference's K / K_diag (tests/golden/trend.npz, written by tests/golden/gen_family.py from the
+models of tests/trend_cases.py); the chain rule and the per-point diagonal's backward against finite differences of those closed forms and
+against the reference's autograd; the refusals; checkpoints.  The bodies shared with the other kernel families are in tests/kernel_family.py.
 """
-import io
 import os
 import numpy as np
 import pytest
 
-import mogptk_amd
 from mogptk_amd import gpr, _lib
-from mogptk_amd.gpr.kernel import KIND_TIMES, KIND_MASK, KIND_DOT, group_slices
+from mogptk_amd.gpr.kernel import KIND_TIMES, KIND_DOT
 from mogptk_amd.gpr.singleoutput import KIND_SINC
 from mogptk_amd.gpr.model import _gtable_from_moments
 import trend_cases as tc
-from helpers import load
-from test_stationary_cpu import with_reference_raw, NumpyDevice
-from test_product_cpu import row_parts
+import kernel_family as kf
+from family_cases import exact, full_cases
+from oracle.table_model import gram_from_table, moments_dense
 
+FAMILY = "trend"
 X_ = KIND_TIMES
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def golden_K(case):
-    for tag in "ab":
-        fx = load("trend_gram_%s.npz" % tag)
-        if case + "__K_tril" in fx:
-            tril = fx[case + "__K_tril"]
-            n = int(round((np.sqrt(8 * len(tril) + 1) - 1) / 2))
-            K = np.zeros((n, n))
-            K[np.tril_indices(n)] = tril
-            return K + np.tril(K, -1).T
-    raise KeyError(case)
-
-
-# ---- the table form in numpy: what the device computes ----------------------------------------------------------------------------------
-def trend_row(row, kind, shape, xa, xb):
-    """(value of one table row WITHOUT its amplitude -- a dot-product row: its full value, flagged --, the integrands of its moments
-    [m0, m4, m1_d, m2_d, m3_d]) at the inputs xa (na, D), xb (nb, D)"""
-    D = xa.shape[1]
-    u = xa[:, None, :] - xb[None, :, :] + row[2 + 2 * D:2 + 3 * D]
-    if kind == KIND_DOT:                                    # k = b^n, b = A <x_a, x_b> + c: m0 = d/dA, m1_0 = d/dc, nothing else
-        ip = xa @ xb.T
-        n = int(shape)
-        b = row[0] * ip + row[1]
-        db = n * b ** (n - 1)
-        zero = np.zeros_like(ip)
-        return b ** n, [db * ip, zero, db] + [zero] * (3 * D - 1)
-    if kind == KIND_SINC:
-        s = np.sum(row[2:2 + D] * u * u, axis=2)
-        r = np.sqrt(s)
-        phi = np.sinc(r)
-        psi = np.where(s > 1e-8, (phi - np.cos(np.pi * r)) / np.where(s > 1e-8, s, 1.0), np.pi ** 2 * (1.0 / 3.0 - np.pi ** 2 * s / 30.0))
-        th = 2.0 * np.pi * (np.sum(row[2 + D:2 + 2 * D] * u, axis=2) + row[1])
-        parts = [phi * np.cos(th), phi * np.sin(th)]
-        parts += [u[..., d] ** 2 * psi * np.cos(th) for d in range(D)] + [u[..., d] * psi * np.cos(th) for d in range(D)]
-        parts += [u[..., d] * phi * np.sin(th) for d in range(D)]
-        return phi * np.cos(th), parts
-    return row_parts(row, kind, shape, u)
-
-
-def evaluate(table, kind, shape, Xa, Xb, G=None):
-    """test_product_cpu.evaluate with kinds 6 and 7: K(Xa, Xb) of a term table with kinds and product groups; with an adjoint G also the
-    moments of every ordered channel pair"""
-    C, T, D = table.shape[0], table.shape[2], Xa.shape[1] - 1
-    ca, cb = Xa[:, 0].astype(int), Xb[:, 0].astype(int)
-    K = np.zeros((len(Xa), len(Xb)))
-    mom = np.zeros((C, C, T, 2 + 3 * D))
-    for i in range(C):
-        for j in range(C):
-            ia, ib = np.where(ca == i)[0], np.where(cb == j)[0]
-            kd = kind[i, j] & KIND_MASK
-            rows = [trend_row(table[i, j, t], int(kd[t]), shape[i, j, t], Xa[ia, 1:], Xb[ib, 1:]) for t in range(T)]
-            for a, b in group_slices(kind[i, j]):
-                vals = [rows[t][0] if kd[t] == KIND_DOT else table[i, j, t, 0] * rows[t][0] for t in range(a, b)]
-                K[np.ix_(ia, ib)] += np.prod(vals, axis=0)
-                if G is not None:
-                    for t in range(a, b):
-                        w = G[np.ix_(ia, ib)] * np.prod([v for h, v in enumerate(vals) if h != t - a] + [np.ones_like(vals[0])], axis=0)
-                        mom[i, j, t] = [np.sum(w * part) for part in rows[t][1]]
-    return K, mom
-
-
-class TrendDevice(NumpyDevice):
-    """test_stationary_cpu.NumpyDevice over the evaluator above; the relative jitter there comes from the evaluated matrix's own diagonal, so
-    the per-point diagonal the model supplies is only checked against it"""
-
-    def set_point_diag(self, kdiag):
-        self.point_diag = None if kdiag is None else np.array(kdiag)
-
-    def eval(self, noise_var, jitter, grad=True, data_var=None):
-        import test_stationary_cpu as ts
-        saved, ts.evaluate = ts.evaluate, evaluate
-        try:
-            if getattr(self, "point_diag", None) is not None:
-                K, _ = evaluate(self.table, self.kind, self.shape, self.X, self.X)
-                assert np.max(np.abs(np.diag(K) - self.point_diag)) <= 1e-13 * max(1.0, np.max(np.diag(K)))
-            return super().eval(noise_var, jitter, grad=grad, data_var=data_var)
-        finally:
-            ts.evaluate = saved
 
 
 # ---- the kernels in closed form, straight from their definitions -----------------------------------------------------------------------
@@ -209,43 +129,16 @@ def test_tables_and_kinds_of_the_three_kernels():
     assert np.all(k._spectral_kinds(1)[0] == np.array([6 | X_, 7])) and k._spectral_terms(1).shape[2] == 2
 
 
-@pytest.mark.parametrize("case", tc.FULL_CASES)
+@pytest.mark.parametrize("case", full_cases(FAMILY))
 def test_table_and_kinds_reproduce_the_reference_gram(case):
-    fx = load("trend.npz")
-    m = tc.exact(gpr, case)
-    with_reference_raw(m, fx, case + "__")
-    k = m.kernel
-    X, Xs = k._kernel_format(fx[case + "__X"]), k._kernel_format(fx[case + "__Xs"])
-    D = X.shape[1] - 1
-    table = k._spectral_terms(D)
-    kind, shape = k._spectral_kinds(D)
-    assert kind.shape == table.shape[:3] == shape.shape and shape.dtype == np.float64
-    want = golden_K(case)
-    tol = 1e-12 * max(1.0, np.max(np.abs(want)))
-    K, _ = evaluate(table, kind, shape, X, X)
-    assert np.max(np.abs(K - want)) <= tol
+    k, _, _, _, X, _, want, tol = kf.check_table_and_kinds(FAMILY, case)
     assert np.max(np.abs(closed_form_mo(k, X, X) - want)) <= tol                # the closed forms of this file are the reference's kernels
-    K12, _ = evaluate(table, kind, shape, X, Xs)
-    assert np.max(np.abs(K12 - fx[case + "__K12"])) <= tol
-    kd = k.K_diag(fx[case + "__X"])
-    assert np.max(np.abs(kd - fx[case + "__Kdiag"])) <= tol
-    assert np.max(np.abs(np.diag(K) - kd)) <= tol           # what the relative jitter takes: per point, the product of a group's rows' diagonals
 
 
-@pytest.mark.parametrize("case", tc.FULL_CASES)
+@pytest.mark.parametrize("case", full_cases(FAMILY))
 def test_chain_rule_reproduces_reference_gradients(case, monkeypatch):
-    """gpr.Exact's own loss path (table push, kinds, per-point diagonal, moments -> table gradient -> _spectral_backward, the jitter term by
-    the product rule at every point) over the numpy device"""
-    fx = load("trend.npz")
-    monkeypatch.setattr(_lib, "ExactHandle", TrendDevice)
-    m = tc.exact(gpr, case)
-    ps = with_reference_raw(m, fx, case + "__")
-    loss = float(m.loss())
-    assert abs(loss - float(fx[case + "__loss"])) <= 1e-9 * max(1.0, abs(float(fx[case + "__loss"])))
-    assert m._handle.kind is not None and (getattr(m._handle, "point_diag", None) is not None) == m.kernel._pointwise(m._handle.D)
-    for i, p in enumerate(ps):
-        g = fx["%s__p%d_grad" % (case, i)]
-        assert np.max(np.abs(p.grad - g)) <= 1e-9 * max(1.0, np.max(np.abs(g))), (p._name, p.grad, g)
+    m = kf.check_chain_rule(FAMILY, case, monkeypatch)
+    assert m._handle.kind is not None                       # every case of this family carries a kind
 
 
 def fd_kernels():
@@ -262,7 +155,7 @@ def fd_kernels():
 @pytest.mark.parametrize("name", ["lin", "poly3", "sinc", "lin*per", "sinc*poly2", "lin+se", "poly2*m32*per+sinc*lin", "lin_d2", "poly2_d2", "imo", "lmc", "lmc_mul"])
 def test_backward_against_finite_differences_of_the_closed_forms(name):
     """f(raw parameters) = sum_ab G_ab K_ab + sum_a w_a K_aa with K from the CLOSED FORMS of this file (no table inside), G symmetric; its
-    gradient from the table evaluator's moments in the device's layout (lower pairs, off-diagonal blocks twice, the odd slots of diagonal
+    gradient from the twin's moments in the device's layout (lower pairs, off-diagonal blocks twice, the odd slots of diagonal
     blocks zeroed), `_gtable_from_moments`, `_point_diag_table_grad` (or the constant diagonal's product rule) and `_spectral_backward`"""
     rng = np.random.default_rng(11)
     k = fd_kernels()[name]
@@ -280,15 +173,9 @@ def test_backward_against_finite_differences_of_the_closed_forms(name):
 
     table = k._spectral_terms(D)
     kind, shape = k._spectral_kinds(D)
-    K, full = evaluate(table, kind, shape, X, X, G)
+    K = gram_from_table(table, X, X, kind, shape)
     assert np.max(np.abs(K - closed_form_mo(k, X, X))) <= 1e-13 * max(1.0, np.max(np.abs(K)))
-    mom = np.zeros((C * (C + 1) // 2,) + full.shape[2:])
-    for i in range(C):
-        for j in range(i + 1):
-            mom[i * (i + 1) // 2 + j] = full[i, j] if i == j else 2.0 * full[i, j]
-            if i == j:
-                mom[i * (i + 1) // 2 + j][:, 1] = 0.0
-                mom[i * (i + 1) // 2 + j][:, 2 + D:2 + 2 * D] = 0.0
+    mom = moments_dense(table, G, X, X, True, kind, shape)
     assert np.max(np.abs(k._point_diag(table, X, D) - np.diag(K))) <= 1e-13 * max(1.0, np.max(np.abs(K)))
     gt = _gtable_from_moments(table, mom, D, lower=True, kind=kind) + k._point_diag_table_grad(table, X, D, weights=w)
     for p in k.parameters():
@@ -306,7 +193,7 @@ def test_backward_against_finite_differences_of_the_closed_forms(name):
 
 
 def test_sinc_series_meets_the_closed_form():
-    """the evaluator's psi switches to its series below s = 1e-8; the device's below pi^2 s = 1 -- both sides of either threshold agree with
+    """the twin's psi switches to its series below s = 1e-8; the device's below pi^2 s = 1 -- both sides of either threshold agree with
     the closed form to rounding where that is well conditioned"""
     s = np.array([0.0, 1e-12, 1e-9, 1e-7, 1e-3, 0.05, 0.1, 0.2, 1.0, 7.3])
     x = np.pi ** 2 * s
@@ -359,7 +246,7 @@ def test_refusals_come_before_any_device_call(monkeypatch):
     gpr.config.comm = Comm()
     try:
         for case in ("lin", "sinc", "poly2_m32"):
-            m = tc.exact(gpr, case)
+            m = exact(FAMILY, gpr, case)
             with pytest.raises(NotImplementedError, match="use_distributed"):
                 m.loss()
             assert m._handle is None
@@ -383,31 +270,12 @@ CHECKPOINTS = ("trend", "lmc")
 @pytest.mark.parametrize("tag", CHECKPOINTS)
 def test_reference_checkpoint_round_trip(tag, tmp_path):
     pytest.importorskip("torch")
-    from mogptk_amd import compat
-    from test_host_logic import _checkpoint_tree, _tree_differences
-    fx = load("trend_checkpoints.npz")
-    raw = fx[tag + "_file"].tobytes()
-    (tmp_path / "ref.npy").write_bytes(raw)
-    m = mogptk_amd.LoadModel(str(tmp_path / "ref"))
-    ps = list(m.gpr.parameters())
-    assert [p._name for p in ps] == [str(n) for n in fx[tag + "_names"]]
-    for i, p in enumerate(ps):
-        ref = fx["%s_p%d" % (tag, i)]
-        assert np.asarray(p()).shape == ref.shape and np.max(np.abs(np.asarray(p()) - ref)) <= 1e-12 * max(1.0, np.max(np.abs(ref))), p._name
-
-    def leaves_of(k):
-        return [n for s in k.kernels for n in leaves_of(s)] + [type(k).__name__] if getattr(k, "kernels", None) else [type(k).__name__]
+    k = kf.check_checkpoint_loads(FAMILY, tag, tmp_path)
     want = dict(trend={"MulKernel", "LinearKernel", "PeriodicKernel", "PolynomialKernel", "SincKernel"}, lmc={"LinearKernel", "MulKernel", "SincKernel", "PolynomialKernel"})[tag]
-    assert want <= set(leaves_of(m.gpr.kernel))
-    degrees = [k.degree for k in _walk(m.gpr.kernel) if type(k).__name__ == "PolynomialKernel"]
+    assert want <= set(kf.kernel_names(k))
+    degrees = [s.degree for s in _walk(k) if type(s).__name__ == "PolynomialKernel"]
     assert degrees == [dict(trend=2, lmc=3)[tag]]
-    written = compat.dump_reference_model(compat.load_reference_model(raw))
-    assert compat.is_reference_checkpoint(written)
-    theirs = _checkpoint_tree(compat._Unpickler(io.BytesIO(raw)).load(), {})
-    ours = _checkpoint_tree(compat._Unpickler(io.BytesIO(written)).load(), {})
-    out = []
-    _tree_differences(theirs, ours, tag, out)
-    assert not out, out[:5]
+    kf.check_checkpoint_is_written_as_the_reference_writes_it(FAMILY, tag)
 
 
 def _walk(k):

@@ -1,6 +1,6 @@
 """
-The models of tests/golden/trend.npz, built the same way on either side: `G` is the reference's `mogptk.gpr` (tests/golden/gen_trend.py) or
-this package's `mogptk_amd.gpr` (tests/test_trend_*.py).  Only seeded numpy inputs go in.
+The models of tests/golden/trend.npz, built the same way on either side: `G` is the reference's `mogptk.gpr` (tests/golden/gen_family.py) or
+this package's `mogptk_amd.gpr` (tests/test_trend_*.py, tests/kernel_family.py).  Only seeded numpy inputs go in.
 
 Shapes as in product_cases.py: N = 150 is three 64-point tile rows with a ragged last one; two channels of 70 and 45 points give tiles that
 stop at a channel boundary; N = 1100 is the smallest size that takes the dataflow schedule.  Inputs over [0, 10], noise variance 0.1.  In
@@ -9,7 +9,10 @@ Dot-product magnitudes in [0.01, 0.03] and biases in [0.2, 0.8] keep (mag x x' +
 frequency 0.3, Matern and squared-exponential lengthscale 0.6, period 3.  The generator asserts cond(K + s2 I) < 1e5, so the exact model's
 accurate-mode repeat never engages.
 """
+from functools import partial
 import numpy as np
+import family_cases
+from family_cases import top
 
 NOISE = 0.1
 ADAM_CASE, ADAM_ITERS, ADAM_LR = "lin_per", 20, 0.05
@@ -33,7 +36,6 @@ CASES = {
     # 5. the dataflow schedule: LML and gradients only
     "big": dict(kern="big", N=1100, light=True),
 }
-FULL_CASES = [c for c in CASES if not CASES[c].get("light")]
 
 
 def data(case, seed=7):
@@ -82,13 +84,7 @@ def single(G, kern, D, rng):
     return k
 
 
-def parse(G, expr, D, rng):
-    """a sum of products over the names of single(): 'a*b+c'"""
-    def product(s):
-        ks = [single(G, f, D, rng) for f in s.split("*")]
-        return ks[0] if len(ks) == 1 else G.MulKernel(*ks)
-    ks = [product(p) for p in expr.split("+")]
-    return ks[0] if len(ks) == 1 else G.AddKernel(*ks)
+parse = partial(family_cases.parse, single)
 
 
 def kernel(G, case, seed=29):
@@ -109,12 +105,14 @@ def kernel(G, case, seed=29):
     return top(G, parse(G, kern, D, rng))
 
 
-def top(G, k):
-    """The reference's Exact adds the noise IN PLACE to what the kernel returns, and autograd needs the output of a product to differentiate
-    it: a MulKernel at the top of a model is wrapped in an AddKernel of one (same kernel, a fresh tensor) on both sides."""
-    return G.AddKernel(k) if isinstance(k, G.MulKernel) else k
+def checkpoint_kernels(G):
+    """(tag, channels, points per channel, kernel) of trend_checkpoints.npz: linear, polynomial and sinc kernels inside AddKernel, MulKernel
+    and LMC"""
+    return [("trend", 1, 40, G.AddKernel(G.MulKernel(G.LinearKernel(), G.PeriodicKernel()), G.PolynomialKernel(2), G.SincKernel())),
+            ("lmc", 2, 30, G.LinearModelOfCoregionalizationKernel(G.LinearKernel(), G.MulKernel(G.SincKernel(), G.PolynomialKernel(3)), output_dims=2, Rq=2))]
 
 
-def exact(G, case, **kw):
-    X, y, _ = data(case)
-    return G.Exact(kernel(G, case), X, y, variance=NOISE, **kw)
+def shake_range(G, module, name):
+    """the range a checkpoint model's parameter `name` of `module` is drawn from: (mag x x' + bias)^n stays of order one"""
+    small = name == "magnitude" and isinstance(module, (G.LinearKernel, G.PolynomialKernel))
+    return (0.01, 0.03) if small else (0.4, 1.2)

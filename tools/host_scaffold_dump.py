@@ -7,8 +7,8 @@ versions of mogptk_amd/gpr/model.py bit for bit (numpy.array_equal): the host la
 Models: Exact, Titsias, Snelson, OpperArchambeau, SparseHensman, Hensman, each single-output (SM), two-channel (MOSM) and enveloped (MOHSM); Exact, Titsias and
 Snelson with a ConstantMean and a LinearMean; Exact with per-channel noise and data_variance; Exact with a Matern kernel; Exact and Snelson under
 use_single_precision().  N = 300 (170 / 130 over two channels), 2 x 16 inducing points, 37 test points.
-The twin has no radial kinds and no gradient of the sparse bounds with respect to the mean, so --twin leaves out the Matern model and the loss() of Titsias / Snelson
-with a mean; it adds the ill-conditioned Exact model of tests/test_host_logic.py and records the file:line its RuntimeWarning is attributed to."""
+The twin has no gradient of the sparse bounds with respect to the mean, so --twin leaves out the loss() of Titsias / Snelson with a mean; it also leaves out
+the Matern model, which the twin carries by now (kinds and product groups, exact evaluations only), so that dumps stay comparable with older ones; it adds the ill-conditioned Exact model of tests/test_host_logic.py and records the file:line its RuntimeWarning is attributed to."""
 import argparse, importlib.util, os, sys, warnings
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
