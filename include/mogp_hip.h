@@ -128,11 +128,21 @@ int  mogp_gram_ex(mogp_ctx* ctx, int C, int D, int T, int width, const double* t
  *           m0 = sum g n b^(n-1) <x_a, x_b> = d/dA and m1_0 = sum g n b^(n-1) = d/dc, b = A <x_a, x_b> + c (the other slots 0; both slots
  *           are even in tau, so the diagonal channel blocks keep them).  K(x, x) = (A |x|^2 + c)^n follows the point: as with enveloped
  *           rows, supply mogp_model_set_point_diag (without it the library forms the diagonal from the table and the kinds itself) and
- *           pass kss_diag to mogp_exact_predict per TEST POINT.  A group's diagonal is the product of its rows' diagonals at that point. */
+ *           pass kss_diag to mogp_exact_predict per TEST POINT.  A group's diagonal is the product of its rows' diagonals at that point.
+ *   kind 8  the gate row  A h(x_a) h(x_b),  h(x) = sigmoid(beta (x - l))   (the separable weights of the reference's ChangePointsKernel.K,
+ *           gpr/kernel.py:327-361; 1 - sigmoid(z) = sigmoid(-z), so a falling gate is a row with beta < 0): beta (signed) in the row's V_0 slot,
+ *           l in its M_0 slot, Psi = Delta = 0 and A = 1 for a pure weight; no cosine stands beside it.  D = 1 only; the row may stand alone in
+ *           a group.  It is A times something and keeps the ordinary amplitude handling.  h is evaluated once per row and column point of a
+ *           tile, without overflow for any finite argument.  Its moments leave the row's OWN amplitude out, as those of the profile rows do:
+ *           m0 = sum g h_a h_b = d/dA,  m1_0 = sum g h_a h_b [(1 - h_a)(x_a - l) + (1 - h_b)(x_b - l)],  m3_0 = -beta sum g h_a h_b [(1 - h_a) + (1 - h_b)]
+ *           (both even under a <-> b; the other slots 0), so d/dbeta = A m1_0 and d/dl = A m3_0 with no further factor.  Launches whose
+ *           kinds hold a gate row run instantiations of the radial kernels of their own; the others contain no gate code.  K(x, x) = A h(x)^2
+ *           follows the point, exactly as for kind 7: mogp_model_set_point_diag, kss_diag per test point. */
 #define MOGP_KIND_PERIODIC 5
 #define MOGP_KIND_SINC 6
 #define MOGP_KIND_DOT 7
 #define MOGP_DOT_DEGREE_MAX 8
+#define MOGP_KIND_GATE 8
 #define MOGP_KIND_TIMES (1 << 8)
 int  mogp_model_set_kinds(mogp_model* m, int T, const int* kind, const double* shape);
 /* mogp_gram_ex with kinds (NULL: mogp_gram_ex itself): replaces Kernel.K of the kernels above, and of their sums, IndependentMultiOutputKernel

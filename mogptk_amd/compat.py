@@ -238,6 +238,12 @@ def _convert_kernel(bag):
         subs = _module_children(mods["kernels"])
         k = cls(_convert_kernel(subs[0]), len(subs))
         return k
+    if name == "ChangePointsKernel":
+        # built on placeholder locations 0, 1, ...: the file's values follow with every other parameter, and whether they are still sorted
+        # is not asked again (the reference asks at construction only)
+        steep = params["steepness"].data
+        return cls([float(j) for j in range(params["locations"].data.shape[0])], [1.0] * steep.shape[0] if steep.ndim else 1.0,
+                   *[_convert_kernel(k) for k in _module_children(mods["kernels"])])
     if name == "IndependentMultiOutputKernel":
         return cls(*[_convert_kernel(k) for k in _module_children(mods["kernels"])], output_dims=odims)
     if name == "MultiOutputSpectralMixtureKernel":
@@ -470,7 +476,7 @@ class _RefPickler(pickle._Pickler):
 
 _PARAMETER_REBUILD = _Global("mogptk.gpr.parameter", "Parameter._rebuild")
 _REF_KERNEL_MODULE = {
-    "AddKernel": "kernel", "MulKernel": "kernel", "MixtureKernel": "kernel",
+    "AddKernel": "kernel", "MulKernel": "kernel", "MixtureKernel": "kernel", "ChangePointsKernel": "kernel",
     "SpectralKernel": "singleoutput", "SpectralMixtureKernel": "singleoutput", "SquaredExponentialKernel": "singleoutput",
     "RationalQuadraticKernel": "singleoutput", "MaternKernel": "singleoutput", "ExponentialKernel": "singleoutput",
     "ConstantKernel": "singleoutput", "CosineKernel": "singleoutput", "PeriodicKernel": "singleoutput", "LocallyPeriodicKernel": "singleoutput",

@@ -227,8 +227,8 @@ __device__ __forceinline__ void stage_item_load(StageItem<DM>& I, int which, int
 // global memory -- a generic pointer), W doubles each.
 // RAD: a launch with radial profiles (below): no Gaussian factor is split off, every term runs entry by entry (GT_GENERAL) and the staged
 // factors are the plain phase factors (times the amplitude; not for the periodic profile, whose phase is the profile's argument).
-// `kinds`: the pair's kind row (RAD only)
-template <int DM, bool AMP, bool RAD = false>
+// `kinds`: the pair's kind row (RAD only).  GATE: the instantiation that carries the gate row (below); the others hold none of its code
+template <int DM, bool AMP, bool RAD = false, bool GATE = false>
 __device__ __forceinline__ void stage_item_compute(TileLds<DM>& L, const StageItem<DM>& I, const TileCtx<DM>& X, const double* tab, int W,
                                                    int which, int t, int pnt, int D, int t0, const int* kinds = nullptr) {
     const double* row = tab + (size_t)(t0 + t) * W;
@@ -248,6 +248,17 @@ __device__ __forceinline__ void stage_item_compute(TileLds<DM>& L, const StageIt
         }
         if (deg == GT_SKIP) return;
         if (dot) return;                                        // no phase factors: the staged slots of the row are not read
+        if (GATE && kd == MOGP_KIND_GATE) {
+            // the sigmoid weight of the point, h = sigmoid(z), z = beta (x - l) (beta in the V slot, l in the M slot; D = 1), once per row / column
+            // point of the tile: cu / cw carry h (the rows' times the amplitude when AMP), su / sw its complement sigmoid(-z) -- never 1 - h.
+            // e = exp(-|z|) <= 1 for every finite z: nothing overflows, and a saturated gate gives 0 or 1
+            const double z = row[2] * (I.x[0] - row[2 + D]);
+            const double e = exp(-fabs(z)), r = 1.0 / (1.0 + e);
+            const double h = z >= 0.0 ? r : e * r, hc = z >= 0.0 ? e * r : r;
+            if (which == 0) { L.cu[t][pnt] = (AMP ? A : 1.0) * h; L.su[t][pnt] = hc; }
+            else { L.cw[t][pnt] = h; L.sw[t][pnt] = hc; }
+            return;
+        }
         const double f = (AMP && !per) ? A : 1.0;
         if (which == 0) { L.cu[t][pnt] = f * I.cs; L.su[t][pnt] = f * I.sn; }
         else { L.cw[t][pnt] = I.cs; L.sw[t][pnt] = I.sn; }
@@ -315,7 +326,7 @@ __device__ __forceinline__ void stage_item_compute(TileLds<DM>& L, const StageIt
 #define STAGE_MAP(tid) const int st_wave = __builtin_amdgcn_readfirstlane((tid) >> 6), st_which = st_wave & 1, st_tb = st_wave >> 1, st_pnt = (tid) & 63
 
 // one chunk of terms into LDS; BATCH: all items' loads first (one memory round trip), else item by item (large D: registers)
-template <int DM, bool AMP, bool BATCH, bool RAD = false>
+template <int DM, bool AMP, bool BATCH, bool RAD = false, bool GATE = false>
 __device__ __forceinline__ void stage_chunk(TileLds<DM>& L, const TileCtx<DM>& X, const GTile& tl, const double* tab, int W, int D,
                                             int C, int T, int t0, int nt, const PhaseView& v, const double* __restrict__ xr, int64_t ldxr,
                                             const double* __restrict__ xc, int64_t ldxc, int tid, const int* kinds = nullptr) {
@@ -327,12 +338,12 @@ __device__ __forceinline__ void stage_chunk(TileLds<DM>& L, const TileCtx<DM>& X
             if (st_tb + 2 * k < nt) stage_item_load<DM>(I[k], st_which, st_tb + 2 * k, st_pnt, tl, D, C, T, t0, v, xr, ldxr, xc, ldxc);
 #pragma unroll
         for (int k = 0; k < STAGE_ITEMS; ++k)
-            if (st_tb + 2 * k < nt) stage_item_compute<DM, AMP, RAD>(L, I[k], X, tab, W, st_which, st_tb + 2 * k, st_pnt, D, t0, kinds);
+            if (st_tb + 2 * k < nt) stage_item_compute<DM, AMP, RAD, GATE>(L, I[k], X, tab, W, st_which, st_tb + 2 * k, st_pnt, D, t0, kinds);
     } else {
         for (int t = st_tb; t < nt; t += 2) {
             StageItem<DM> I;
             stage_item_load<DM>(I, st_which, t, st_pnt, tl, D, C, T, t0, v, xr, ldxr, xc, ldxc);
-            stage_item_compute<DM, AMP, RAD>(L, I, X, tab, W, st_which, t, st_pnt, D, t0, kinds);
+            stage_item_compute<DM, AMP, RAD, GATE>(L, I, X, tab, W, st_which, t, st_pnt, D, t0, kinds);
         }
     }
 }
@@ -484,6 +495,10 @@ __device__ __forceinline__ double dot_row_power(double b, int n) {
 }
 __device__ __forceinline__ int dot_row_degree(double shape) { return __builtin_amdgcn_readfirstlane((int)shape); }
 
+// The gate row (MOGP_KIND_GATE, D = 1): k = A h(x_a) h(x_b), h(x) = sigmoid(beta (x - l)) -- the separable weight of the reference's
+// ChangePointsKernel.  h is a property of the point: the staging evaluates it (and its complement) once per row and column point into the
+// slots the phase factors take for other rows, and an entry only multiplies: cu = (A) h_a, cw = h_b, su = 1 - h_a, sw = 1 - h_b.
+
 // Chunks of a radial launch end at a group end (a group never straddles two chunks): at most MOGP_TC rows from t0 on, shortened while the
 // last one still multiplies with its successor.  `kinds`: one pair's kind row -- the flags are the same in every pair.
 __device__ __forceinline__ int radial_chunk(const int* kinds, int T, int t0) {
@@ -492,7 +507,7 @@ __device__ __forceinline__ int radial_chunk(const int* kinds, int T, int t0) {
     return nt;
 }
 
-template <int DM>
+template <int DM, bool GATE = false>
 __device__ __forceinline__ void gram_term_radial(double (&acc)[4][4], const double (&p)[4][DM], const double (&q)[4][DM], const TileLds<DM>& L, int t,
                                                  int D, int kind, double shape, const double (&cu)[4], const double (&su)[4],
                                                  const double (&cw)[4], const double (&sw)[4]) {
@@ -503,6 +518,13 @@ __device__ __forceinline__ void gram_term_radial(double (&acc)[4][4], const doub
         for (int m = 0; m < 4; ++m)
 #pragma unroll
             for (int nn = 0; nn < 4; ++nn) acc[m][nn] += dot_row_power(fma(L.A[t], dot_row_inner<DM>(p[m], q[nn], L, t, D), L.e[t][0]), n);
+        return;
+    }
+    if (GATE && kind == MOGP_KIND_GATE) {                   // A h_a h_b from the staged factors (the amplitude rides in cu)
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int nn = 0; nn < 4; ++nn) acc[m][nn] = fma(cu[m], cw[nn], acc[m][nn]);
         return;
     }
 #pragma unroll
@@ -521,7 +543,7 @@ __device__ __forceinline__ void gram_term_radial(double (&acc)[4][4], const doub
 // One row of a product group: prod *= k_t per entry, k_t = A phi cos theta (the amplitude rides in the staged row factors when AMPF, else
 // it is L.A[t]: the moment pass stages unit amplitudes) -- for a row whose value is A times something, the moment pass leaves the row's OWN
 // amplitude to the host and this function supplies the other rows'.  A dot-product row is not of that form and always brings its full value.
-template <int DM, bool AMPF>
+template <int DM, bool AMPF, bool GATE = false>
 __device__ __forceinline__ void group_factor_radial(double (&prod)[4][4], const double (&p)[4][DM], const double (&q)[4][DM],
                                                     const TileLds<DM>& L, int t, int D, int kind, double shape, int rg, int cg) {
     const bool per = kind == MOGP_KIND_PERIODIC;
@@ -532,6 +554,15 @@ __device__ __forceinline__ void group_factor_radial(double (&prod)[4][4], const 
         for (int m = 0; m < 4; ++m)
 #pragma unroll
             for (int nn = 0; nn < 4; ++nn) prod[m][nn] *= dot_row_power(fma(A, dot_row_inner<DM>(p[m], q[nn], L, t, D), L.e[t][0]), n);
+        return;
+    }
+    if (GATE && kind == MOGP_KIND_GATE) {                   // a row of the form A times something: the staged factors, and A where they do not carry it
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const double hu = AMPF ? L.cu[t][rg * 4 + m] : A * L.cu[t][rg * 4 + m];
+#pragma unroll
+            for (int nn = 0; nn < 4; ++nn) prod[m][nn] *= hu * L.cw[t][cg * 4 + nn];
+        }
         return;
     }
     double cw[4], sw[4];
@@ -605,7 +636,7 @@ __device__ __forceinline__ void gram_store(const GramArgs& a, const GTile& tl, c
 // in its arithmetic (measured: 66 of 126 us).  The staged factors are double buffered in LDS: one barrier per tile.
 // RAD: the radial instantiation (a.kind / a.shape are set): same pipeline, entry-by-entry profiles.  The Gaussian instantiations (RAD = false)
 // contain nothing of it.
-template <int DT, bool RAD = false>
+template <int DT, bool RAD = false, bool GATE = false>
 __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a, int ntiles) {
     constexpr int DM = DT > 0 ? DT : MOGP_MAXD;
     constexpr bool BATCH = DT == 1;
@@ -648,9 +679,9 @@ __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a, int ntiles) {
         if (BATCH) {
 #pragma unroll
             for (int k = 0; k < STAGE_ITEMS; ++k)
-                if (st_tb + 2 * k < nt0) stage_item_compute<DM, true, RAD>(L, I[k], X, tab, W, st_which, st_tb + 2 * k, st_pnt, D, 0, RAD ? a.kind + (size_t)cur.pair * a.T : nullptr);
+                if (st_tb + 2 * k < nt0) stage_item_compute<DM, true, RAD, GATE>(L, I[k], X, tab, W, st_which, st_tb + 2 * k, st_pnt, D, 0, RAD ? a.kind + (size_t)cur.pair * a.T : nullptr);
         } else {
-            stage_chunk<DM, true, false, RAD>(L, X, cur, tab, W, D, a.C, a.T, 0, nt0, v, a.xr, a.ldxr, a.xc, a.ldxc, tid, RAD ? a.kind + (size_t)cur.pair * a.T : nullptr);
+            stage_chunk<DM, true, false, RAD, GATE>(L, X, cur, tab, W, D, a.C, a.T, 0, nt0, v, a.xr, a.ldxr, a.xc, a.ldxc, tid, RAD ? a.kind + (size_t)cur.pair * a.T : nullptr);
         }
         double pc[4][DM], qc[4][DM];
 #pragma unroll
@@ -682,7 +713,7 @@ __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a, int ntiles) {
                 __syncthreads();
                 TileCtx<DM> Xc;
                 tile_centres<DM>(Xc, cur, D, v, a.ldxr, a.ldxc);
-                stage_chunk<DM, true, false, RAD>(L, Xc, cur, tab, W, D, a.C, a.T, t0, nt, v, a.xr, a.ldxr, a.xc, a.ldxc, tid, RAD ? a.kind + (size_t)cur.pair * a.T : nullptr);
+                stage_chunk<DM, true, false, RAD, GATE>(L, Xc, cur, tab, W, D, a.C, a.T, t0, nt, v, a.xr, a.ldxr, a.xc, a.ldxc, tid, RAD ? a.kind + (size_t)cur.pair * a.T : nullptr);
                 __syncthreads();
             }
             if constexpr (RAD) {
@@ -704,7 +735,7 @@ __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a, int ntiles) {
                             cu[m] = L.cu[t][rg * 4 + m]; su[m] = L.su[t][rg * 4 + m];
                             cw[m] = L.cw[t][cg * 4 + m]; sw[m] = L.sw[t][cg * 4 + m];
                         }
-                        gram_term_radial<DM>(acc, pc, qc, L, t, D, __builtin_amdgcn_readfirstlane(kd[t]) & MOGP_KIND_MASK, sh[t], cu, su, cw, sw);
+                        gram_term_radial<DM, GATE>(acc, pc, qc, L, t, D, __builtin_amdgcn_readfirstlane(kd[t]) & MOGP_KIND_MASK, sh[t], cu, su, cw, sw);
                         continue;
                     }
                     double prod[4][4];
@@ -713,7 +744,7 @@ __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a, int ntiles) {
 #pragma unroll
                         for (int n = 0; n < 4; ++n) prod[m][n] = 1.0;
                     for (int f = t; f <= te; ++f)
-                        group_factor_radial<DM, true>(prod, pc, qc, L, f, D, __builtin_amdgcn_readfirstlane(kd[f]) & MOGP_KIND_MASK, sh[f], rg, cg);
+                        group_factor_radial<DM, true, GATE>(prod, pc, qc, L, f, D, __builtin_amdgcn_readfirstlane(kd[f]) & MOGP_KIND_MASK, sh[f], rg, cg);
 #pragma unroll
                     for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -1186,7 +1217,7 @@ void split_strip_tiles(const std::vector<GTile>& tiles, int maxrun, std::vector<
     }
 }
 
-int launch_gram(const GramArgs& a0, int ntiles, hipStream_t s) {
+int launch_gram(const GramArgs& a0, int ntiles, hipStream_t s, bool gate) {
     if (ntiles <= 0) return 0;
     GramArgs a = a0;
     if (a.W <= 0) a.W = 2 + 3 * a.D;
@@ -1207,11 +1238,16 @@ int launch_gram(const GramArgs& a0, int ntiles, hipStream_t s) {
     if (a.kind) {                                            // radial profiles: every tile of the list through the radial general kernel
         if (!a.shape) { set_error("launch_gram: kinds without shapes"); return -1; }
         if (a.W != 2 + 3 * a.D) { set_error("launch_gram: radial profiles do not combine with enveloped term rows"); return -1; }
+        if (gate && a.D != 1) { set_error("launch_gram: gate rows take one input dimension"); return -1; }
+        if (gate) {                                          // (the instantiations below hold no gate code)
+            hipLaunchKernelGGL((k_gram<1, true, true>), dim3(grid), dim3(256), dyn, s, a, ntiles);
+        } else {
         switch (a.D) {
             case 1: hipLaunchKernelGGL((k_gram<1, true>), dim3(grid), dim3(256), dyn, s, a, ntiles); break;
             case 2: hipLaunchKernelGGL((k_gram<2, true>), dim3(grid), dim3(256), dyn, s, a, ntiles); break;
             case 3: hipLaunchKernelGGL((k_gram<3, true>), dim3(grid), dim3(256), dyn, s, a, ntiles); break;
             default: hipLaunchKernelGGL((k_gram<0, true>), dim3(grid), dim3(256), dyn, s, a, ntiles); break;
+        }
         }
         if (a.ev1) HIP_TRY(hipEventRecord(a.ev1, s));
         HIP_TRY(hipGetLastError());
@@ -1321,7 +1357,7 @@ __device__ __forceinline__ void moment_term(double* mom, const double (&g)[4][4]
 }
 
 // the radial form of moment_term (exact mode, no envelope, no input gradients): phi weighs m0, m4, m3_d; psi = -2 dphi/ds weighs m1_d, m2_d
-template <int DM>
+template <int DM, bool GATE = false>
 __device__ __forceinline__ void moment_term_radial(double* mom, const double (&g)[4][4], const double (&p)[4][DM], const double (&q)[4][DM],
                                                    const TileLds<DM>& L, int t, int D, int kind, double shape,
                                                    const double (&cu)[4], const double (&su)[4], const double (&cw)[4], const double (&sw)[4]) {
@@ -1342,6 +1378,25 @@ __device__ __forceinline__ void moment_term_radial(double* mom, const double (&g
                 mom[0] = fma(w, ip, mom[0]);
                 mom[2] += w;
             }
+        return;
+    }
+    if (GATE && kind == MOGP_KIND_GATE) {
+        // k = h_a h_b (unit amplitude staged: the row's own A is the host's, as for a profile row), h = sigmoid(beta (x - l)), dh/dz = h (1 - h):
+        // m0 = sum g k,  m1_0 = sum g k [(1 - h_a)(x_a - l) + (1 - h_b)(x_b - l)] = d/dbeta / A,  m3_0 = -beta sum g k [(1 - h_a) + (1 - h_b)] = d/dl / A  (slots 0, 2, 4: all
+        // even under a <-> b, k_moment_reduce keeps them on diagonal channel blocks); the other slots stay 0.  x - l from the thread's centred
+        // input and the tile centre the staging left in L.Kp / L.L; the complements come staged (su, sw)
+        const double er = L.Kp[t][0] - L.M[t][0], ec = L.L[t][0] - L.M[t][0];
+        double m3 = 0.0;
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int nn = 0; nn < 4; ++nn) {
+                const double k = g[m][nn] * (cu[m] * cw[nn]);
+                mom[0] += k;
+                mom[2] = fma(k, fma(su[m], p[m][0] + er, sw[nn] * (q[nn][0] + ec)), mom[2]);
+                m3 = fma(k, su[m] + sw[nn], m3);
+            }
+        mom[4] = fma(-V[0], m3, mom[4]);
         return;
     }
 #pragma unroll
@@ -1386,7 +1441,7 @@ __device__ __forceinline__ void moment_term_radial(double* mom, const double (&g
 // (round 4: cutting the registers to three or four waves per SIMD -- __launch_bounds__(256, 3 / 4) -- costs 81 / 92 spilled VGPRs; the pressure is
 // the tile's adjoint block (g: 32 VGPRs), the staged factors and the staging prefetch, not the Horner chains)
 // RAD: the radial instantiation (a.kind / a.shape are set; DENSE, ZG and ENV are false); the others contain nothing of it.
-template <int DT, bool DENSE, bool ZG, bool ENV, bool RAD = false>
+template <int DT, bool DENSE, bool ZG, bool ENV, bool RAD = false, bool GATE = false>
 __global__ __launch_bounds__(256, (DT == 1 && !RAD ? 2 : 1)) void k_moments(MomentArgs a) {      // (RAD, D = 1: the library exps push two workgroups per CU into scratch)
     static_assert(!RAD || (!DENSE && !ZG && !ENV), "radial moments: exact mode only");
     constexpr int DM = DT > 0 ? DT : MOGP_MAXD;
@@ -1465,7 +1520,7 @@ __global__ __launch_bounds__(256, (DT == 1 && !RAD ? 2 : 1)) void k_moments(Mome
     for (int t0 = 0, nt; t0 < a.T; t0 += RAD ? nt : MOGP_TC) {
         if constexpr (RAD) nt = radial_chunk(a.kind, a.T, t0); else nt = min(MOGP_TC, a.T - t0);
         if (t0 > 0) __syncthreads();                         // the first chunk has nothing to wait for
-        stage_chunk<DM, false, (DT == 1 && !RAD), RAD>(L, X, tl, tab, W, D, a.C, a.T, t0, nt, v, a.x, a.ldx, xcol, ldxc, tid, RAD ? a.kind + (size_t)tl.pair * a.T : nullptr);
+        stage_chunk<DM, false, (DT == 1 && !RAD), RAD, GATE>(L, X, tl, tab, W, D, a.C, a.T, t0, nt, v, a.x, a.ldx, xcol, ldxc, tid, RAD ? a.kind + (size_t)tl.pair * a.T : nullptr);
         __syncthreads();
         te = -1;
         for (int t = 0; t < nt; ++t) {
@@ -1500,10 +1555,10 @@ __global__ __launch_bounds__(256, (DT == 1 && !RAD ? 2 : 1)) void k_moments(Mome
 #pragma unroll
                         for (int n = 0; n < 4; ++n) wg[m][n] = g[m][n];
                     for (int h = tg; h <= te; ++h)
-                        if (h != t) group_factor_radial<DM, false>(wg, p, q, L, h, D, __builtin_amdgcn_readfirstlane(kd[h]) & MOGP_KIND_MASK, sh[h], rg, cg);
-                    moment_term_radial<DM>(mom, wg, p, q, L, t, D, kind, sh[t], cu, su, cw, sw);
+                        if (h != t) group_factor_radial<DM, false, GATE>(wg, p, q, L, h, D, __builtin_amdgcn_readfirstlane(kd[h]) & MOGP_KIND_MASK, sh[h], rg, cg);
+                    moment_term_radial<DM, GATE>(mom, wg, p, q, L, t, D, kind, sh[t], cu, su, cw, sw);
                 } else {
-                    moment_term_radial<DM>(mom, g, p, q, L, t, D, kind, sh[t], cu, su, cw, sw);
+                    moment_term_radial<DM, GATE>(mom, g, p, q, L, t, D, kind, sh[t], cu, su, cw, sw);
                 }
             } else
             switch (deg) {
@@ -1799,7 +1854,7 @@ static int launch_moments_t(const MomentArgs& a, hipStream_t s) {
     return 0;
 }
 
-int launch_moments(const MomentArgs& a0, hipStream_t s) {
+int launch_moments(const MomentArgs& a0, hipStream_t s, bool gate) {
     if (a0.ntiles <= 0) return 0;
     MomentArgs a = a0;
     if (a.W <= 0) a.W = 2 + 3 * a.D;
@@ -1812,11 +1867,16 @@ int launch_moments(const MomentArgs& a0, hipStream_t s) {
         if (!a.shape) { set_error("launch_moments: kinds without shapes"); return -1; }
         if (a.G != nullptr || env) { set_error("launch_moments: radial profiles run in exact mode without an envelope only"); return -1; }
         if (a.ev0) HIP_TRY(hipEventRecord(a.ev0, s));
+        if (gate && a.D != 1) { set_error("launch_moments: gate rows take one input dimension"); return -1; }
+        if (gate) {
+            hipLaunchKernelGGL((k_moments<1, false, false, false, true, true>), dim3(a.ntiles), dim3(256), 0, s, a);
+        } else {
         switch (a.D) {
             case 1: hipLaunchKernelGGL((k_moments<1, false, false, false, true>), dim3(a.ntiles), dim3(256), 0, s, a); break;
             case 2: hipLaunchKernelGGL((k_moments<2, false, false, false, true>), dim3(a.ntiles), dim3(256), 0, s, a); break;
             case 3: hipLaunchKernelGGL((k_moments<3, false, false, false, true>), dim3(a.ntiles), dim3(256), 0, s, a); break;
             default: hipLaunchKernelGGL((k_moments<0, false, false, false, true>), dim3(a.ntiles), dim3(256), 0, s, a); break;
+        }
         }
         HIP_TRY(hipGetLastError());
         if (a.ev1) HIP_TRY(hipEventRecord(a.ev1, s));

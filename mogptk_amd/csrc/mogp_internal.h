@@ -25,6 +25,9 @@
 #define MOGP_KIND_DOT 7        // (A <x_a, x_b> + Psi)^shape: the dot-product row -- not a profile of s, and non-stationary (its diagonal follows the point)
 #define MOGP_DOT_DEGREE_MAX 8
 #endif
+#ifndef MOGP_KIND_GATE
+#define MOGP_KIND_GATE 8       // A h(x_a) h(x_b), h(x) = sigmoid(V (x - M)): the separable sigmoid weight of a change-point kernel (D = 1; its diagonal follows the point)
+#endif
 // Product groups: a row whose kind carries MOGP_KIND_TIMES multiplies with the next row.  A maximal run of flagged rows plus the row that
 // ends it is a group (at most MOGP_GROUP_MAX rows); the Gram is the sum over groups of the product of their rows' values.
 #ifndef MOGP_KIND_TIMES
@@ -163,10 +166,14 @@ struct MomentArgs {
     const double* shape;
 };
 
-int launch_gram(const GramArgs& a, int ntiles, hipStream_t s);
+// gate: some kind of the launch is MOGP_KIND_GATE -- the radial instantiation that carries the gate code (D = 1); the others hold none of it.
+// The launchers cannot see the device-side kinds: a caller whose `kind` may hold an 8 MUST pass `gate` (mogp_model::gate_kinds, which
+// mogp_model_set_kinds keeps beside `radial`), or the row is staged as phase factors without an error.  The flag is an argument and not a
+// member of GramArgs / MomentArgs because those are the kernels' arguments: a member would move every kernel's argument layout.
+int launch_gram(const GramArgs& a, int ntiles, hipStream_t s, bool gate = false);
 // split a tile list into runs of at most `maxrun` full interior tiles (same pair and row block, consecutive columns) and the rest
 void split_strip_tiles(const std::vector<GTile>& tiles, int maxrun, std::vector<GSeg>& segs, std::vector<GTile>& rest);
-int launch_moments(const MomentArgs& a, hipStream_t s);
+int launch_moments(const MomentArgs& a, hipStream_t s, bool gate = false);
 inline size_t gz_scratch_doubles(int nrb, int ncb, int D) { return (size_t)2 * nrb * ncb * D * MOGP_GT; }
 // [first point, number of points] of every 64-point block, channel by channel: the enumeration GTile::rb / cb refers to
 void tile_blocks(const std::vector<int>& off, int C, std::vector<int>& blk);

@@ -41,6 +41,16 @@ KIND_TIMES, KIND_MASK, GROUP_MAX = 1 << 8, 0xff, 4
 # The dot-product row (A <x_a, x_b> + c)^n of LinearKernel / PolynomialKernel: A in the amplitude slot, the bias c in the Psi slot, n the shape.
 # It is the one row whose diagonal value follows the point, (A |x|^2 + c)^n, instead of being its amplitude.
 KIND_DOT = 7
+# The gate row A h(x_a) h(x_b), h(x) = sigmoid(beta (x - l)), of ChangePointsKernel: the signed steepness beta in the V slot, the location l in
+# the M slot, A = 1 (one input dimension).  Its diagonal value A h(x)^2 follows the point too: both are "point rows".
+KIND_GATE = 8
+POINT_KINDS = (KIND_DOT, KIND_GATE)
+
+
+def _sigmoid(z):
+    """1 / (1 + exp(-z)) without overflow for any finite z; the complement 1 - sigmoid(z) is _sigmoid(-z)"""
+    e = np.exp(-np.abs(z))
+    return np.where(z >= 0, 1.0, e) / (1.0 + e)
 
 
 def group_slices(kind_row):
@@ -200,8 +210,9 @@ class Kernel(ParameterHolder):
         return bool(np.any(self._spectral_kinds(D)[0]))
 
     def _pointwise(self, D):
-        """some row is a dot-product row: K(x, x) follows the point, as with an envelope, and `_point_diag` stands where `_spectral_diag` stood"""
-        return bool(np.any((self._spectral_kinds(D)[0] & KIND_MASK) == KIND_DOT))
+        """some row is a point row (dot product, gate): K(x, x) follows the point, as with an envelope, and `_point_diag` stands where
+        `_spectral_diag` stood"""
+        return bool(np.any(np.isin(self._spectral_kinds(D)[0] & KIND_MASK, POINT_KINDS)))
 
     def _spectral_diag(self, D):
         """K_diag value per channel AS THE REFERENCE RETURNS IT (constant per channel for every spectral kernel).
@@ -265,39 +276,52 @@ class Kernel(ParameterHolder):
 
     def _point_rows(self, table, Xk, D):
         """From a table with kinds (no envelope), per point k (channel c) and row t of the diagonal pair (c, c): the row's value v on the
-        diagonal -- its amplitude (every profile is 1 at zero distance, Delta = Psi = 0 there), for a dot-product row (A |x|^2 + c)^n --
-        with dv/dA and dv/dc (c: the bias in a dot-product row's Psi slot), and the groups, which are the same in every pair"""
+        diagonal -- its amplitude (every profile is 1 at zero distance, Delta = Psi = 0 there), for a dot-product row (A |x|^2 + c)^n, for
+        a gate row A h(x)^2 -- with dv / d(table column) for the columns that move it (N, T, W: the amplitude; the bias in a dot-product
+        row's Psi slot; beta and l in a gate row's V and M slots), and the groups, which are the same in every pair"""
         kind, shape = self._spectral_kinds(D)
         c = Xk[:, 0].astype(np.int64)
         rows = table[c, c]                                        # (N, T, W)
-        dot = (kind[c, c] & KIND_MASK) == KIND_DOT
+        kd = kind[c, c] & KIND_MASK
+        dot, gate = kd == KIND_DOT, kd == KIND_GATE
         x2 = np.sum(np.square(Xk[:, 1:]), axis=1)[:, None]
         n = np.where(dot, shape[c, c], 1.0)
         b = np.where(dot, rows[..., 0] * x2 + rows[..., 1], 1.0)
         db = n * b ** (n - 1.0)
-        return np.where(dot, b ** n, rows[..., 0]), np.where(dot, db * x2, 1.0), np.where(dot, db, 0.0), group_slices(kind[0, 0])
+        v, dv = np.where(dot, b ** n, rows[..., 0]), np.zeros(rows.shape)
+        dv[..., 0], dv[..., 1] = np.where(dot, db * x2, 1.0), np.where(dot, db, 0.0)
+        if np.any(gate):                                          # h = sigmoid(beta (x - l)), dh/dz = h (1 - h); one input dimension
+            A, beta, a = rows[..., 0], rows[..., 2], Xk[:, 1:2] - rows[..., 2 + D]
+            z = np.where(gate, beta * a, 0.0)
+            h2, hc = np.square(_sigmoid(z)), _sigmoid(-z)
+            v = np.where(gate, A * h2, v)
+            dv[..., 0] = np.where(gate, h2, dv[..., 0])
+            dv[..., 2] = np.where(gate, 2.0 * A * h2 * hc * a, 0.0)
+            dv[..., 2 + D] = np.where(gate, -2.0 * A * h2 * hc * beta, 0.0)
+        return v, dv, group_slices(kind[0, 0])
 
     def _point_diag(self, table, Xk, D):
         """K_diag per point.  Enveloped term table: sum_t A_cct env_t(x)   (Delta = Psi = 0 on diagonal pairs); a table with kinds: the sum
         over groups of the product of the rows' diagonal values at the point (`_point_rows`)"""
         if table.shape[3] == term_width(D):
-            v, _, _, groups = self._point_rows(table, Xk, D)
+            v, _, groups = self._point_rows(table, Xk, D)
             return sum(np.prod(v[:, a:b], axis=1) for a, b in groups)
         env, _, rows = self._point_env(table, Xk, D)
         return np.sum(rows[..., 0] * env, axis=1)
 
     def _point_diag_table_grad(self, table, Xk, D, weights=None):
         """d [ sum_k w_k K_diag(x_k) ] / d table (w = 1: what the relative jitter, gpr/model.py:244, contributes per unit of d/d mean(diag) * N)"""
-        if table.shape[3] == term_width(D):                     # kinds: the product rule inside a group, amplitude and (dot-product rows) bias
-            v, dA, dc, groups = self._point_rows(table, Xk, D)
+        if table.shape[3] == term_width(D):                     # kinds: the product rule inside a group; amplitude, a dot-product row's bias, a gate row's beta and l
+            v, dv, groups = self._point_rows(table, Xk, D)
             w = np.ones(len(Xk)) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
             c = Xk[:, 0].astype(np.int64)
             gt = np.zeros_like(table)
+            cols = [col for col in range(table.shape[3]) if col < 2 or np.any(dv[..., col])]
             for a, b in groups:
                 for t in range(a, b):
                     others = w * np.prod(np.delete(v[:, a:b], t - a, axis=1), axis=1)
-                    gt[:, :, t, 0][np.diag_indices(table.shape[0])] = np.bincount(c, weights=others * dA[:, t], minlength=table.shape[0])
-                    gt[:, :, t, 1][np.diag_indices(table.shape[0])] = np.bincount(c, weights=others * dc[:, t], minlength=table.shape[0])
+                    for col in cols:
+                        gt[:, :, t, col][np.diag_indices(table.shape[0])] = np.bincount(c, weights=others * dv[:, t, col], minlength=table.shape[0])
             return gt
         env, a, rows = self._point_env(table, Xk, D)
         if weights is not None:
@@ -457,6 +481,111 @@ class MulKernel(Kernels):
         kd = [k._spectral_diag(D) for k in self.kernels]
         for f, k in enumerate(self.kernels):
             k._spectral_diag_backward(np.asarray(gc) * np.prod([d for h, d in enumerate(kd) if h != f], axis=0), D)
+
+
+class ChangePointsKernel(Kernels):
+    """Change-point kernel (reference gpr/kernel.py:294-377): K(x, x') = sum_i a_i(x) a_i(x') k_i(x, x') over one input dimension, with
+    a_i = sigma_i (1 - sigma_{i+1}), sigma_j(x) = sigmoid(s_j (x - l_j)) at the sorted `locations` l_1 < ... < l_n (sigma_0 = 1 - sigma_{n+1} = 1)
+    and steepnesses s_j > 0, one shared or one per location.  Every weight is a product of separable factors h(x) h(x'),
+    h(x) = sigmoid(beta (x - l)): beta = +s_j the rising gate of kernel j, beta = -s_j the falling gate of kernel j - 1 (1 - sigmoid(z) =
+    sigmoid(-z)).  So every group of sub-kernel i travels with one (the end kernels) or two (the middle kernels) gate rows (kind 8)
+    appended BEHIND its own rows -- a group's first row stays a kernel row, which is the one LMC scales; a sum inside a sub-kernel
+    distributes, as in MulKernel.  At most GROUP_MAX rows per group."""
+
+    def __init__(self, locations, steepnesses=1.0, *kernels):
+        if not isinstance(locations, list):
+            locations = [locations]
+        if len(kernels) != len(locations) + 1:
+            raise ValueError("Must pass one more kernel than the number of locations points. "
+                             f"Got {len(kernels)} kernels and {len(locations)} locations points.")
+        if isinstance(steepnesses, list) and len(steepnesses) > 1:
+            if len(locations) != len(steepnesses):
+                raise ValueError("Must pass as many locations as steepness point(s). "
+                                 f"Got {len(locations)} locations and {len(steepnesses)} steepness points.")
+        if not np.array_equal(np.asarray(locations, dtype=np.float64), np.sort(np.asarray(locations, dtype=np.float64))):
+            raise ValueError("'locations' must be sorted ascendingly and 'steepnesses' should be ordered correspondingly.")
+        super().__init__(*kernels)
+        if len(self.kernels) != len(locations) + 1:
+            raise NotImplementedError("a ChangePointsKernel directly inside a ChangePointsKernel is taken apart by the base class (as in the reference, "
+                                      "whose K then fails): wrap the inner one in an AddKernel")
+        if self.output_dims is not None:
+            raise NotImplementedError("a change-point kernel over multi-output kernels is not on the MI355X spectral path: ChangePointsKernel "
+                                      "weighs single-output kernels")
+        if self.input_dims != 1:
+            raise ValueError("Must pass kernels defined over a 1D input domain.")
+        self.locations = Parameter(locations)
+        self.steepness = Parameter(steepnesses, lower=config.positive_minimum)
+
+    def _steepness_index(self, j):
+        """where location j's steepness lives in the parameter: its own entry, or the one shared value"""
+        return j if self.steepness.data.size > 1 else 0
+
+    @cached_terms
+    def _plan(self, D):
+        """(tables and kinds of the sub-kernels, the produced rows -- (i, t): row t of sub-kernel i; (-1, j, sign): the gate at location j,
+        rising (+1) or falling (-1) --, kind and shape of every produced row)"""
+        if D != 1:
+            raise ValueError("Must pass kernels defined over a 1D input domain.")
+        tabs = [k._spectral_terms(D) for k in self.kernels]
+        if any(t.shape[0] != 1 or t.shape[3] != term_width(D) for t in tabs):
+            raise NotImplementedError("a change-point kernel over enveloped (harmonizable) terms is not on the MI355X spectral path")
+        kinds = [k._spectral_kinds(D) for k in self.kernels]
+        n = len(self.kernels)
+        rows, kind, shape = [], [], []
+        for i, (kd, sh) in enumerate(kinds):
+            gates = ([(-1, i - 1, 1.0)] if i > 0 else []) + ([(-1, i, -1.0)] if i < n - 1 else [])
+            for a, b in group_slices(kd[0, 0]):
+                count = b - a + len(gates)
+                if count > GROUP_MAX:
+                    raise NotImplementedError("a change-point weight on a product of %d table rows (sub-kernel %d, %s: %d rows with its %d gate "
+                                              "row%s) is not on the MI355X spectral path: the device multiplies groups of at most %d rows"
+                                              % (b - a, i, self.kernels[i].name(), count, len(gates), "s" if len(gates) > 1 else "", GROUP_MAX))
+                rows += [(i, t) for t in range(a, b)] + gates
+                kind += [int(kd[0, 0, t]) & KIND_MASK for t in range(a, b)] + [KIND_GATE] * len(gates)
+                shape += [float(sh[0, 0, t]) for t in range(a, b)] + [0.0] * len(gates)
+                for r in range(len(kind) - count, len(kind) - 1):
+                    kind[r] |= KIND_TIMES
+        return tabs, kinds, rows, np.array(kind, dtype=np.int32), np.array(shape, dtype=np.float64)
+
+    @cached_terms
+    def _spectral_terms(self, D):
+        tabs, _, rows, _, _ = self._plan(D)
+        loc, steep = np.reshape(self.locations(), -1), np.reshape(self.steepness(), -1)
+        table = np.zeros((len(rows), term_width(D)))
+        for r, row in enumerate(rows):
+            if row[0] >= 0:
+                table[r] = tabs[row[0]][0, 0, row[1]]
+            else:                                                  # [A, Psi, V, M, Delta] = [1, 0, beta, l, 0]
+                _, j, sign = row
+                table[r, 0], table[r, 2], table[r, 2 + D] = 1.0, sign * steep[self._steepness_index(j)], loc[j]
+        return table[None, None]
+
+    @cached_terms
+    def _spectral_kinds(self, D):
+        _, _, _, kind, shape = self._plan(D)
+        return kind[None, None], shape[None, None]
+
+    def _spectral_diag(self, D):
+        raise NotImplementedError("%s has no diagonal value per channel: K(x, x) follows the point (Kernel._point_diag)" % self.name())
+
+    def _spectral_backward(self, gtable):
+        """a kernel row's gradient back to the sub-kernel row it copies; a gate row's V and M columns are d/dbeta and d/dl: into the
+        steepness (with beta's sign) and the location that the row carries.  A gate row's amplitude is not a parameter."""
+        D = 1
+        tabs, _, rows, _, _ = self._plan(D)
+        gts = [np.zeros_like(t) for t in tabs]
+        gloc, gsteep = np.zeros(self.locations.data.size), np.zeros(self.steepness.data.size)
+        for r, row in enumerate(rows):
+            if row[0] >= 0:
+                gts[row[0]][0, 0, row[1]] += gtable[0, 0, r, :term_width(D)]
+            else:
+                _, j, sign = row
+                gsteep[self._steepness_index(j)] += sign * gtable[0, 0, r, 2]
+                gloc[j] += gtable[0, 0, r, 2 + D]
+        self.locations.accumulate_grad(np.reshape(gloc, self.locations.data.shape))
+        self.steepness.accumulate_grad(np.reshape(gsteep, self.steepness.data.shape))
+        for k, g in zip(self.kernels, gts):
+            k._spectral_backward(g)
 
 
 class MixtureKernel(AddKernel):

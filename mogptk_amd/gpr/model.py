@@ -10,7 +10,7 @@ from math import erf, sqrt
 
 from .config import config
 from .parameter import Parameter, ParameterHolder
-from .kernel import Kernel, MulKernel, terms_cache, KIND_TIMES, KIND_MASK, KIND_DOT, group_diag_grad
+from .kernel import Kernel, MulKernel, ChangePointsKernel, terms_cache, KIND_TIMES, KIND_MASK, KIND_DOT, KIND_GATE, group_diag_grad
 from .likelihood import Likelihood, GaussianLikelihood
 from .mean import Mean
 
@@ -36,7 +36,7 @@ def _to_array(X):
 def _leaf_kernels(kernel):
     """the kernels of a composition that carry parameters of their own"""
     subs = getattr(kernel, "kernels", None)
-    if not subs or isinstance(kernel, MulKernel):          # a product is radial as a whole, whatever its factors are
+    if not subs or isinstance(kernel, (MulKernel, ChangePointsKernel)):      # a product, a change-point kernel: radial as a whole, whatever is inside
         return [kernel]
     return [leaf for k in subs for leaf in _leaf_kernels(k)]
 
@@ -70,7 +70,9 @@ def _gtable_from_moments(table, mom, D, lower=True, kind=None):
     """d(objective)/d(term table) from the device's gradient moments [m0, m4, m1_d, m2_d, m3_d]:
     dA = m0, dPsi = -2 pi A m4, dV_d = -1/2 A m1_d, dM_d = -2 pi A m3_d, dDelta_d = -V_d A m2_d - 2 pi M_d A m4.
     `kind` (the table's kinds, when they travelled): a dot-product row's moments are derivatives already -- dA = m0, and the bias in its Psi
-    slot gets m1_0 (an even slot, which the device keeps on diagonal channel blocks); its other columns are not parameters.
+    slot gets m1_0 (an even slot, which the device keeps on diagonal channel blocks); its other columns are not parameters.  A gate row's
+    m1_0 and m3_0 are d/dbeta and d/dl of h_a h_b: times the row's own amplitude (1 as ChangePointsKernel writes it) they are the V and M
+    columns; the other columns but the amplitude's are zero.
     lower=True: mom is indexed by lower channel pairs p = i(i+1)/2 + j (symmetric Gram, double count already
     included); lower=False: mom is indexed by all ordered pairs i*C + j (rectangular Gram)."""
     C, T = table.shape[0], table.shape[2]
@@ -97,6 +99,11 @@ def _gtable_from_moments(table, mom, D, lower=True, kind=None):
         if np.any(dot):
             g[dot, 1:] = 0.0
             g[dot, 1] = mom[..., 2][dot]
+        gate = (kind[ii, jj] & KIND_MASK) == KIND_GATE
+        if np.any(gate):
+            g[gate, 1:] = 0.0
+            g[gate, 2] = (A * mom[..., 2])[gate]
+            g[gate, 2 + D] = (A * mom[..., 2 + 2 * D])[gate]
     gt[ii, jj] = g
     return gt
 
@@ -446,8 +453,8 @@ class Exact(Model):
             h.set_kinds(None, None)               # the kernel was replaced by an all-Gaussian one with the same number of terms
         h.radial_kinds = radial
         h.group_kinds = kind if radial and np.any(kind & KIND_TIMES) else None      # product groups: _loss_impl's jitter term needs them
-        h.dot_kinds = kind if radial and self.kernel._pointwise(D) else None      # dot-product rows: _loss_impl's moments and jitter term need them
-        if _enveloped(table, D) or h.dot_kinds is not None:      # envelope, dot-product rows: the diagonal varies from point to point and enters the relative jitter (:244)
+        h.point_kinds = kind if radial and self.kernel._pointwise(D) else None      # point rows (dot product, gate): _loss_impl's moments and jitter term need them
+        if _enveloped(table, D) or h.point_kinds is not None:      # envelope, point rows: the diagonal varies from point to point and enters the relative jitter (:244)
             h.set_point_diag(self.kernel._point_diag(table, self.kernel._kernel_format(self.X), D))
             h.point_diag_set = True
         elif getattr(h, "point_diag_set", False):                # the kernel was replaced by one with a constant diagonal
@@ -510,9 +517,9 @@ class Exact(Model):
         jit_rel = self.jitter * res["trG"] / self.X.shape[0]            # d LML / d (mean diag) through the jitter term (:244)
 
         # d LML / d table for the lower channel pairs (i >= j); zero elsewhere
-        dot_kinds = getattr(self._handle, "dot_kinds", None)
-        gt = _gtable_from_moments(table, res["moments"], D, lower=True, kind=dot_kinds)
-        if _enveloped(table, D) or dot_kinds is not None:
+        point_kinds = getattr(self._handle, "point_kinds", None)
+        gt = _gtable_from_moments(table, res["moments"], D, lower=True, kind=point_kinds)
+        if _enveloped(table, D) or point_kinds is not None:
             gt += jit_rel * self.kernel._point_diag_table_grad(table, self.kernel._kernel_format(self.X), D)
         else:
             kind = getattr(self._handle, "group_kinds", None)
