@@ -137,12 +137,30 @@ int  mogp_gram_ex(mogp_ctx* ctx, int C, int D, int T, int width, const double* t
  *           m0 = sum g h_a h_b = d/dA,  m1_0 = sum g h_a h_b [(1 - h_a)(x_a - l) + (1 - h_b)(x_b - l)],  m3_0 = -beta sum g h_a h_b [(1 - h_a) + (1 - h_b)]
  *           (both even under a <-> b; the other slots 0), so d/dbeta = A m1_0 and d/dl = A m3_0 with no further factor.  Launches whose
  *           kinds hold a gate row run instantiations of the radial kernels of their own; the others contain no gate code.  K(x, x) = A h(x)^2
- *           follows the point, exactly as for kind 7: mogp_model_set_point_diag, kss_diag per test point. */
+ *           follows the point, exactly as for kind 7: mogp_model_set_point_diag, kss_diag per test point.
+ *   kind 9  the weighted inner product  A sum_d V_d x_a,d x_b,d,  D >= 2  (the reference's FunctionKernel, gpr/singleoutput.py:140-179,
+ *           K = phi(x) diag(sigma^2) phi(x')^T: the caller evaluates phi and passes the feature values as further input columns of X, the
+ *           weights sigma_f^2 in the row's V slots of those columns and 0 in the others).  Psi, M, Delta and the shape are not read, and no
+ *           cosine stands beside the row.  It is A times something: a zero amplitude silences its group, and the moments leave the row's OWN
+ *           amplitude out:  m0 = sum g sum_d V_d x_a,d x_b,d = d/dA,  m1_d = sum g x_a,d x_b,d, so d/dV_d = A m1_d with no further factor (both
+ *           even under a <-> b; the other slots 0).  K(x, x) = A sum_d V_d x_d^2 follows the point, as for kinds 7 and 8.  D counts the inputs
+ *           and the feature columns, so D >= 2; with D = 1 the kind is refused as unknown, as it always was (over one column the row would
+ *           be kind 7 of degree 1).
+ *   kind 10 the white row: A where row and column are THE SAME POINT OF THE SAME SET -- a symmetric evaluation (X2 == NULL of mogp_gram_kinds,
+ *           the exact model's K, the K_ss of a full prediction) at equal index -- and 0 elsewhere: everywhere in a rectangular evaluation,
+ *           and between two different points with equal inputs (the reference's WhiteKernel, gpr/singleoutput.py:5-35).  V, M, Psi, Delta and
+ *           the shape are not read.  In a group it multiplies like any row: White x k = diag(A k(x, x)).  m0 = sum_k g_kk, the other slots 0.
+ *           Its diagonal value is A, like a profile's: not a point row.
+ *   Kinds 5 and 6 take any D: the periodic profile reads V_0 and the row's phase (its moments are m1_0 and m3_0), the sinc profile is a
+ *   function of s.  Kind 8 stays D = 1.  Launches whose kinds hold a 9 or 10 run instantiations of the radial kernels of their own (as
+ *   launches with gate rows alone do): the others contain none of this code. */
 #define MOGP_KIND_PERIODIC 5
 #define MOGP_KIND_SINC 6
 #define MOGP_KIND_DOT 7
 #define MOGP_DOT_DEGREE_MAX 8
 #define MOGP_KIND_GATE 8
+#define MOGP_KIND_WDOT 9
+#define MOGP_KIND_WHITE 10
 #define MOGP_KIND_TIMES (1 << 8)
 int  mogp_model_set_kinds(mogp_model* m, int T, const int* kind, const double* shape);
 /* mogp_gram_ex with kinds (NULL: mogp_gram_ex itself): replaces Kernel.K of the kernels above, and of their sums, IndependentMultiOutputKernel

@@ -227,6 +227,9 @@ def _convert_kernel(bag):
     """same class, same structure, default parameter values (they are overwritten afterwards, in order)"""
     name, st = bag.cls(), bag.state()
     params = st.get("_parameters", {})
+    if name == "FunctionKernel":
+        raise NotImplementedError("checkpoint uses the kernel FunctionKernel, which holds code (its phi): a checkpoint is data, and the loader "
+                                  "runs none; build the model with gpr.FunctionKernel(phi) and assign the parameters")
     cls = getattr(_gpr, name, None)
     if cls is None:
         raise NotImplementedError("checkpoint uses the kernel %s, which this package does not have" % name)
@@ -480,7 +483,7 @@ _REF_KERNEL_MODULE = {
     "SpectralKernel": "singleoutput", "SpectralMixtureKernel": "singleoutput", "SquaredExponentialKernel": "singleoutput",
     "RationalQuadraticKernel": "singleoutput", "MaternKernel": "singleoutput", "ExponentialKernel": "singleoutput",
     "ConstantKernel": "singleoutput", "CosineKernel": "singleoutput", "PeriodicKernel": "singleoutput", "LocallyPeriodicKernel": "singleoutput",
-    "LinearKernel": "singleoutput", "PolynomialKernel": "singleoutput", "SincKernel": "singleoutput",
+    "LinearKernel": "singleoutput", "PolynomialKernel": "singleoutput", "SincKernel": "singleoutput", "WhiteKernel": "singleoutput",
     "IndependentMultiOutputKernel": "multioutput", "MultiOutputSpectralMixtureKernel": "multioutput", "CrossSpectralKernel": "multioutput",
     "LinearModelOfCoregionalizationKernel": "multioutput", "GaussianConvolutionProcessKernel": "multioutput",
     "MultiOutputHarmonizableSpectralKernel": "multioutput", "MultiOutputSpectralKernel": "multioutput",
@@ -539,6 +542,8 @@ class _Exporter:
 
     def kernel(self, k):
         name = type(k).__name__
+        if name == "FunctionKernel":
+            raise NotImplementedError("the checkpoint writer does not write the kernel FunctionKernel: it holds code (its phi), a checkpoint holds data")
         where = _REF_KERNEL_MODULE.get(name)
         if where is None or type(k) is not getattr(_gpr, name, None):
             raise NotImplementedError("the checkpoint writer does not cover the kernel %s" % name)

@@ -240,7 +240,7 @@ static int factorize_finish(mogp_model* m, const GramArgs& ga, double* lml, int6
         // distinguish NaN / Inf in the Gram from a plain indefinite matrix (reference prints which, gpr/model.py:249-252)
         int flag = 0;
         HIP_TRY(hipMemsetAsync(m->d_flag.p, 0, sizeof(int), m->st));
-        if ((rc = launch_gram(ga, (int)m->tiles.size(), m->st, m->radial && m->gate_kinds))) return rc;
+        if ((rc = launch_gram(ga, (int)m->tiles.size(), m->st, m->radial ? m->gate_kinds : 0))) return rc;
         if ((rc = launch_nonfinite_scan(m->k.A.p, Npad, N, m->d_flag.p, m->st))) return rc;
         HIP_TRY(hipMemcpyAsync(&flag, m->d_flag.p, sizeof(int), hipMemcpyDeviceToHost, m->st));
         HIP_TRY(hipStreamSynchronize(m->st));
@@ -292,19 +292,19 @@ static int factorize(mogp_model* m, const double* noise_var, const double* data_
         GramArgs gh = ga, gt = ga;
         gh.tiles = m->d_tiles_head.p; m->strip_head.attach(gh); gh.ev1 = nullptr;
         gt.tiles = m->d_tiles_tail.p; m->strip_tail.attach(gt); gt.ev0 = nullptr; gt.phases_ready = 1;
-        if ((rc = launch_gram(gh, (int)m->tiles_head.size(), m->st, m->radial && m->gate_kinds))) return rc;
+        if ((rc = launch_gram(gh, (int)m->tiles_head.size(), m->st, m->radial ? m->gate_kinds : 0))) return rc;
         if ((rc = launch_pad_identity(m->k.A.p, Npad, N, Npad, m->st))) return rc;
         if (!m->gram_ev) HIP_TRY(hipEventCreateWithFlags(&m->gram_ev, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(m->gram_ev, m->st));
         HIP_TRY(hipStreamWaitEvent(m->st2, m->gram_ev, 0));
-        if ((rc = launch_gram(gt, (int)m->tiles_tail.size(), m->st2, m->radial && m->gate_kinds))) return rc;       // spd_potri_flow enqueues the dataflow kernel behind it
+        if ((rc = launch_gram(gt, (int)m->tiles_tail.size(), m->st2, m->radial ? m->gate_kinds : 0))) return rc;       // spd_potri_flow enqueues the dataflow kernel behind it
         // ... and makes the private stream wait for this event before the first launch that reads beyond the first 512 columns (round 4: with
         // four processes on one GPU the next-diagonal update of block 0 ran BEFORE this launch had written its block: "not positive definite")
         if (!m->gram_tail_ev) HIP_TRY(hipEventCreateWithFlags(&m->gram_tail_ev, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(m->gram_tail_ev, m->st2));
         m->k.tail_ready = m->gram_tail_ev;
     } else {
-        if ((rc = launch_gram(ga, (int)m->tiles.size(), m->st, m->radial && m->gate_kinds))) return rc;
+        if ((rc = launch_gram(ga, (int)m->tiles.size(), m->st, m->radial ? m->gate_kinds : 0))) return rc;
         if ((rc = launch_pad_identity(m->k.A.p, Npad, N, Npad, m->st))) return rc;
     }
     ga.ev0 = ga.ev1 = nullptr;
@@ -445,7 +445,7 @@ int moment_pass_device(mogp_model* m, const double* kinv, double ksign) {
     ma.partial = m->d_partial.p;
     ma.phases_ready = 1;                       // ph_xx was filled by this evaluation's Gram launch: same inputs, same table
     ma.ev0 = prof_event(m, 9); ma.ev1 = prof_event(m, 10);
-    if ((rc = launch_moments(ma, m->st, m->radial && m->gate_kinds))) return rc;
+    if ((rc = launch_moments(ma, m->st, m->radial ? m->gate_kinds : 0))) return rc;
     if ((rc = launch_moment_reduce(m->d_partial.p, own ? m->d_pair_start_own.p : m->d_pair_start.p, P, T, W, D, m->d_moments.p, m->st))) return rc;
     if ((rc = launch_diagG(kinv, Npad, m->d_alpha.p, m->d_chan_off.p, C, m->d_diagG.p, m->st, ksign, rm, m->sh_rank))) return rc;
     if ((rc = mean_grad_enqueue(m, m->d_alpha.p, -1.0))) return rc;            // dp/dr = -alpha (nothing is launched without a mean table)
@@ -586,7 +586,7 @@ static int predict_core(mogp_model* m, const double* noise_var, const double* da
     if ((rc = m->d_Vt.ensure((size_t)Srow * Npad))) return rc;
     if ((rc = m->d_var.ensure(Spad))) return rc;
     HIP_TRY(hipMemcpyAsync(m->d_Ksf.p + Spad * Npad, m->d_y.p, Npad * sizeof(double), hipMemcpyDeviceToDevice, sv));
-    if ((rc = launch_gram(ga, ts.ntiles, sv, m->radial && m->gate_kinds))) return rc;
+    if ((rc = launch_gram(ga, ts.ntiles, sv, m->radial ? m->gate_kinds : 0))) return rc;
     if (mean_w) {                                                    // mu = K_sf w, before the substitution consumes K_sf
         std::vector<double> hw(Npad, 0.0);
         for (int64_t pos = 0; pos < m->N; ++pos) hw[pos] = mean_w[m->sx.perm[pos]];
@@ -696,7 +696,7 @@ static int predict_core(mogp_model* m, const double* noise_var, const double* da
     HIP_TRY(hipMemcpyAsync(m->d_ptiles.p, st_tiles.data(), st_tiles.size() * sizeof(GTile), hipMemcpyHostToDevice, m->st));
     ga.tiles = m->d_ptiles.p; ga.xc = m->d_xs.p; ga.ldxc = Spad; ga.ncols = S; ga.out = m->d_Kss.p; ga.ldo = Spad; ga.mirror = 1;
     if ((rc = m->ph_ss.prepare(ss.off, ss.off, C, m->T, Spad, Spad, m->st, ga.ph))) return rc;
-    if ((rc = launch_gram(ga, (int)st_tiles.size(), m->st, m->radial && m->gate_kinds))) return rc;
+    if ((rc = launch_gram(ga, (int)st_tiles.size(), m->st, m->radial ? m->gate_kinds : 0))) return rc;
     GemmArgs c{};
     c.A = m->d_Vt.p; c.lda = Npad; c.a_kmajor = 0; c.B = m->d_Vt.p; c.ldb = Npad; c.b_kmajor = 0;
     c.C = m->d_Kss.p; c.ldc = Spad; c.alpha = -1.0; c.beta = 1.0;

@@ -227,8 +227,9 @@ __device__ __forceinline__ void stage_item_load(StageItem<DM>& I, int which, int
 // global memory -- a generic pointer), W doubles each.
 // RAD: a launch with radial profiles (below): no Gaussian factor is split off, every term runs entry by entry (GT_GENERAL) and the staged
 // factors are the plain phase factors (times the amplitude; not for the periodic profile, whose phase is the profile's argument).
-// `kinds`: the pair's kind row (RAD only).  GATE: the instantiation that carries the gate row (below); the others hold none of its code
-template <int DM, bool AMP, bool RAD = false, bool GATE = false>
+// `kinds`: the pair's kind row (RAD only).  GATE: 1 = the instantiation that carries the gate row, 2 = the one that carries the gate,
+// weighted-dot and white rows (all below); an instantiation holds none of the code of the rows it does not carry
+template <int DM, bool AMP, bool RAD = false, int GATE = 0>
 __device__ __forceinline__ void stage_item_compute(TileLds<DM>& L, const StageItem<DM>& I, const TileCtx<DM>& X, const double* tab, int W,
                                                    int which, int t, int pnt, int D, int t0, const int* kinds = nullptr) {
     const double* row = tab + (size_t)(t0 + t) * W;
@@ -248,6 +249,7 @@ __device__ __forceinline__ void stage_item_compute(TileLds<DM>& L, const StageIt
         }
         if (deg == GT_SKIP) return;
         if (dot) return;                                        // no phase factors: the staged slots of the row are not read
+        if (GATE > 1 && (kd == MOGP_KIND_WDOT || kd == MOGP_KIND_WHITE)) return;      // nothing per point: the centres above, the tile's diagonal flag
         if (GATE && kd == MOGP_KIND_GATE) {
             // the sigmoid weight of the point, h = sigmoid(z), z = beta (x - l) (beta in the V slot, l in the M slot; D = 1), once per row / column
             // point of the tile: cu / cw carry h (the rows' times the amplitude when AMP), su / sw its complement sigmoid(-z) -- never 1 - h.
@@ -326,7 +328,7 @@ __device__ __forceinline__ void stage_item_compute(TileLds<DM>& L, const StageIt
 #define STAGE_MAP(tid) const int st_wave = __builtin_amdgcn_readfirstlane((tid) >> 6), st_which = st_wave & 1, st_tb = st_wave >> 1, st_pnt = (tid) & 63
 
 // one chunk of terms into LDS; BATCH: all items' loads first (one memory round trip), else item by item (large D: registers)
-template <int DM, bool AMP, bool BATCH, bool RAD = false, bool GATE = false>
+template <int DM, bool AMP, bool BATCH, bool RAD = false, int GATE = 0>
 __device__ __forceinline__ void stage_chunk(TileLds<DM>& L, const TileCtx<DM>& X, const GTile& tl, const double* tab, int W, int D,
                                             int C, int T, int t0, int nt, const PhaseView& v, const double* __restrict__ xr, int64_t ldxr,
                                             const double* __restrict__ xc, int64_t ldxc, int tid, const int* kinds = nullptr) {
@@ -499,6 +501,19 @@ __device__ __forceinline__ int dot_row_degree(double shape) { return __builtin_a
 // ChangePointsKernel.  h is a property of the point: the staging evaluates it (and its complement) once per row and column point into the
 // slots the phase factors take for other rows, and an entry only multiplies: cu = (A) h_a, cw = h_b, su = 1 - h_a, sw = 1 - h_b.
 
+// The weighted-dot row (MOGP_KIND_WDOT, D >= 2: check_kinds): k = A sum_d V_d x_a,d x_b,d -- the reference's FunctionKernel, whose feature values the host
+// appends to the inputs as columns of their own.  Inputs as for the dot-product row (dot_row_inner: centred inputs plus the tile centres in
+// L.Kp / L.L); the weights are the row's V.  Without the amplitude: it is A times something, and the callers place A.
+template <int DM>
+__device__ __forceinline__ double wdot_row_inner(const double (&p)[DM], const double (&q)[DM], const TileLds<DM>& L, int t, int D) {
+    double ip = L.V[t][0] * ((p[0] + L.Kp[t][0]) * (q[0] + L.L[t][0]));
+    for (int d = 1; d < D; ++d) ip = fma(L.V[t][d], (p[d] + L.Kp[t][d]) * (q[d] + L.L[t][d]), ip);
+    return ip;
+}
+// The white row (MOGP_KIND_WHITE): k = A where row and column are the SAME point of the same set, 0 elsewhere -- also between two different
+// points with equal inputs.  Only the tile lists of a symmetric launch carry GT_DIAG, on the tiles of the matrix diagonal; there a thread's
+// entry (m, n) has equal global indices when rg == cg and m == n.  `ondiag` = GT_DIAG && rg == cg.
+
 // Chunks of a radial launch end at a group end (a group never straddles two chunks): at most MOGP_TC rows from t0 on, shortened while the
 // last one still multiplies with its successor.  `kinds`: one pair's kind row -- the flags are the same in every pair.
 __device__ __forceinline__ int radial_chunk(const int* kinds, int T, int t0) {
@@ -507,10 +522,10 @@ __device__ __forceinline__ int radial_chunk(const int* kinds, int T, int t0) {
     return nt;
 }
 
-template <int DM, bool GATE = false>
+template <int DM, int GATE = 0>
 __device__ __forceinline__ void gram_term_radial(double (&acc)[4][4], const double (&p)[4][DM], const double (&q)[4][DM], const TileLds<DM>& L, int t,
                                                  int D, int kind, double shape, const double (&cu)[4], const double (&su)[4],
-                                                 const double (&cw)[4], const double (&sw)[4]) {
+                                                 const double (&cw)[4], const double (&sw)[4], bool ondiag = false) {
     const bool per = kind == MOGP_KIND_PERIODIC;
     if (kind == MOGP_KIND_DOT) {                            // the row's value is the whole entry: no amplitude in front, no cosine beside it
         const int n = dot_row_degree(shape);
@@ -525,6 +540,20 @@ __device__ __forceinline__ void gram_term_radial(double (&acc)[4][4], const doub
         for (int m = 0; m < 4; ++m)
 #pragma unroll
             for (int nn = 0; nn < 4; ++nn) acc[m][nn] = fma(cu[m], cw[nn], acc[m][nn]);
+        return;
+    }
+    if (GATE > 1 && kind == MOGP_KIND_WDOT) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int nn = 0; nn < 4; ++nn) acc[m][nn] = fma(L.A[t], wdot_row_inner<DM>(p[m], q[nn], L, t, D), acc[m][nn]);
+        return;
+    }
+    if (GATE > 1 && kind == MOGP_KIND_WHITE) {
+        if (ondiag) {
+#pragma unroll
+            for (int m = 0; m < 4; ++m) acc[m][m] += L.A[t];
+        }
         return;
     }
 #pragma unroll
@@ -543,9 +572,9 @@ __device__ __forceinline__ void gram_term_radial(double (&acc)[4][4], const doub
 // One row of a product group: prod *= k_t per entry, k_t = A phi cos theta (the amplitude rides in the staged row factors when AMPF, else
 // it is L.A[t]: the moment pass stages unit amplitudes) -- for a row whose value is A times something, the moment pass leaves the row's OWN
 // amplitude to the host and this function supplies the other rows'.  A dot-product row is not of that form and always brings its full value.
-template <int DM, bool AMPF, bool GATE = false>
+template <int DM, bool AMPF, int GATE = 0>
 __device__ __forceinline__ void group_factor_radial(double (&prod)[4][4], const double (&p)[4][DM], const double (&q)[4][DM],
-                                                    const TileLds<DM>& L, int t, int D, int kind, double shape, int rg, int cg) {
+                                                    const TileLds<DM>& L, int t, int D, int kind, double shape, int rg, int cg, bool ondiag = false) {
     const bool per = kind == MOGP_KIND_PERIODIC;
     const double A = L.A[t];
     if (kind == MOGP_KIND_DOT) {                            // the full value b^n with or without AMPF: the row's amplitude is inside the power, and
@@ -563,6 +592,20 @@ __device__ __forceinline__ void group_factor_radial(double (&prod)[4][4], const 
 #pragma unroll
             for (int nn = 0; nn < 4; ++nn) prod[m][nn] *= hu * L.cw[t][cg * 4 + nn];
         }
+        return;
+    }
+    if (GATE > 1 && kind == MOGP_KIND_WDOT) {                   // A times something, nothing staged: A from L.A with or without AMPF
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int nn = 0; nn < 4; ++nn) prod[m][nn] *= A * wdot_row_inner<DM>(p[m], q[nn], L, t, D);
+        return;
+    }
+    if (GATE > 1 && kind == MOGP_KIND_WHITE) {                  // White x k = diag(A k(x, x))
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int nn = 0; nn < 4; ++nn) prod[m][nn] *= (ondiag && m == nn) ? A : 0.0;
         return;
     }
     double cw[4], sw[4];
@@ -636,7 +679,7 @@ __device__ __forceinline__ void gram_store(const GramArgs& a, const GTile& tl, c
 // in its arithmetic (measured: 66 of 126 us).  The staged factors are double buffered in LDS: one barrier per tile.
 // RAD: the radial instantiation (a.kind / a.shape are set): same pipeline, entry-by-entry profiles.  The Gaussian instantiations (RAD = false)
 // contain nothing of it.
-template <int DT, bool RAD = false, bool GATE = false>
+template <int DT, bool RAD = false, int GATE = 0>
 __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a, int ntiles) {
     constexpr int DM = DT > 0 ? DT : MOGP_MAXD;
     constexpr bool BATCH = DT == 1;
@@ -721,6 +764,7 @@ __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a, int ntiles) {
                 // a row of zero amplitude makes its whole group zero
                 const int* kd = a.kind + (size_t)cur.pair * a.T + t0;
                 const double* sh = a.shape + (size_t)cur.pair * a.T + t0;
+                const bool ondiag = GATE > 1 && (cur.flags & GT_DIAG) && rg == cg;      // (white rows: the thread's entries (m, m) are matrix-diagonal entries)
                 for (int t = 0, te; t < nt; t = te + 1) {
                     bool skip = GRAM_DBG(a, 2);
                     for (te = t;; ++te) {
@@ -735,7 +779,7 @@ __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a, int ntiles) {
                             cu[m] = L.cu[t][rg * 4 + m]; su[m] = L.su[t][rg * 4 + m];
                             cw[m] = L.cw[t][cg * 4 + m]; sw[m] = L.sw[t][cg * 4 + m];
                         }
-                        gram_term_radial<DM, GATE>(acc, pc, qc, L, t, D, __builtin_amdgcn_readfirstlane(kd[t]) & MOGP_KIND_MASK, sh[t], cu, su, cw, sw);
+                        gram_term_radial<DM, GATE>(acc, pc, qc, L, t, D, __builtin_amdgcn_readfirstlane(kd[t]) & MOGP_KIND_MASK, sh[t], cu, su, cw, sw, ondiag);
                         continue;
                     }
                     double prod[4][4];
@@ -744,7 +788,7 @@ __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a, int ntiles) {
 #pragma unroll
                         for (int n = 0; n < 4; ++n) prod[m][n] = 1.0;
                     for (int f = t; f <= te; ++f)
-                        group_factor_radial<DM, true, GATE>(prod, pc, qc, L, f, D, __builtin_amdgcn_readfirstlane(kd[f]) & MOGP_KIND_MASK, sh[f], rg, cg);
+                        group_factor_radial<DM, true, GATE>(prod, pc, qc, L, f, D, __builtin_amdgcn_readfirstlane(kd[f]) & MOGP_KIND_MASK, sh[f], rg, cg, ondiag);
 #pragma unroll
                     for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -1217,7 +1261,7 @@ void split_strip_tiles(const std::vector<GTile>& tiles, int maxrun, std::vector<
     }
 }
 
-int launch_gram(const GramArgs& a0, int ntiles, hipStream_t s, bool gate) {
+int launch_gram(const GramArgs& a0, int ntiles, hipStream_t s, int rows) {
     if (ntiles <= 0) return 0;
     GramArgs a = a0;
     if (a.W <= 0) a.W = 2 + 3 * a.D;
@@ -1238,9 +1282,16 @@ int launch_gram(const GramArgs& a0, int ntiles, hipStream_t s, bool gate) {
     if (a.kind) {                                            // radial profiles: every tile of the list through the radial general kernel
         if (!a.shape) { set_error("launch_gram: kinds without shapes"); return -1; }
         if (a.W != 2 + 3 * a.D) { set_error("launch_gram: radial profiles do not combine with enveloped term rows"); return -1; }
-        if (gate && a.D != 1) { set_error("launch_gram: gate rows take one input dimension"); return -1; }
-        if (gate) {                                          // (the instantiations below hold no gate code)
-            hipLaunchKernelGGL((k_gram<1, true, true>), dim3(grid), dim3(256), dyn, s, a, ntiles);
+        if (rows == 1 && a.D != 1) { set_error("launch_gram: gate rows take one input dimension"); return -1; }
+        if (rows == 1) {                                     // gate rows only (the instantiations below hold no gate code)
+            hipLaunchKernelGGL((k_gram<1, true, 1>), dim3(grid), dim3(256), dyn, s, a, ntiles);
+        } else if (rows > 1) {                               // weighted-dot or white rows, with or without gate rows
+        switch (a.D) {
+            case 1: hipLaunchKernelGGL((k_gram<1, true, 2>), dim3(grid), dim3(256), dyn, s, a, ntiles); break;
+            case 2: hipLaunchKernelGGL((k_gram<2, true, 2>), dim3(grid), dim3(256), dyn, s, a, ntiles); break;
+            case 3: hipLaunchKernelGGL((k_gram<3, true, 2>), dim3(grid), dim3(256), dyn, s, a, ntiles); break;
+            default: hipLaunchKernelGGL((k_gram<0, true, 2>), dim3(grid), dim3(256), dyn, s, a, ntiles); break;
+        }
         } else {
         switch (a.D) {
             case 1: hipLaunchKernelGGL((k_gram<1, true>), dim3(grid), dim3(256), dyn, s, a, ntiles); break;
@@ -1357,13 +1408,14 @@ __device__ __forceinline__ void moment_term(double* mom, const double (&g)[4][4]
 }
 
 // the radial form of moment_term (exact mode, no envelope, no input gradients): phi weighs m0, m4, m3_d; psi = -2 dphi/ds weighs m1_d, m2_d
-template <int DM, bool GATE = false>
+template <int DM, int GATE = 0>
 __device__ __forceinline__ void moment_term_radial(double* mom, const double (&g)[4][4], const double (&p)[4][DM], const double (&q)[4][DM],
                                                    const TileLds<DM>& L, int t, int D, int kind, double shape,
-                                                   const double (&cu)[4], const double (&su)[4], const double (&cw)[4], const double (&sw)[4]) {
+                                                   const double (&cu)[4], const double (&su)[4], const double (&cw)[4], const double (&sw)[4],
+                                                   bool ondiag = false) {
     const double* V = L.V[t];
     const double* s = L.s[t];
-    const bool per = kind == MOGP_KIND_PERIODIC;             // (D = 1: the moment slots are 0, 1, 2, 3, 4)
+    const bool per = kind == MOGP_KIND_PERIODIC;             // (it reads V_0 and the row's phase: m1_0 and m3_0, slots 2 and 2 + 2 D)
     if (kind == MOGP_KIND_DOT) {
         // k = b^n, b = A <x_a, x_b> + c:  m0 = sum g n b^(n-1) <x_a, x_b> = d/dA,  m1_0 = sum g n b^(n-1) = d/dc (slots 0 and 2: both even in tau,
         // k_moment_reduce keeps them on diagonal channel blocks); the other slots stay 0
@@ -1399,6 +1451,30 @@ __device__ __forceinline__ void moment_term_radial(double* mom, const double (&g
         mom[4] = fma(-V[0], m3, mom[4]);
         return;
     }
+    if (GATE > 1 && kind == MOGP_KIND_WDOT) {
+        // k = sum_d V_d x_a,d x_b,d (the row's own A is the host's): m0 = sum g k = d/dA, m1_d = sum g x_a,d x_b,d = d/dV_d / A (slots 0 and 2 + d: even
+        // under a <-> b); the other slots stay 0
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int nn = 0; nn < 4; ++nn) {
+                double k = 0.0;
+                for (int d = 0; d < D; ++d) {
+                    const double xx = (p[m][d] + L.Kp[t][d]) * (q[nn][d] + L.L[t][d]);
+                    mom[2 + d] = fma(g[m][nn], xx, mom[2 + d]);
+                    k = fma(V[d], xx, k);
+                }
+                mom[0] = fma(g[m][nn], k, mom[0]);
+            }
+        return;
+    }
+    if (GATE > 1 && kind == MOGP_KIND_WHITE) {                  // m0 = sum_k g_kk; the other slots stay 0
+        if (ondiag) {
+#pragma unroll
+            for (int m = 0; m < 4; ++m) mom[0] += g[m][m];
+        }
+        return;
+    }
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
 #pragma unroll
@@ -1417,7 +1493,7 @@ __device__ __forceinline__ void moment_term_radial(double* mom, const double (&g
                 mom[0] += ge;
                 mom[1] += ks;
                 mom[2] = fma(ge, 2.0 * (1.0 - cc), mom[2]);
-                mom[4] = fma(u[0], ks, mom[4]);
+                mom[2 + 2 * D] = fma(u[0], ks, mom[2 + 2 * D]);
                 continue;
             }
             radial_profile<true>(kind, shape, arg, phi, psi);
@@ -1441,7 +1517,7 @@ __device__ __forceinline__ void moment_term_radial(double* mom, const double (&g
 // (round 4: cutting the registers to three or four waves per SIMD -- __launch_bounds__(256, 3 / 4) -- costs 81 / 92 spilled VGPRs; the pressure is
 // the tile's adjoint block (g: 32 VGPRs), the staged factors and the staging prefetch, not the Horner chains)
 // RAD: the radial instantiation (a.kind / a.shape are set; DENSE, ZG and ENV are false); the others contain nothing of it.
-template <int DT, bool DENSE, bool ZG, bool ENV, bool RAD = false, bool GATE = false>
+template <int DT, bool DENSE, bool ZG, bool ENV, bool RAD = false, int GATE = 0>
 __global__ __launch_bounds__(256, (DT == 1 && !RAD ? 2 : 1)) void k_moments(MomentArgs a) {      // (RAD, D = 1: the library exps push two workgroups per CU into scratch)
     static_assert(!RAD || (!DENSE && !ZG && !ENV), "radial moments: exact mode only");
     constexpr int DM = DT > 0 ? DT : MOGP_MAXD;
@@ -1517,6 +1593,7 @@ __global__ __launch_bounds__(256, (DT == 1 && !RAD ? 2 : 1)) void k_moments(Mome
 
     int nred = 0;                                            // reductions done so far (selects the staging buffer)
     int tg = 0, te = -1;                                     // RAD: the product group [tg, te] (chunk-relative) that row t belongs to
+    const bool ondiag = GATE > 1 && (tl.flags & GT_DIAG) && rg == cg;      // (white rows: the thread's entries (m, m) are matrix-diagonal entries)
     for (int t0 = 0, nt; t0 < a.T; t0 += RAD ? nt : MOGP_TC) {
         if constexpr (RAD) nt = radial_chunk(a.kind, a.T, t0); else nt = min(MOGP_TC, a.T - t0);
         if (t0 > 0) __syncthreads();                         // the first chunk has nothing to wait for
@@ -1555,10 +1632,10 @@ __global__ __launch_bounds__(256, (DT == 1 && !RAD ? 2 : 1)) void k_moments(Mome
 #pragma unroll
                         for (int n = 0; n < 4; ++n) wg[m][n] = g[m][n];
                     for (int h = tg; h <= te; ++h)
-                        if (h != t) group_factor_radial<DM, false, GATE>(wg, p, q, L, h, D, __builtin_amdgcn_readfirstlane(kd[h]) & MOGP_KIND_MASK, sh[h], rg, cg);
-                    moment_term_radial<DM, GATE>(mom, wg, p, q, L, t, D, kind, sh[t], cu, su, cw, sw);
+                        if (h != t) group_factor_radial<DM, false, GATE>(wg, p, q, L, h, D, __builtin_amdgcn_readfirstlane(kd[h]) & MOGP_KIND_MASK, sh[h], rg, cg, ondiag);
+                    moment_term_radial<DM, GATE>(mom, wg, p, q, L, t, D, kind, sh[t], cu, su, cw, sw, ondiag);
                 } else {
-                    moment_term_radial<DM, GATE>(mom, g, p, q, L, t, D, kind, sh[t], cu, su, cw, sw);
+                    moment_term_radial<DM, GATE>(mom, g, p, q, L, t, D, kind, sh[t], cu, su, cw, sw, ondiag);
                 }
             } else
             switch (deg) {
@@ -1854,7 +1931,7 @@ static int launch_moments_t(const MomentArgs& a, hipStream_t s) {
     return 0;
 }
 
-int launch_moments(const MomentArgs& a0, hipStream_t s, bool gate) {
+int launch_moments(const MomentArgs& a0, hipStream_t s, int rows) {
     if (a0.ntiles <= 0) return 0;
     MomentArgs a = a0;
     if (a.W <= 0) a.W = 2 + 3 * a.D;
@@ -1867,9 +1944,16 @@ int launch_moments(const MomentArgs& a0, hipStream_t s, bool gate) {
         if (!a.shape) { set_error("launch_moments: kinds without shapes"); return -1; }
         if (a.G != nullptr || env) { set_error("launch_moments: radial profiles run in exact mode without an envelope only"); return -1; }
         if (a.ev0) HIP_TRY(hipEventRecord(a.ev0, s));
-        if (gate && a.D != 1) { set_error("launch_moments: gate rows take one input dimension"); return -1; }
-        if (gate) {
-            hipLaunchKernelGGL((k_moments<1, false, false, false, true, true>), dim3(a.ntiles), dim3(256), 0, s, a);
+        if (rows == 1 && a.D != 1) { set_error("launch_moments: gate rows take one input dimension"); return -1; }
+        if (rows == 1) {
+            hipLaunchKernelGGL((k_moments<1, false, false, false, true, 1>), dim3(a.ntiles), dim3(256), 0, s, a);
+        } else if (rows > 1) {
+        switch (a.D) {
+            case 1: hipLaunchKernelGGL((k_moments<1, false, false, false, true, 2>), dim3(a.ntiles), dim3(256), 0, s, a); break;
+            case 2: hipLaunchKernelGGL((k_moments<2, false, false, false, true, 2>), dim3(a.ntiles), dim3(256), 0, s, a); break;
+            case 3: hipLaunchKernelGGL((k_moments<3, false, false, false, true, 2>), dim3(a.ntiles), dim3(256), 0, s, a); break;
+            default: hipLaunchKernelGGL((k_moments<0, false, false, false, true, 2>), dim3(a.ntiles), dim3(256), 0, s, a); break;
+        }
         } else {
         switch (a.D) {
             case 1: hipLaunchKernelGGL((k_moments<1, false, false, false, true>), dim3(a.ntiles), dim3(256), 0, s, a); break;

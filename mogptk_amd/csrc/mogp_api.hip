@@ -553,10 +553,11 @@ const char* check_kinds(const int* kind, const double* shape, int C, int D, int 
     const size_t n = (size_t)C * C * T;
     for (size_t i = 0; i < n; ++i) {
         const int k = kind[i] & MOGP_KIND_MASK;
-        if (kind[i] < 0 || (kind[i] & ~(MOGP_KIND_MASK | MOGP_KIND_TIMES)) || k > MOGP_KIND_GATE) return "unknown kind";
-        if (k == MOGP_KIND_PERIODIC && D != 1) return "the periodic profile takes one input dimension";
-        if (k == MOGP_KIND_SINC && D != 1) return "the sinc profile takes one input dimension";
+        if (kind[i] < 0 || (kind[i] & ~(MOGP_KIND_MASK | MOGP_KIND_TIMES)) || k > MOGP_KIND_WHITE) return "unknown kind";
         if (k == MOGP_KIND_GATE && D != 1) return "the gate row takes one input dimension";
+        // a weighted-dot row stands over the model's own input columns AND the feature columns behind them: with one column there is no such
+        // row (over a single input it would be the dot-product row of degree 1), and 9 stays the unknown kind it has always been there
+        if (k == MOGP_KIND_WDOT && D < 2) return "unknown kind in one input dimension: a weighted-dot row takes the inputs and at least one feature column, D >= 2";
         *any |= kind[i] != MOGP_KIND_GAUSS;
     }
     if (!*any) return nullptr;
@@ -587,8 +588,9 @@ namespace mogp { double table_diag_points(const mogp_model* m, const SortedX& pt
     const int D = m->D, W = m->Wt, C = m->C;
     double s = 0.0;
     if (W == 2 + 3 * D && m->radial && m->point_kinds) {
-        // point rows: a dot-product row's diagonal value at the point x is (A |x|^2 + c)^n, a gate row's A h(x)^2 (its amplitude for every other
-        // row: the profiles are 1 at zero distance), a group's the product of its rows', the diagonal the sum over groups
+        // point rows: a dot-product row's diagonal value at the point x is (A |x|^2 + c)^n, a gate row's A h(x)^2, a weighted-dot row's
+        // A sum_d V_d x_d^2 (its amplitude for every other row: the profiles are 1 at zero distance, a white row is A on the diagonal), a group's
+        // the product of its rows', the diagonal the sum over groups
         for (int c = 0; c < C; ++c) {
             const double* tab = m->table.data() + (size_t)(c * C + c) * m->T * W;
             const int* kd = m->hkind.data() + (size_t)(c * C + c) * m->T;
@@ -603,6 +605,10 @@ namespace mogp { double table_diag_points(const mogp_model* m, const SortedX& pt
                         const double b = r[0] * x2 + r[1];
                         v = b;
                         for (int k = 1; k < (int)sh[t]; ++k) v *= b;
+                    } else if ((kd[t] & MOGP_KIND_MASK) == MOGP_KIND_WDOT) {      // A sum_d V_d x_d^2
+                        double q = 0.0;
+                        for (int d = 0; d < D; ++d) { const double x = pts.xs[(size_t)d * pts.Mpad + pos]; q += r[2 + d] * x * x; }
+                        v = r[0] * q;
                     } else if ((kd[t] & MOGP_KIND_MASK) == MOGP_KIND_GATE) {      // h = sigmoid(z) without overflow, as the staging forms it (D = 1)
                         const double z = r[2] * (pts.xs[pos] - r[3]), e = std::exp(-std::fabs(z));
                         const double h = z >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
@@ -813,7 +819,7 @@ int mogp_model_set_terms_ex(mogp_model* m, int T, int width, const double* table
     const size_t n = (size_t)m->C * m->C * T * W;
     for (size_t i = 0; i < n; ++i)
         if (!std::isfinite(table[i])) return fail(MOGP_ENONFINITE, "spectral term table has non-finite entries (kernel parameters diverged)");
-    if (T != m->T) m->radial = m->point_kinds = m->gate_kinds = false;           // kinds belong to a table shape (mogp_model_set_kinds)
+    if (T != m->T) { m->radial = m->point_kinds = false; m->gate_kinds = 0; }       // kinds belong to a table shape (mogp_model_set_kinds)
     m->T = T;
     m->Wt = W;
     if (m->tw) m->tw->pred_valid = false;       // mogp_sparse_predict_cov combines the last prediction's panels with the CURRENT table: a new table ends that
@@ -835,14 +841,16 @@ int mogp_model_set_kinds(mogp_model* m, int T, const int* kind, const double* sh
     const size_t n = (size_t)m->C * m->C * T;
     bool any = false;
     if (const char* bad = check_kinds(kind, shape, m->C, m->D, T, &any)) return fail(MOGP_EINVAL, std::string("mogp_model_set_kinds: ") + bad);
-    m->radial = false; m->point_kinds = false; m->gate_kinds = false;
+    m->radial = false; m->point_kinds = false; m->gate_kinds = 0;
     if (!any) return MOGP_OK;                   // all Gaussian: as if never called
     if (m->Wt != 2 + 3 * m->D) return fail(MOGP_EINVAL, "mogp_model_set_kinds: radial profiles do not combine with enveloped term rows");
     m->hkind.assign(kind, kind + n);            // table_diag needs the groups on the host
     m->hshape.assign(shape, shape + n);
-    for (size_t i = 0; i < n; ++i) m->gate_kinds |= (kind[i] & MOGP_KIND_MASK) == MOGP_KIND_GATE;
-    for (size_t i = 0; i < n; ++i) m->point_kinds |= (kind[i] & MOGP_KIND_MASK) == MOGP_KIND_DOT;
-    m->point_kinds |= m->gate_kinds;
+    for (size_t i = 0; i < n; ++i) {
+        const int k = kind[i] & MOGP_KIND_MASK;
+        m->point_kinds |= k == MOGP_KIND_DOT || k == MOGP_KIND_GATE || k == MOGP_KIND_WDOT;        // rows whose diagonal follows the point
+    }
+    m->gate_kinds = extra_rows(kind, n);
     int rc;
     if ((rc = use_device(m->ctx))) return rc;
     if ((rc = m->d_kind.ensure(n))) return rc;
@@ -924,9 +932,7 @@ int mogp_gram_kinds(mogp_ctx* ctx, int C, int D, int T, int width, const double*
         G_HIP(dev_upload(dshape.p, shape, (size_t)C * C * T * sizeof(double)));
         ga.kind = dkind.p; ga.shape = dshape.p;
     }
-    bool gate = false;
-    if (radial) for (size_t i = 0; i < (size_t)C * C * T; ++i) gate |= (kind[i] & MOGP_KIND_MASK) == MOGP_KIND_GATE;
-    G_TRY(launch_gram(ga, (int)tiles.size(), nullptr, gate));
+    G_TRY(launch_gram(ga, (int)tiles.size(), nullptr, radial ? extra_rows(kind, (size_t)C * C * T) : 0));
     G_HIP(hipDeviceSynchronize());
     if (s1.identity && sc.identity) {
         G_HIP(hipMemcpy(K_out, dout.p, (size_t)R * Cc * sizeof(double), hipMemcpyDeviceToHost));

@@ -28,6 +28,10 @@
 #ifndef MOGP_KIND_GATE
 #define MOGP_KIND_GATE 8       // A h(x_a) h(x_b), h(x) = sigmoid(V (x - M)): the separable sigmoid weight of a change-point kernel (D = 1; its diagonal follows the point)
 #endif
+#ifndef MOGP_KIND_WDOT
+#define MOGP_KIND_WDOT 9       // A sum_d V_d x_a,d x_b,d: the weighted inner product of explicit basis functions, which travel as input columns (D >= 2; its diagonal follows the point)
+#define MOGP_KIND_WHITE 10     // A where row and column are the same point of the same set (a symmetric launch, equal global index), 0 elsewhere
+#endif
 // Product groups: a row whose kind carries MOGP_KIND_TIMES multiplies with the next row.  A maximal run of flagged rows plus the row that
 // ends it is a group (at most MOGP_GROUP_MAX rows); the Gram is the sum over groups of the product of their rows' values.
 #ifndef MOGP_KIND_TIMES
@@ -166,14 +170,25 @@ struct MomentArgs {
     const double* shape;
 };
 
-// gate: some kind of the launch is MOGP_KIND_GATE -- the radial instantiation that carries the gate code (D = 1); the others hold none of it.
-// The launchers cannot see the device-side kinds: a caller whose `kind` may hold an 8 MUST pass `gate` (mogp_model::gate_kinds, which
+// rows: 0 = no kind of the launch is MOGP_KIND_GATE, MOGP_KIND_WDOT or MOGP_KIND_WHITE; 1 = gate rows only -- the radial instantiation that
+// carries the gate code alone (D = 1); 2 = weighted-dot or white rows, with or without gate rows -- the instantiations that carry all three
+// (any D).  An instantiation holds none of the code of the rows it does not carry (mogp::extra_rows scans a kind array).
+// The launchers cannot see the device-side kinds: a caller whose `kind` may hold an 8, 9 or 10 MUST pass `rows` (mogp_model::gate_kinds, which
 // mogp_model_set_kinds keeps beside `radial`), or the row is staged as phase factors without an error.  The flag is an argument and not a
 // member of GramArgs / MomentArgs because those are the kernels' arguments: a member would move every kernel's argument layout.
-int launch_gram(const GramArgs& a, int ntiles, hipStream_t s, bool gate = false);
+int launch_gram(const GramArgs& a, int ntiles, hipStream_t s, int rows = 0);
 // split a tile list into runs of at most `maxrun` full interior tiles (same pair and row block, consecutive columns) and the rest
 void split_strip_tiles(const std::vector<GTile>& tiles, int maxrun, std::vector<GSeg>& segs, std::vector<GTile>& rest);
-int launch_moments(const MomentArgs& a, hipStream_t s, bool gate = false);
+int launch_moments(const MomentArgs& a, hipStream_t s, int rows = 0);
+inline int extra_rows(const int* kind, size_t n) {
+    int rows = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const int k = kind[i] & MOGP_KIND_MASK;
+        if (k == MOGP_KIND_WDOT || k == MOGP_KIND_WHITE) return 2;
+        if (k == MOGP_KIND_GATE) rows = 1;
+    }
+    return rows;
+}
 inline size_t gz_scratch_doubles(int nrb, int ncb, int D) { return (size_t)2 * nrb * ncb * D * MOGP_GT; }
 // [first point, number of points] of every 64-point block, channel by channel: the enumeration GTile::rb / cb refers to
 void tile_blocks(const std::vector<int>& off, int C, std::vector<int>& blk);

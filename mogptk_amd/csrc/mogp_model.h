@@ -318,13 +318,13 @@ struct mogp_model {
     std::vector<GTile> tiles;
     std::vector<int> pair_start;
     std::vector<double> table;          // host copy [C*C*T*W]
-    bool gate_kinds = false;            // some row is a gate row (MOGP_KIND_GATE): the Gram and moment launches take the radial instantiation that carries the gate code
+    int gate_kinds = 0;                 // the `rows` argument of the Gram and moment launches (mogp::extra_rows): 1 = some row is a gate row, 2 = some row is a weighted-dot or white row
     bool radial = false;                // mogp_model_set_kinds: some (pair, term) has a non-Gaussian profile; d_kind / d_shape [C*C*T] then hold them
     mogp::DevBuf<int> d_kind;
     std::vector<int> hkind;             // host copy of the kinds while `radial` (table_diag: a product group's diagonal is the product of its amplitudes)
     mogp::DevBuf<double> d_shape;
     std::vector<double> hshape;         // host copy of the shapes while `radial` (the degree of a dot-product row)
-    bool point_kinds = false;           // some row is a dot-product or gate row (MOGP_KIND_DOT, MOGP_KIND_GATE): K(x, x) follows the point, as with an envelope
+    bool point_kinds = false;           // some row is a dot-product, gate or weighted-dot row (MOGP_KIND_DOT, _GATE, _WDOT): K(x, x) follows the point, as with an envelope
     hipStream_t st = nullptr;           // critical-path stream (high priority)
     hipStream_t st2 = nullptr;          // bulk trailing updates of the fused schedule (CU-masked: everything but the reserved CUs)
     hipStream_t st2u = nullptr;         // bulk trailing updates over ALL CUs, for flop-bound sizes (MOGP_CHAIN_BOUND_TILES)

@@ -354,7 +354,7 @@ int mogp_exact_predict_sharded(mogp_model* m, const double* noise_var, const dou
     if ((rc = m->d_pred_tasks.ensure(std::max<size_t>(tasks.size(), 1)))) return rc;
     if (!tasks.empty()) HIP_TRY(hipMemcpyAsync(m->d_pred_tasks.p, tasks.data(), tasks.size() * sizeof(GemmTask), hipMemcpyHostToDevice, m->st));
     HIP_TRY(hipMemsetAsync(m->d_var.p, 0, 2 * Spad * sizeof(double), m->st));
-    if ((rc = launch_gram(ga, ts.ntiles, m->st, m->radial && m->gate_kinds))) return rc;
+    if ((rc = launch_gram(ga, ts.ntiles, m->st, m->radial ? m->gate_kinds : 0))) return rc;
     if ((rc = launch_gemv_rows(m->d_Ksf.p, Npad, Spad, Npad, m->d_alpha.p, m->d_mu.p, m->st))) return rc;            // mu = K_sf alpha (alpha is complete on every rank)
     if (nown > 0) {
         GemmArgs g{};

@@ -44,7 +44,12 @@ KIND_DOT = 7
 # The gate row A h(x_a) h(x_b), h(x) = sigmoid(beta (x - l)), of ChangePointsKernel: the signed steepness beta in the V slot, the location l in
 # the M slot, A = 1 (one input dimension).  Its diagonal value A h(x)^2 follows the point too: both are "point rows".
 KIND_GATE = 8
-POINT_KINDS = (KIND_DOT, KIND_GATE)
+# The weighted-dot row A sum_d V_d x_a,d x_b,d of FunctionKernel: the basis functions' values are input columns of their own behind the
+# model's inputs, V holds the weights on those columns; its diagonal A sum_d V_d x_d^2 follows the point.  The white row of WhiteKernel: A
+# where row and column are the same point of the same set, 0 elsewhere; its diagonal is A, like a profile's.
+KIND_WDOT, KIND_WHITE = 9, 10
+POINT_KINDS = (KIND_DOT, KIND_GATE, KIND_WDOT)
+MAXD = 8                                                    # input columns of the device (MOGP_MAXD), feature columns included
 
 
 def _sigmoid(z):
@@ -187,10 +192,88 @@ class Kernel(ParameterHolder):
         return 1 if self.output_dims is None else self.output_dims
 
     def _kernel_format(self, X):
-        """single-output kernels have no channel column: prepend channel 0"""
+        """single-output kernels have no channel column: prepend channel 0.  Behind the inputs: the feature columns phi_k(x) of every
+        distinct FunctionKernel leaf, in leaf order (none: the array as it was)"""
         if self.output_dims is None:
-            return np.concatenate([np.zeros((X.shape[0], 1)), X], axis=1)
-        return X
+            X = np.concatenate([np.zeros((X.shape[0], 1)), X], axis=1)
+        leaves = self._feature_leaves()
+        if not leaves:
+            return X
+        x = X[:, 1:]
+        return np.concatenate([X] + [k._phi_values(x) for k in leaves], axis=1)
+
+    # -- feature columns (FunctionKernel, DESIGN 1b): the composition's table, kinds and gradient keep the kernels' own D; the device sees D + F
+    def _feature_leaves(self):
+        """the distinct FunctionKernel leaves of the composition in leaf order; each learns the offset of its columns among the feature columns"""
+        out = []
+
+        def walk(k):
+            if hasattr(k, "_phi_values") and not any(k is o for o in out):
+                out.append(k)
+            for s in getattr(k, "kernels", None) or []:
+                walk(s)
+        walk(self)
+        off = 0
+        for k in out:
+            k._feature_offset = off
+            off += k._features()
+        return out
+
+    def _device_terms(self, Dd):
+        """(table, kind, shape, D) for inputs of Dd device columns: the composition's own D = Dd - F, its kinds and shapes, and its table re-laid
+        to Dd columns -- V, M, Delta widened with zeros, and the magnitude of its leaf in the V slots of every weighted-dot row.  Without a
+        FunctionKernel: the kernel's own arrays.  What the device cannot carry is refused here, before any device call."""
+        leaves = self._feature_leaves()
+        F = sum(k._features() for k in leaves)
+        D = Dd - F
+        if leaves and Dd > MAXD:
+            raise NotImplementedError("the basis functions of a FunctionKernel travel as input columns: %d input dimension%s and %d features make %d "
+                                      "columns, the device takes %d; use fewer basis functions (sum features that share a weight inside phi)"
+                                      % (D, "" if D == 1 else "s", F, Dd, MAXD))
+        table = self._spectral_terms(D)
+        kind, shape = self._spectral_kinds(D)
+        if not leaves:
+            return table, kind, shape, D
+        kd = kind & KIND_MASK
+        if np.any(kd == KIND_DOT):
+            raise NotImplementedError("LinearKernel / PolynomialKernel beside a FunctionKernel is not on the MI355X spectral path: the dot-product "
+                                      "row sums over every input column of the device, the feature columns included; put x among the features "
+                                      "instead (phi = [x, ...] is the linear kernel)")
+        if np.any(kd == KIND_GATE):
+            raise NotImplementedError("ChangePointsKernel in a model that holds a FunctionKernel is not on the MI355X spectral path: gate rows take "
+                                      "one input column on the device; weigh the basis functions by the sigmoid inside phi instead")
+        if table.shape[3] > term_width(D):
+            raise NotImplementedError("a sum of enveloped (harmonizable) terms and a FunctionKernel is not on the HIP path")
+        wide = np.zeros(table.shape[:3] + (term_width(Dd),))
+        wide[..., :2] = table[..., :2]
+        for b in range(3):
+            wide[..., 2 + b * Dd:2 + b * Dd + D] = table[..., 2 + b * D:2 + (b + 1) * D]
+        for k in leaves:
+            rows = (kd == KIND_WDOT) & (shape == k._feature_offset)
+            c0 = 2 + D + k._feature_offset
+            wide[rows, c0:c0 + k._features()] = np.reshape(k.magnitude(), -1)
+        return wide, kind, shape, D
+
+    def _table_backward(self, gtable):
+        """d loss / d (the table `_device_terms` returned) -> `.grad`: a weighted-dot row's V columns on its leaf's feature columns are
+        d / d magnitude (every copy of the row accumulates), the rest narrows back to the kernels' own columns for `_spectral_backward`"""
+        leaves = self._feature_leaves()
+        if not leaves:
+            return self._spectral_backward(gtable)
+        F = sum(k._features() for k in leaves)
+        Dd = (gtable.shape[3] - 2) // 3
+        D = Dd - F
+        kind, shape = self._spectral_kinds(D)
+        kd = kind & KIND_MASK
+        for k in leaves:
+            rows = (kd == KIND_WDOT) & (shape == k._feature_offset)
+            c0 = 2 + D + k._feature_offset
+            k.magnitude.accumulate_grad(np.reshape(np.sum(gtable[rows][:, c0:c0 + k._features()], axis=0), k.magnitude.data.shape))
+        own = np.zeros(gtable.shape[:3] + (term_width(D),))
+        own[..., :2] = gtable[..., :2]
+        for b in range(3):
+            own[..., 2 + b * D:2 + (b + 1) * D] = gtable[..., 2 + b * Dd:2 + b * Dd + D]
+        self._spectral_backward(own)
 
     def _spectral_terms(self, D):
         raise NotImplementedError("%s is not on the MI355X spectral path (MOSM / SM / CSM are)" % self.name())
@@ -207,12 +290,17 @@ class Kernel(ParameterHolder):
 
     def _radial(self, D):
         """some term has a non-Gaussian profile: only then do kinds travel to the device"""
-        return bool(np.any(self._spectral_kinds(D)[0]))
+        return bool(np.any(self._spectral_kinds(self._own_dims(D))[0]))
 
     def _pointwise(self, D):
         """some row is a point row (dot product, gate): K(x, x) follows the point, as with an envelope, and `_point_diag` stands where
         `_spectral_diag` stood"""
-        return bool(np.any(np.isin(self._spectral_kinds(D)[0] & KIND_MASK, POINT_KINDS)))
+        return bool(np.any(np.isin(self._spectral_kinds(self._own_dims(D))[0] & KIND_MASK, POINT_KINDS)))
+
+    def _own_dims(self, D):
+        """the composition's own input dimensions when D counts the feature columns of its FunctionKernel leaves as well (D itself otherwise)"""
+        F = sum(k._features() for k in self._feature_leaves())
+        return D - F if F and self.input_dims is not None and D == self.input_dims + F else D
 
     def _spectral_diag(self, D):
         """K_diag value per channel AS THE REFERENCE RETURNS IT (constant per channel for every spectral kernel).
@@ -245,10 +333,9 @@ class Kernel(ParameterHolder):
         from .._lib import gram
         X1k = self._kernel_format(np.asarray(X1, dtype=np.float64))
         X2k = None if X2 is None else self._kernel_format(np.asarray(X2, dtype=np.float64))
-        D = X1k.shape[1] - 1
+        D = X1k.shape[1] - 1                                      # the device's columns: the feature columns of a FunctionKernel included
         with terms_cache():
-            table = self._spectral_terms(D)
-            kind, shape = self._spectral_kinds(D)
+            table, kind, shape, _ = self._device_terms(D)
         if not np.any(kind):
             return gram(config.device, self._channels(), D, table, X1k, X2k)
         if table.shape[3] > term_width(D):
@@ -259,10 +346,10 @@ class Kernel(ParameterHolder):
         """reference gpr/kernel.py:152-163, MO :483-495.  Constant per channel for every stationary spectral kernel; with an
         envelope (MOHSM) it follows the points."""
         X1k = self._kernel_format(np.asarray(X1, dtype=np.float64))
-        D = X1k.shape[1] - 1
-        table = self._spectral_terms(D)
-        if table.shape[3] > term_width(D) or self._pointwise(D):
-            return self._point_diag(table, X1k, D)
+        Dd = X1k.shape[1] - 1
+        table, _, _, D = self._device_terms(Dd)
+        if table.shape[3] > term_width(Dd) or self._pointwise(D):
+            return self._point_diag(table, X1k, Dd)
         return self._spectral_diag(D)[X1k[:, 0].astype(np.int64)]
 
     @staticmethod
@@ -277,9 +364,10 @@ class Kernel(ParameterHolder):
     def _point_rows(self, table, Xk, D):
         """From a table with kinds (no envelope), per point k (channel c) and row t of the diagonal pair (c, c): the row's value v on the
         diagonal -- its amplitude (every profile is 1 at zero distance, Delta = Psi = 0 there), for a dot-product row (A |x|^2 + c)^n, for
-        a gate row A h(x)^2 -- with dv / d(table column) for the columns that move it (N, T, W: the amplitude; the bias in a dot-product
-        row's Psi slot; beta and l in a gate row's V and M slots), and the groups, which are the same in every pair"""
-        kind, shape = self._spectral_kinds(D)
+        a gate row A h(x)^2, for a weighted-dot row A sum_d V_d x_d^2 -- with dv / d(table column) for the columns that move it (N, T, W: the
+        amplitude; the bias in a dot-product row's Psi slot; beta and l in a gate row's V and M slots; a weighted-dot row's V slots), and the
+        groups, which are the same in every pair.  `table`, `Xk` and `D` are the device's (`_device_terms`): the feature columns included"""
+        kind, shape = self._spectral_kinds(D - sum(k._features() for k in self._feature_leaves()))
         c = Xk[:, 0].astype(np.int64)
         rows = table[c, c]                                        # (N, T, W)
         kd = kind[c, c] & KIND_MASK
@@ -298,6 +386,13 @@ class Kernel(ParameterHolder):
             dv[..., 0] = np.where(gate, h2, dv[..., 0])
             dv[..., 2] = np.where(gate, 2.0 * A * h2 * hc * a, 0.0)
             dv[..., 2 + D] = np.where(gate, -2.0 * A * h2 * hc * beta, 0.0)
+        wdot = kd == KIND_WDOT
+        if np.any(wdot):
+            xx = np.square(Xk[:, None, 1:])                          # (N, 1, D)
+            q = np.sum(rows[..., 2:2 + D] * xx, axis=2)
+            v = np.where(wdot, rows[..., 0] * q, v)
+            dv[..., 0] = np.where(wdot, q, dv[..., 0])
+            dv[..., 2:2 + D] = np.where(wdot[..., None], rows[..., 0:1] * xx, dv[..., 2:2 + D])
         return v, dv, group_slices(kind[0, 0])
 
     def _point_diag(self, table, Xk, D):

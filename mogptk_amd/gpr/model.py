@@ -10,7 +10,7 @@ from math import erf, sqrt
 
 from .config import config
 from .parameter import Parameter, ParameterHolder
-from .kernel import Kernel, MulKernel, ChangePointsKernel, terms_cache, KIND_TIMES, KIND_MASK, KIND_DOT, KIND_GATE, group_diag_grad
+from .kernel import Kernel, MulKernel, ChangePointsKernel, terms_cache, KIND_TIMES, KIND_MASK, KIND_DOT, KIND_GATE, KIND_WDOT, group_diag_grad
 from .likelihood import Likelihood, GaussianLikelihood
 from .mean import Mean
 
@@ -72,7 +72,8 @@ def _gtable_from_moments(table, mom, D, lower=True, kind=None):
     `kind` (the table's kinds, when they travelled): a dot-product row's moments are derivatives already -- dA = m0, and the bias in its Psi
     slot gets m1_0 (an even slot, which the device keeps on diagonal channel blocks); its other columns are not parameters.  A gate row's
     m1_0 and m3_0 are d/dbeta and d/dl of h_a h_b: times the row's own amplitude (1 as ChangePointsKernel writes it) they are the V and M
-    columns; the other columns but the amplitude's are zero.
+    columns; the other columns but the amplitude's are zero.  A weighted-dot row's m1_d is d/dV_d of sum_d V_d x_a,d x_b,d: times the row's
+    own amplitude it is the V column d (FunctionKernel's magnitude on its feature columns); M, Delta and Psi are not parameters.
     lower=True: mom is indexed by lower channel pairs p = i(i+1)/2 + j (symmetric Gram, double count already
     included); lower=False: mom is indexed by all ordered pairs i*C + j (rectangular Gram)."""
     C, T = table.shape[0], table.shape[2]
@@ -104,6 +105,10 @@ def _gtable_from_moments(table, mom, D, lower=True, kind=None):
             g[gate, 1:] = 0.0
             g[gate, 2] = (A * mom[..., 2])[gate]
             g[gate, 2 + D] = (A * mom[..., 2 + 2 * D])[gate]
+        wdot = (kind[ii, jj] & KIND_MASK) == KIND_WDOT
+        if np.any(wdot):
+            g[wdot, 1:] = 0.0
+            g[wdot, 2:2 + D] = (A[..., None] * m1)[wdot]
     gt[ii, jj] = g
     return gt
 
@@ -171,8 +176,14 @@ class Model(ParameterHolder):
         return self.y - np.asarray(self.mean(self.X)).reshape(-1, 1)
 
     def _mean_affine(self):
+        """(the mean's affine table over the model's own inputs -- with zero slopes on the feature columns of a FunctionKernel, which the device
+        sees as inputs too --, whether X has a channel column)"""
         channel_col = self.kernel.output_dims is not None
-        return self.mean._affine(self.kernel._channels(), self._D, channel_col), channel_col
+        table = self.mean._affine(self.kernel._channels(), self._D, channel_col)
+        F = sum(k._features() for k in self.kernel._feature_leaves())
+        if table is not None and F:
+            table = np.concatenate([table, np.zeros((table.shape[0], F))], axis=1)
+        return table, channel_col
 
     def _sync_mean(self, h):
         """before an evaluation: the affine table to the device (it re-forms the residual only when the table changed), or -- a user's
@@ -195,7 +206,7 @@ class Model(ParameterHolder):
             return
         table, channel_col = self._mean_affine()
         if table is not None:
-            self.mean._affine_backward(h.mean_grad(), channel_col)
+            self.mean._affine_backward(np.asarray(h.mean_grad())[:, :1 + self._D], channel_col)
         else:
             self.mean.backward(self.X, h.fetch(3).reshape(-1, 1))
 
@@ -248,7 +259,7 @@ class Model(ParameterHolder):
 
     def _kernel_diag(self, table, Xk, D):
         """K_diag as the device takes it: per point of Xk with enveloped terms, else per channel"""
-        return self.kernel._point_diag(table, Xk, D) if _enveloped(table, D) or self.kernel._pointwise(D) else self.kernel._spectral_diag(D)
+        return self.kernel._point_diag(table, Xk, D) if _enveloped(table, D) or self.kernel._pointwise(self._D) else self.kernel._spectral_diag(self._D)
 
     def _train_counts(self):
         """training points per channel.  X does not change under a model (reference gpr/model.py:113-118): counted once per X and number of channels"""
@@ -436,24 +447,27 @@ class Exact(Model):
         comm = getattr(config, "comm", None)
         if comm is not None and (comm.world > 1 or comm.force):
             self._mean_refuse("the sharded exact evaluation (use_distributed)")
-        D = self._D
-        table = self.kernel._spectral_terms(D)
-        kind, shape = self.kernel._spectral_kinds(D)
+        # the device's columns: the model's own and the feature columns of every FunctionKernel (none: the kernel's own table); what the
+        # feature columns cannot go with is refused in there
+        Dd = self._D + sum(k._features() for k in self.kernel._feature_leaves())
+        table, kind, shape, D = self.kernel._device_terms(Dd)
         radial = bool(np.any(kind))
         if radial:                              # refused before any device call
             if comm is not None and (comm.world > 1 or comm.force):
                 raise NotImplementedError("non-Gaussian stationary kernels (periodic ones included) and product kernels are not carried through the "
                                           "sharded exact evaluation (use_distributed)")
-            if _enveloped(table, D):
+            if _enveloped(table, Dd):
                 raise NotImplementedError("a sum of enveloped (harmonizable) terms and non-Gaussian stationary kernels is not on the HIP path")
-        h, table, D = self._push(table)
+        pointwise = radial and self.kernel._pointwise(D)
+        h, table, _ = self._push(table)
+        D = Dd                                  # from here on the table's columns are the device's
         if radial:
             h.set_kinds(kind, shape)
         elif getattr(h, "radial_kinds", False):
             h.set_kinds(None, None)               # the kernel was replaced by an all-Gaussian one with the same number of terms
         h.radial_kinds = radial
         h.group_kinds = kind if radial and np.any(kind & KIND_TIMES) else None      # product groups: _loss_impl's jitter term needs them
-        h.point_kinds = kind if radial and self.kernel._pointwise(D) else None      # point rows (dot product, gate): _loss_impl's moments and jitter term need them
+        h.point_kinds = kind if pointwise else None      # point rows (dot product, gate, weighted dot): _loss_impl's moments and jitter term need them
         if _enveloped(table, D) or h.point_kinds is not None:      # envelope, point rows: the diagonal varies from point to point and enters the relative jitter (:244)
             h.set_point_diag(self.kernel._point_diag(table, self.kernel._kernel_format(self.X), D))
             h.point_diag_set = True
@@ -529,7 +543,7 @@ class Exact(Model):
             else:
                 for i in range(table.shape[0]):
                     gt[i, i, :, 0] += jit_rel * counts[i]
-        self.kernel._spectral_backward(-gt)                    # loss = -LML
+        self.kernel._table_backward(-gt)                       # loss = -LML (without a FunctionKernel: _spectral_backward itself)
 
         # noise: d LML / d sigma_c = 2 sigma_c (sum_{k in c} G_kk + jitter n_c/N tr G)
         self._noise_backward(res["diagG"] + jit_rel * counts)

@@ -9,7 +9,7 @@ import numpy as np
 
 from .config import config
 from .parameter import Parameter
-from .kernel import Kernel, term_width, cached_terms, KIND_TIMES, KIND_DOT
+from .kernel import Kernel, term_width, cached_terms, KIND_TIMES, KIND_DOT, KIND_WDOT, KIND_WHITE
 from .multioutput import _accumulate
 
 FOUR_PI2 = 4.0 * np.pi ** 2
@@ -96,7 +96,7 @@ class SpectralKernel(Kernel):
 
 
 # radial profile of a term (include/mogp_hip.h: mogp_model_set_kinds)
-KIND_GAUSS, KIND_RQ, KIND_MATERN12, KIND_MATERN32, KIND_MATERN52, KIND_PERIODIC, KIND_SINC = 0, 1, 2, 3, 4, 5, 6      # (KIND_DOT = 7: gpr/kernel.py)
+KIND_GAUSS, KIND_RQ, KIND_MATERN12, KIND_MATERN32, KIND_MATERN52, KIND_PERIODIC, KIND_SINC = 0, 1, 2, 3, 4, 5, 6      # (KIND_DOT = 7, KIND_GATE = 8, KIND_WDOT = 9, KIND_WHITE = 10: gpr/kernel.py)
 
 
 class _RadialKernel(Kernel):
@@ -424,3 +424,75 @@ class PolynomialKernel(LinearKernel):
     @property
     def _degree(self):
         return int(self.degree)
+
+
+class WhiteKernel(_MagnitudeKernel):
+    """K(X) = mag I and K(X, X') = 0 (reference :5-35): one white row (kind 10) -- the identity by INDEX, not by distance: two
+    different points with equal inputs do not see each other.  A noise term inside the kernel: per channel under
+    IndependentMultiOutputKernel, or as a factor of a product (White x k = diag(mag k(x, x)))."""
+
+    def __init__(self, input_dims=1, active_dims=None):
+        super().__init__(input_dims, active_dims)
+        self.magnitude = Parameter(1.0, lower=config.positive_minimum)
+
+    @cached_terms
+    def _spectral_terms(self, D):
+        self._check_dims(D)
+        table = np.zeros((1, 1, 1, term_width(D)))
+        table[0, 0, 0, 0] = self.magnitude()
+        return table
+
+    @cached_terms
+    def _spectral_kinds(self, D):
+        return np.full((1, 1, 1), KIND_WHITE, dtype=np.int32), np.zeros((1, 1, 1))
+
+    def _spectral_backward(self, gtable):
+        _accumulate(self.magnitude, np.reshape(gtable[0, 0, 0, 0], self.magnitude.shape))
+
+
+class FunctionKernel(Kernel):
+    """K(x, x') = phi(x) diag(mag) phi(x')^T (reference :140-179): explicit basis functions.  `phi` maps a float64 array (n, input_dims) to
+    (n, F); `magnitude` (F,) are the weights sigma_f^2.  phi is the user's Python and runs on the host: its values travel to the device as F
+    further input columns behind the model's own (Kernel._kernel_format), and the kernel is ONE weighted-dot row (kind 9) with unit
+    amplitude whose V slots on those columns hold the magnitude.  In the composition's own table (D columns) the row is [1, 0, ...]; the
+    re-laying to the device's columns, and the magnitude's gradient from the row's V columns, happen at the seam (Kernel._device_terms,
+    Kernel._table_backward).  The row's shape slot, which the device does not read for this kind, names the first feature column of the
+    leaf it came from: that is how a row copied into a product or under LMC finds its weights.  K_diag follows the point."""
+    _feature_offset = 0
+
+    def __init__(self, phi, input_dims=1, active_dims=None):
+        super().__init__(input_dims, active_dims)
+        out = phi(np.ones((42, input_dims), dtype=np.float64))
+        if not isinstance(out, np.ndarray) or out.dtype != np.float64:
+            raise ValueError("phi must return an array of the same dtype as the input")
+        if out.ndim != 2 or out.shape[0] != 42:
+            raise ValueError("phi must take (data_points,input_dims) as input, and return (data_points,feature_dims) as output")
+        self.magnitude = Parameter(np.ones(out.shape[1]), lower=config.positive_minimum)
+        self.phi = phi
+
+    def _features(self):
+        return int(self.magnitude.data.size)
+
+    def _phi_values(self, x):
+        """phi at the inputs x (n, input_dims) -> (n, F) float64"""
+        out = np.asarray(self.phi(np.ascontiguousarray(x, dtype=np.float64)), dtype=np.float64)
+        if out.shape != (x.shape[0], self._features()):
+            raise ValueError("phi returned %s for %d points; the kernel was built for (data_points, %d)" % (out.shape, x.shape[0], self._features()))
+        return out
+
+    @cached_terms
+    def _spectral_terms(self, D):
+        if D != self.input_dims:
+            raise ValueError("X must have %d input dimensions" % self.input_dims)
+        table = np.zeros((1, 1, 1, term_width(D)))
+        table[0, 0, 0, 0] = 1.0
+        return table
+
+    def _spectral_kinds(self, D):
+        return np.full((1, 1, 1), KIND_WDOT, dtype=np.int32), np.full((1, 1, 1), float(self._feature_offset))
+
+    def _spectral_diag(self, D):
+        raise NotImplementedError("%s has no diagonal value per channel: K(x, x) follows the point (Kernel._point_diag)" % self.name())
+
+    def _spectral_backward(self, gtable):
+        pass                                                   # the unit amplitude is no parameter; the magnitude's gradient comes from the device's V columns (Kernel._table_backward)
