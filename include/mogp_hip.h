@@ -184,6 +184,28 @@ int  mogp_gram_kinds(mogp_ctx* ctx, int C, int D, int T, int width, const double
 int  mogp_exact_eval(mogp_model* m, const double* noise_var, const double* data_var, double jitter, int flags,
                      double* lml, double* moments, double* diagG, double* trG, double* jitter_abs, int64_t* info);
 
+/* The leave-one-out predictive log-likelihood of the exact model and its gradient (Rasmussen & Williams, Gaussian Processes for Machine
+ * Learning, section 5.4.2; Sundararajan & Keerthi 2001).  No reference seam: mogptk has no such score -- the formulas are the book's, checked
+ * against N refits and against torch's autograd through them (tests/golden/gen_loo.py).  With Kj as in mogp_exact_eval, r = y - m(X),
+ * alpha = Kj^-1 r and kappa_i = (Kj^-1)_ii the predictive of y_i given all OTHER points is
+ *   mu_i = y_i - alpha_i / kappa_i,   var_i = 1 / kappa_i   (noise included),
+ *   *loo = L = sum_i [ 1/2 log kappa_i - alpha_i^2 / (2 kappa_i) - 1/2 log 2 pi ];
+ * mu, var: N each, in the caller's row order; y_i are the targets as mogp_model_create / mogp_model_set_y gave them (the raw ones under a
+ * mean table, whose mean is then part of the prediction).  With MOGP_EVAL_GRAD, a_i = 1/2 / kappa_i + alpha_i^2 / (2 kappa_i^2),
+ * b_i = alpha_i / kappa_i and rho = Kj^-1 b give
+ *   dL/dKj = G_loo = - Kj^-1 diag(a) Kj^-1 + 1/2 (alpha rho^T + rho alpha^T),      dL/dr = -rho,
+ * and moments, diagG, *trG are those of G_loo in the layout of mogp_exact_eval (G_loo stands where G = 1/2 (alpha alpha^T - Kj^-1) stands
+ * there, so the caller's chain rule is the same); every row kind of mogp_model_set_kinds and enveloped rows are taken.  mogp_model_mean_grad
+ * and mogp_model_fetch(3) then refer to L (fetch 3: -rho).  The factorisation and inversion are those of a gradient evaluation (same
+ * schedules, mogp_model_set_accurate included; mogp_model_pivot_range is valid afterwards) except that the inverse is always formed whole:
+ * mogp_model_inverse_fraction reports 1 and mogp_model_fetch(1) copies it; after a gradient call mogp_model_fetch(0) has nothing to return.
+ * The first call on a handle allocates one more N x N matrix (the first gradient call) and a few vectors; they go with the handle.
+ * moments / diagG / trG may be NULL without MOGP_EVAL_GRAD, jitter_abs always.  Not sharded.  On MOGP_ENOTPD *info as for mogp_exact_eval. */
+int  mogp_exact_loo(mogp_model* m, const double* noise_var, const double* data_var, double jitter, int flags,
+                    double* loo, double* mu, double* var, double* moments, double* diagG, double* trG, double* jitter_abs, int64_t* info);
+/* bytes of device memory the handle holds for mogp_exact_loo alone: 0 until its first call (no reference seam) */
+int  mogp_model_loo_bytes(mogp_model* m, int64_t* bytes);
+
 /* replaces Exact.predict_f (gpr/model.py:455-483): mu = Kfs^T Kj^-1 y, var = Kss_diag - colsum((L^-1 Kfs)^2)
  * (full != 0: var is S x S = Kss - v^T v).  Xs: S x (1+D).  mu: S, var: S or S*S.  No noise added to var.
  * kss_diag[C]: the kernel's K_diag value per channel as the reference returns it (gpr/kernel.py:483-495; for SM

@@ -55,6 +55,9 @@ SIGNATURES = {
                                        ctypes.c_int64, c_dp, ctypes.c_int64, c_dp, c_dp]),
     "mogp_exact_eval": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.c_double, ctypes.c_int,
                                        c_dp, c_dp, c_dp, c_dp, c_dp, c_i64p]),
+    "mogp_exact_loo": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.c_double, ctypes.c_int,
+                                      c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_i64p]),
+    "mogp_model_loo_bytes": (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
     "mogp_exact_predict": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.c_double, c_dp, ctypes.c_int64, c_dp,
                                           ctypes.c_int, c_dp, c_dp, c_i64p]),
     "mogp_titsias_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_dp, ctypes.c_double, ctypes.c_double, c_dp, ctypes.c_int,
@@ -320,6 +323,27 @@ class ExactHandle:
                                      ctypes.byref(trG), ctypes.byref(jit), ctypes.byref(info))
         check(code, info.value)
         return dict(lml=lml.value, moments=moments, diagG=diagG, trG=trG.value, jitter_abs=jit.value)
+
+    def loo(self, noise_var, jitter, grad=True, data_var=None):
+        """leave-one-out predictive log-likelihood (mogp_exact_loo) -> dict(loo, mu[N], var[N], moments[P,T,W], diagG[C], trG, jitter_abs): the
+        gradient outputs are those of dL/dKj in the layout of `eval`; never sharded (gpr.Exact refuses before it gets here)"""
+        noise_var = _f64(noise_var)
+        data_var = _f64(data_var)
+        C, T, W = self.C, self.T, self.W
+        loo, trG, jit, info = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int64(0)
+        mu, var = np.empty(self.N), np.empty(self.N)
+        moments = np.zeros((C * (C + 1) // 2, T, W)) if grad else None
+        diagG = np.zeros(C) if grad else None
+        code = lib().mogp_exact_loo(self._h, _dp(noise_var), _dp(data_var), float(jitter), MOGP_EVAL_GRAD if grad else 0, ctypes.byref(loo),
+                                    _dp(mu), _dp(var), _dp(moments), _dp(diagG), ctypes.byref(trG), ctypes.byref(jit), ctypes.byref(info))
+        check(code, info.value)
+        return dict(loo=loo.value, mu=mu, var=var, moments=moments, diagG=diagG, trG=trG.value, jitter_abs=jit.value)
+
+    def loo_bytes(self):
+        """device memory held for `loo` alone (mogp_model_loo_bytes): 0 on a handle that never called it"""
+        b = ctypes.c_int64(0)
+        check(lib().mogp_model_loo_bytes(self._h, ctypes.byref(b)))
+        return int(b.value)
 
     def eval_sharded(self, noise_var, jitter, data_var=None):
         """mogp_exact_eval_sharded: the evaluation spread over the ranks of the context's communicator (collectives inside the library)"""

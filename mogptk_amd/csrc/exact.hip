@@ -497,6 +497,40 @@ int test_side(mogp_model* m, int64_t S, const double* Xs, const double* kss_diag
 }
 }  // namespace mogp
 
+static const std::string& grad_path_env() {
+    static const std::string grad_path = []() { const char* e = std::getenv("MOGP_GRAD_PATH"); return std::string(e ? e : ""); }();
+    return grad_path;
+}
+
+// The factorisation of an evaluation on the POTRF path, and with `inverse` Kj^-1 (lower tiles, full diagonal tiles) in k.B behind it -- then
+// ENQUEUED only: the caller adds its own passes, waits once and calls factorize_finish.  Three schedules of the same arithmetic
+// (MOGP_GRAD_PATH = fused | phases overrides the choice; sweep is mogp_exact_eval's own):
+//   fused   potri.hip: the inverse streamed behind the Cholesky chain.  Wins while the serial chain dominates: 15.1 vs 15.9 ms at
+//           N = 8192, 20.1 vs 21.1 ms at N = 9216, even at N = 10240 -- the default up to 80 tile rows (112 as dataflow, below).
+//   phases  POTRF, TRTRI, LAUUM one after the other: fewer, larger GEMM launches.  Wins once the evaluation is flop-bound
+//           (38.8 vs 41.8 ms at N = 12288, 80.6 vs 90.1 ms at N = 16384, 569 vs 657 ms at N = 32768) -- the default above.
+//   sweep   sweep.hip: single-sweep blocked inversion; slower on one GPU (47 evals/s at N = 8192) but with one panel
+//           exchange per pivot block, which is what the sharded multi-GPU evaluation (mogp_shard_*) is built on.
+// banded: the inverse may stop at the tiles the marginal likelihood's gradient reads (kinv_plan); a caller that reads every tile says false.
+static int enqueue_inverse(mogp_model* m, const double* noise_var, const double* data_var, double jitter, bool inverse, bool banded,
+                           double* lml, double* jitter_abs, int64_t* info, GramArgs& ga) {
+    const std::string& grad_path = grad_path_env();
+    int rc;
+    if ((rc = ensure_system(m))) return rc;
+    if ((rc = kinv_plan(m, inverse && banded && !m->accurate))) return rc;
+    // round 4: as tile dataflow (flow.hip) the fused schedule also beats the phases at 81 .. 112 tile rows (configs[1]'s kernel, tools/r4_sizes.sh:
+    // 19.3 vs 22.4 ms at N = 10240, 32.5 vs 35.9 at 12288, 41.0 vs 43.8 at 13312, 50.7 vs 53.0 at 14336; 76.6 vs 75.8 the other way at 16384); where
+    // the dataflow kernel is not available (switched off, fallen back, a planned inverse) the stream form keeps its 80
+    const int fused_max = flow_enabled(m, m->k) ? 112 : 80;
+    const bool fused = inverse && !m->accurate && (grad_path == "fused" || (grad_path != "phases" && m->nb <= fused_max));
+    FactorPlan plan;
+    plan.schedule = fused ? FactorPlan::Fused : FactorPlan::Phases; plan.defer = inverse; plan.want_inverse = inverse;
+    if ((rc = factorize(m, noise_var, data_var, jitter, plan, lml, jitter_abs, info, &ga))) return rc;
+    if (!inverse) return 0;
+    if (!fused && !m->accurate_ran && (rc = spd_lauum(m, m->k))) return rc;          // (the accurate form left Kj^-1 itself in k.B)
+    return mark(m, 5);
+}
+
 extern "C" {
 
 int mogp_exact_eval(mogp_model* m, const double* noise_var, const double* data_var, double jitter, int flags,
@@ -504,42 +538,27 @@ int mogp_exact_eval(mogp_model* m, const double* noise_var, const double* data_v
     if (!m) return fail(MOGP_EINVAL, "mogp_exact_eval: model is null");
     int rc;
     if ((rc = begin_call(m, info, true))) return rc;
-    // Gradient evaluation, three schedules of the same arithmetic (MOGP_GRAD_PATH = fused | phases | sweep overrides the choice):
-    //   fused   potri.hip: the inverse streamed behind the Cholesky chain.  Wins while the serial chain dominates: 15.1 vs 15.9 ms at
-    //           N = 8192, 20.1 vs 21.1 ms at N = 9216, even at N = 10240 -- the default up to 80 tile rows (112 as dataflow, below).
-    //   phases  POTRF, TRTRI, LAUUM one after the other: fewer, larger GEMM launches.  Wins once the evaluation is flop-bound
-    //           (38.8 vs 41.8 ms at N = 12288, 80.6 vs 90.1 ms at N = 16384, 569 vs 657 ms at N = 32768) -- the default above.
-    //   sweep   sweep.hip: single-sweep blocked inversion; slower on one GPU (47 evals/s at N = 8192) but with one panel
-    //           exchange per pivot block, which is what the sharded multi-GPU evaluation (mogp_shard_*) is built on.
-    static const std::string grad_path = []() { const char* e = std::getenv("MOGP_GRAD_PATH"); return std::string(e ? e : ""); }();
+    const std::string& grad_path = grad_path_env();
     const bool sweep = grad_path == "sweep" && (flags & MOGP_EVAL_GRAD);
     const bool grad = (flags & MOGP_EVAL_GRAD) != 0;
     GramArgs ga{};
-    if ((rc = ensure_system(m))) return rc;
-    if ((rc = kinv_plan(m, grad && !sweep && !m->accurate))) return rc;
-    // round 4: as tile dataflow (flow.hip) the fused schedule also beats the phases at 81 .. 112 tile rows (configs[1]'s kernel, tools/r4_sizes.sh:
-    // 19.3 vs 22.4 ms at N = 10240, 32.5 vs 35.9 at 12288, 41.0 vs 43.8 at 13312, 50.7 vs 53.0 at 14336; 76.6 vs 75.8 the other way at 16384); where
-    // the dataflow kernel is not available (switched off, fallen back, a planned inverse) the stream form keeps its 80
-    const int fused_max = flow_enabled(m, m->k) ? 112 : 80;
-    const bool fused = !sweep && grad && !m->accurate && (grad_path == "fused" || (grad_path != "phases" && m->nb <= fused_max));
     auto again = [&]() { return mogp_exact_eval(m, noise_var, data_var, jitter, flags, lml, moments, diagG, trG, jitter_abs, info); };
-    FactorPlan plan;
-    plan.schedule = fused ? FactorPlan::Fused : FactorPlan::Phases; plan.defer = grad; plan.want_inverse = grad;
+    if (grad && (!moments || !diagG || !trG)) return fail(MOGP_EINVAL, "mogp_exact_eval: gradient outputs are null");
     if (sweep) {
+        if ((rc = ensure_system(m))) return rc;
+        if ((rc = kinv_plan(m, false))) return rc;
         m->pivot_min = m->pivot_max = 0.0;                     // (the sweep reports no pivot range)
         if ((rc = eval_sweep(m, noise_var, data_var, jitter, lml, jitter_abs, info))) return retry_on_streams(m, rc, again);
     }
-    else if ((rc = factorize(m, noise_var, data_var, jitter, plan, lml, jitter_abs, info, &ga))) return retry_on_streams(m, rc, again);
+    else if ((rc = enqueue_inverse(m, noise_var, data_var, jitter, grad, /*banded=*/true, lml, jitter_abs, info, ga))) return retry_on_streams(m, rc, again);
     if (!grad) { collect_timing(m, 4); return MOGP_OK; }
-    if (!moments || !diagG || !trG) return fail(MOGP_EINVAL, "mogp_exact_eval: gradient outputs are null");
 
     const int C = m->C, W = m->Wt, T = m->T, P = C * (C + 1) / 2;
 
-    // K^-1: the sweep left -Kj^-1 in k.A; the POTRF path needs W^T W (lower tiles, full diagonal tiles) in k.B
-    if (!sweep && !fused && !m->accurate_ran && (rc = spd_lauum(m, m->k))) return rc;          // (the accurate form left Kj^-1 itself in k.B)
+    // K^-1: the sweep left -Kj^-1 in k.A; the POTRF path W^T W (lower tiles, full diagonal tiles) in k.B
     const double* kinv = sweep ? m->k.A.p : m->k.B.p;
     const double ksign = sweep ? -1.0 : 1.0;
-    if ((rc = mark(m, 5))) return rc;
+    if (sweep && (rc = mark(m, 5))) return rc;
     if (sweep) {
         if ((rc = moment_pass(m, kinv, ksign, moments, diagG))) return rc;
     } else {
@@ -560,6 +579,65 @@ int mogp_exact_eval(mogp_model* m, const double* noise_var, const double* data_v
     m->kinv_in_A = sweep;
     mean_grad_collect(m);
     collect_timing(m, 6);
+    return MOGP_OK;
+}
+
+int mogp_exact_loo(mogp_model* m, const double* noise_var, const double* data_var, double jitter, int flags,
+                   double* loo, double* mu, double* var, double* moments, double* diagG, double* trG, double* jitter_abs, int64_t* info) {
+    if (!m) return fail(MOGP_EINVAL, "mogp_exact_loo: model is null");
+    if (!loo || !mu || !var) return fail(MOGP_EINVAL, "mogp_exact_loo: loo, mu or var is null");
+    const bool grad = (flags & MOGP_EVAL_GRAD) != 0;
+    if (grad && (!moments || !diagG || !trG)) return fail(MOGP_EINVAL, "mogp_exact_loo: gradient outputs are null");
+    int rc;
+    if ((rc = begin_call(m, info, true))) return rc;
+    auto again = [&]() { return mogp_exact_loo(m, noise_var, data_var, jitter, flags, loo, mu, var, moments, diagG, trG, jitter_abs, info); };
+    const int C = m->C, W = m->Wt, T = m->T, P = C * (C + 1) / 2;
+    const int64_t N = m->N, Npad = m->Npad;
+    // every allocation before the co-operating kernels are enqueued (see factorize): the LOO workspace, and the pinned block with L, mu and var behind the evaluation's own scalars
+    if ((rc = ensure_system(m))) return rc;
+    if ((rc = loo_workspace(m, grad))) return rc;
+    const PinLayout pl(m);
+    const size_t pin_loo = pl.total, pin_mu = pin_loo + 1, pin_var = pin_mu + (size_t)Npad;
+    if ((rc = pin_ensure(m, pin_var + (size_t)Npad))) return rc;
+    GramArgs ga{};
+    // the factorisation and inversion of a gradient evaluation, the COMPLETE inverse: Kj^-1 diag(a) Kj^-1 reads every tile
+    if ((rc = enqueue_inverse(m, noise_var, data_var, jitter, true, /*banded=*/false, nullptr, jitter_abs, info, ga))) return retry_on_streams(m, rc, again);
+    double* v = m->loo.vec.p;
+    if ((rc = loo_points(m, m->k.B.p))) return rc;
+    if (grad) {
+        // S = Kj^-1 diag(sqrt a) goes where the factorisation's own matrix was (k.A: the Gram matrix, then L or W): nothing reads it after alpha,
+        // and the next evaluation builds it anew -- so the handle no longer holds W for mogp_model_fetch(0)
+        m->have_W = false;
+        if ((rc = loo_adjoint(m, m->k.B.p, m->k.A.p))) return rc;
+        if ((rc = loo_moment_pass(m))) return rc;
+        HIP_TRY(hipMemcpyAsync(m->h_pin + pl.moments, m->d_moments.p, (size_t)P * T * W * sizeof(double), hipMemcpyDeviceToHost, m->st));
+        HIP_TRY(hipMemcpyAsync(m->h_pin + pl.diagG, m->d_diagG.p, C * sizeof(double), hipMemcpyDeviceToHost, m->st));
+    }
+    HIP_TRY(hipMemcpyAsync(m->h_pin + pin_loo, v + LOO_SUM * Npad, sizeof(double), hipMemcpyDeviceToHost, m->st));
+    HIP_TRY(hipMemcpyAsync(m->h_pin + pin_mu, v + LOO_MU * Npad, N * sizeof(double), hipMemcpyDeviceToHost, m->st));
+    HIP_TRY(hipMemcpyAsync(m->h_pin + pin_var, v + LOO_VAR * Npad, N * sizeof(double), hipMemcpyDeviceToHost, m->st));
+    if ((rc = wait_stream(m->st))) return rc;
+    if ((rc = factorize_finish(m, ga, nullptr, info))) return retry_on_streams(m, rc, again);
+    if (grad) m->have_W = false;                              // (factorize_finish set it: k.A holds S now)
+    *loo = m->h_pin[pin_loo];
+    scatter_by_perm(m->sx, m->h_pin + pin_mu, mu);
+    scatter_by_perm(m->sx, m->h_pin + pin_var, var);
+    m->have_Kinv = true;                                      // complete and mirrored: mogp_model_fetch(1) copies it as it is
+    m->kinv_in_A = false;
+    if (!grad) { collect_timing(m, 5); return MOGP_OK; }
+    std::memcpy(moments, m->h_pin + pl.moments, (size_t)P * T * W * sizeof(double));
+    std::memcpy(diagG, m->h_pin + pl.diagG, C * sizeof(double));
+    double tr = 0.0;
+    for (int c = 0; c < C; ++c) tr += diagG[c];
+    *trG = tr;
+    mean_grad_collect(m);
+    collect_timing(m, 6);
+    return MOGP_OK;
+}
+
+int mogp_model_loo_bytes(mogp_model* m, int64_t* bytes) {
+    if (!m || !bytes) return fail(MOGP_EINVAL, "mogp_model_loo_bytes: bad argument");
+    *bytes = (int64_t)((m->loo.G.n + m->loo.vec.n) * sizeof(double));
     return MOGP_OK;
 }
 

@@ -1516,10 +1516,12 @@ __device__ __forceinline__ void moment_term_radial(double* mom, const double (&g
 // unconstrained, i.e. ONE wave per SIMD and nothing to hide its loads behind).
 // (round 4: cutting the registers to three or four waves per SIMD -- __launch_bounds__(256, 3 / 4) -- costs 81 / 92 spilled VGPRs; the pressure is
 // the tile's adjoint block (g: 32 VGPRs), the staged factors and the staging prefetch, not the Horner chains)
-// RAD: the radial instantiation (a.kind / a.shape are set; DENSE, ZG and ENV are false); the others contain nothing of it.
+// RAD: the radial instantiation (a.kind / a.shape are set; ZG and ENV are false); the others contain nothing of it.  RAD with DENSE takes
+// g from a dense symmetric adjoint (a.G, lower-stored, the `sym` weights) where the exact form makes it of alpha and Kj^-1 -- the walk over
+// rows and groups is the same (mogp_exact_loo: the adjoint of the leave-one-out likelihood).
 template <int DT, bool DENSE, bool ZG, bool ENV, bool RAD = false, int GATE = 0>
 __global__ __launch_bounds__(256, (DT == 1 && !RAD ? 2 : 1)) void k_moments(MomentArgs a) {      // (RAD, D = 1: the library exps push two workgroups per CU into scratch)
-    static_assert(!RAD || (!DENSE && !ZG && !ENV), "radial moments: exact mode only");
+    static_assert(!RAD || (!ZG && !ENV), "radial moments: no input gradients, no envelope");
     constexpr int DM = DT > 0 ? DT : MOGP_MAXD;
     constexpr int WM = 2 + (ENV ? 5 : 3) * DM;
     constexpr int RSTRIDE = 256 + 16;                        // one moment of all threads, +1 per 16 (the slice reads hit distinct banks)
@@ -1931,6 +1933,28 @@ static int launch_moments_t(const MomentArgs& a, hipStream_t s) {
     return 0;
 }
 
+// the radial instantiations: GATE by `rows` (mogp_internal.h: launch_gram), D = 1, 2, 3 or generic; DENSE: the adjoint comes from a.G
+template <bool DENSE>
+static void launch_moments_radial(const MomentArgs& a, hipStream_t s, int rows) {
+    if (rows == 1) {
+        hipLaunchKernelGGL((k_moments<1, DENSE, false, false, true, 1>), dim3(a.ntiles), dim3(256), 0, s, a);
+    } else if (rows > 1) {
+        switch (a.D) {
+            case 1: hipLaunchKernelGGL((k_moments<1, DENSE, false, false, true, 2>), dim3(a.ntiles), dim3(256), 0, s, a); break;
+            case 2: hipLaunchKernelGGL((k_moments<2, DENSE, false, false, true, 2>), dim3(a.ntiles), dim3(256), 0, s, a); break;
+            case 3: hipLaunchKernelGGL((k_moments<3, DENSE, false, false, true, 2>), dim3(a.ntiles), dim3(256), 0, s, a); break;
+            default: hipLaunchKernelGGL((k_moments<0, DENSE, false, false, true, 2>), dim3(a.ntiles), dim3(256), 0, s, a); break;
+        }
+    } else {
+        switch (a.D) {
+            case 1: hipLaunchKernelGGL((k_moments<1, DENSE, false, false, true>), dim3(a.ntiles), dim3(256), 0, s, a); break;
+            case 2: hipLaunchKernelGGL((k_moments<2, DENSE, false, false, true>), dim3(a.ntiles), dim3(256), 0, s, a); break;
+            case 3: hipLaunchKernelGGL((k_moments<3, DENSE, false, false, true>), dim3(a.ntiles), dim3(256), 0, s, a); break;
+            default: hipLaunchKernelGGL((k_moments<0, DENSE, false, false, true>), dim3(a.ntiles), dim3(256), 0, s, a); break;
+        }
+    }
+}
+
 int launch_moments(const MomentArgs& a0, hipStream_t s, int rows) {
     if (a0.ntiles <= 0) return 0;
     MomentArgs a = a0;
@@ -1942,26 +1966,11 @@ int launch_moments(const MomentArgs& a0, hipStream_t s, int rows) {
     if (rc) return rc;
     if (a.kind) {                                            // radial profiles: every tile through the radial form of the staged kernel
         if (!a.shape) { set_error("launch_moments: kinds without shapes"); return -1; }
-        if (a.G != nullptr || env) { set_error("launch_moments: radial profiles run in exact mode without an envelope only"); return -1; }
+        // (a dense adjoint: the symmetric lower-tile form alone -- no rank-one rider, no input gradients, square)
+        if (env || (a.G != nullptr && (!a.sym || a.ru || a.gzr || a.gzc || a.xc))) { set_error("launch_moments: radial profiles take the exact mode or a dense symmetric adjoint, without an envelope"); return -1; }
         if (a.ev0) HIP_TRY(hipEventRecord(a.ev0, s));
         if (rows == 1 && a.D != 1) { set_error("launch_moments: gate rows take one input dimension"); return -1; }
-        if (rows == 1) {
-            hipLaunchKernelGGL((k_moments<1, false, false, false, true, 1>), dim3(a.ntiles), dim3(256), 0, s, a);
-        } else if (rows > 1) {
-        switch (a.D) {
-            case 1: hipLaunchKernelGGL((k_moments<1, false, false, false, true, 2>), dim3(a.ntiles), dim3(256), 0, s, a); break;
-            case 2: hipLaunchKernelGGL((k_moments<2, false, false, false, true, 2>), dim3(a.ntiles), dim3(256), 0, s, a); break;
-            case 3: hipLaunchKernelGGL((k_moments<3, false, false, false, true, 2>), dim3(a.ntiles), dim3(256), 0, s, a); break;
-            default: hipLaunchKernelGGL((k_moments<0, false, false, false, true, 2>), dim3(a.ntiles), dim3(256), 0, s, a); break;
-        }
-        } else {
-        switch (a.D) {
-            case 1: hipLaunchKernelGGL((k_moments<1, false, false, false, true>), dim3(a.ntiles), dim3(256), 0, s, a); break;
-            case 2: hipLaunchKernelGGL((k_moments<2, false, false, false, true>), dim3(a.ntiles), dim3(256), 0, s, a); break;
-            case 3: hipLaunchKernelGGL((k_moments<3, false, false, false, true>), dim3(a.ntiles), dim3(256), 0, s, a); break;
-            default: hipLaunchKernelGGL((k_moments<0, false, false, false, true>), dim3(a.ntiles), dim3(256), 0, s, a); break;
-        }
-        }
+        if (a.G != nullptr) launch_moments_radial<true>(a, s, rows); else launch_moments_radial<false>(a, s, rows);
         HIP_TRY(hipGetLastError());
         if (a.ev1) HIP_TRY(hipEventRecord(a.ev1, s));
         return 0;

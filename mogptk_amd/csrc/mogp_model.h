@@ -306,6 +306,13 @@ struct OaWork {
     void release() { K.release(); Sc.release(); Y.release(); vec.release(); valid = false; }
 };
 
+// workspace of the leave-one-out evaluation (loo.hip): the one N x N buffer of the adjoint G_loo and the per-point vectors.  Allocated by the
+// first mogp_exact_loo of a handle and released with it; a model that never calls it holds none of this (mogp_model_loo_bytes)
+struct LooWork {
+    mogp::DevBuf<double> G, vec;
+    void release() { G.release(); vec.release(); }
+};
+
 // right-hand sides of the prediction's dataflow schedule: X L^T = T, `nt` tile rows (row-major, the leading dimension of the N x N matrices), `ready`: T is in place
 struct FlowRhs { double* T; double* X; int nt; hipEvent_t ready; };
 struct mogp_model {
@@ -413,6 +420,7 @@ struct mogp_model {
     bool no_chain = false;              // the persistent chain kernel timed out once on this model (another process's chain kernel held the reserved CUs): launch-per-step chain from now on
     TitsiasWork* tw = nullptr;
     OaWork oa;
+    LooWork loo;
 
     // trainable mean (mean.hip, mogp_model_set_mean): with a table set, d_y / hy hold the residual y0 - m(X) and d_y0 / hy0 the raw targets
     bool mean_on = false, mean_g_valid = false, mean_g_pending = false;
@@ -519,6 +527,12 @@ inline void scatter_by_perm(const SortedX& ss, const double* sorted, double* out
 int moment_pass_device(mogp_model* m, const double* kinv, double ksign);      // gradient moments over this rank's rows of Kj^-1 into d_moments / d_diagG
 int moment_pass(mogp_model* m, const double* kinv, double ksign, double* moments, double* diagG);      // ... and to the host, with a stream sync
 void collect_timing(mogp_model* m, int last_mark);
+// loo.hip -- the leave-one-out predictive likelihood on Kj^-1 (lower tiles in kinv, mirrored in place here) and alpha.  Vector slots of LooWork::vec, Npad each:
+enum { LOO_MU = 0, LOO_VAR, LOO_A, LOO_B, LOO_SA, LOO_TERM, LOO_RHO, LOO_SUM, LOO_COUNT };
+int loo_workspace(mogp_model* m, bool grad);                        // every allocation of a LOO evaluation (before the factorisation is enqueued)
+int loo_points(mogp_model* m, double* kinv);                        // mu, var, a, b, sqrt a, the N terms of L and their fixed-order sum (vec[LOO_SUM])
+int loo_adjoint(mogp_model* m, const double* kinv, double* scratch);  // rho = Kj^-1 b and G_loo (lower) into LooWork::G; scratch: N x N, overwritten
+int loo_moment_pass(mogp_model* m);                                 // moments of G_loo (every row kind), per-channel diagonal sums, dp/dr = -rho
 int eval_sweep(mogp_model* m, const double* noise_var, const double* data_var, double jitter, double* lml, double* jitter_abs, int64_t* info);   // shard.hip
 void one_gpu_call(mogp_model* m);   // ownership state of a previous sharded evaluation off (every one-GPU entry point calls this first)
 int ensure_system(mogp_model* m);     // the N x N system of the exact / OA paths and the tile lists over (X, X), on first use (mogp_api.hip)

@@ -476,12 +476,23 @@ class Exact(Model):
             h.point_diag_set = False
         return h, table, D
 
-    def _eval(self, grad):
+    def _refuse_sharded_loo(self):
+        comm = getattr(config, "comm", None)
+        if comm is not None and (comm.world > 1 or comm.force):
+            raise NotImplementedError("the leave-one-out likelihood is not carried through the sharded exact evaluation (use_distributed): it "
+                                      "reads the whole of Kj^-1, which no rank of a sharded evaluation holds")
+
+    def _eval(self, grad, loo=False):
+        """one device evaluation of the marginal likelihood, or -- loo -- of the leave-one-out likelihood: push, guard, conditioning check"""
+        if loo:
+            self._refuse_sharded_loo()              # before any device call
         h, table, D = self._push_terms()
         with self._cholesky_guard():
-            run = lambda: h.eval(self._noise_var(), self.jitter, grad=grad, data_var=self.data_variance)
+            call = h.loo if loo else h.eval
+            run = lambda: call(self._noise_var(), self.jitter, grad=grad, data_var=self.data_variance)
             res = run()
-            again = self._check_conditioning(h, run) if grad else None          # (the LML alone: the fast factorisation's log-determinant and z are good to ~1e-7 even at 1e8)
+            # (the LML alone: the fast factorisation's log-determinant and z are good to ~1e-7 even at 1e8; a LOO evaluation reads the inverse, like a gradient)
+            again = self._check_conditioning(h, run) if grad or loo else None
             return (res if again is None else again), table, D
 
     CONDITION_WARN = 1e5       # on the pivot-spread estimate (max L_jj / min L_jj)^2, a LOWER bound of cond(Kj) -- 9e5 where cond is 7e7, 9e3 where it is 8e5;
@@ -522,11 +533,13 @@ class Exact(Model):
         res, _, _ = self._eval(grad=False)
         return config.dtype(res["lml"])
 
-    def _loss_impl(self):
+    def _loss_impl(self, loo=False):
         """reference gpr/model.py:279-292: zero grads, loss = -LML - log prior, fresh `.grad` on every
-        parameter in the graph.  Gradients come from the device's moment pass + the host chain rule."""
+        parameter in the graph.  Gradients come from the device's moment pass + the host chain rule.
+        loo: the leave-one-out likelihood L in the LML's place -- the device returns the moments, diagonal sums and trace of dL/dKj in the
+        same layout, so the chain rule below is the same."""
         self.zero_grad(set_to_none=True)
-        res, table, D = self._eval(grad=True)
+        res, table, D = self._eval(grad=True, loo=loo)
         counts = self._train_counts()
         jit_rel = self.jitter * res["trG"] / self.X.shape[0]            # d LML / d (mean diag) through the jitter term (:244)
 
@@ -548,7 +561,26 @@ class Exact(Model):
         # noise: d LML / d sigma_c = 2 sigma_c (sum_{k in c} G_kk + jitter n_c/N tr G)
         self._noise_backward(res["diagG"] + jit_rel * counts)
         self._mean_backward(self._handle)
-        return config.dtype(-res["lml"] - self.log_prior())
+        return config.dtype(-res["loo" if loo else "lml"] - self.log_prior())
+
+    # -- leave-one-out predictive likelihood (Rasmussen & Williams 5.4.2; csrc/loo.hip) -----------------------------------------
+    def loo(self):
+        """-> (mu, var), each (N, 1): mean and variance (noise included) of the prediction of every training target from all the others"""
+        res, _, _ = self._eval(grad=False, loo=True)
+        mu = res["mu"].reshape(-1, 1)
+        if self.mean is not None and not (self._trainable_mean() and self._mean_affine()[0] is not None):
+            mu = self._add_mean(mu, self.X)         # the device holds y - m(X) as its targets (an affine gpr.Mean is on the device: it holds y)
+        return mu.astype(config.dtype, copy=False), res["var"].reshape(-1, 1).astype(config.dtype, copy=False)
+
+    def loo_log_likelihood(self):
+        """sum_i log p(y_i | X, y_-i): one device evaluation without gradients"""
+        res, _, _ = self._eval(grad=False, loo=True)
+        return config.dtype(res["loo"])
+
+    def loo_loss(self):
+        """-(leave-one-out log-likelihood) - log prior, and like `loss` a fresh `.grad` on every parameter: kernel, noise, trainable mean"""
+        with terms_cache():
+            return self._loss_impl(loo=True)
 
     def predict_f(self, X, full=False):
         """reference gpr/model.py:455-483"""

@@ -590,6 +590,16 @@ class Model:
         """reference mogptk/model.py:374-384"""
         return float(self.gpr.loss())
 
+    def _exact_only(self, what):
+        if not isinstance(self.gpr, gpr.Exact):
+            raise ValueError("%s needs exact inference (mogptk_amd.Exact): %s has no leave-one-out likelihood" % (what, self.gpr.name()))
+
+    def loo_log_likelihood(self):
+        """Leave-one-out predictive log-likelihood sum_i log p(y_i | X, y_-i) in transformed space (Rasmussen & Williams 5.4.2): a score for
+        comparing kernels on the same data without setting points aside; exact inference only."""
+        self._exact_only("loo_log_likelihood()")
+        return float(self.gpr.loo_log_likelihood())
+
     _ERROR_MEASURES = {"mae": mean_absolute_error, "mape": mean_absolute_percentage_error,
                        "smape": symmetric_mean_absolute_percentage_error, "mse": mean_squared_error,
                        "rmse": root_mean_squared_error}
@@ -615,7 +625,7 @@ class Model:
                      for channel, part, x in zip(self.dataset, np.split(flat, ends[:-1]), X)]
         return measure(np.concatenate(truth), np.concatenate(predicted))
 
-    def train(self, method="Adam", iters=500, verbose=False, error=None, plot=False, jit=None, **kwargs):
+    def train(self, method="Adam", iters=500, verbose=False, error=None, plot=False, jit=None, objective="lml", **kwargs):
         """
         Optimise the hyper-parameters (reference mogptk/model.py:441-579): `iters` optimiser steps and
         `iters+1` loss evaluations; `times/losses/errors` are continued across calls, the optimiser state is not.
@@ -627,6 +637,8 @@ class Model:
             error (str, function): prediction error evaluated per iteration.
             plot (bool): accepted; plotting is out of scope.
             jit (bool): accepted and ignored (one native call per evaluation already).
+            objective (str): "lml" minimises -(log marginal likelihood) - log prior; "loo" the negative leave-one-out predictive
+                log-likelihood - log prior (exact inference only).
             **kwargs: passed to the optimiser (lr=..., betas=..., ...).
 
         Returns:
@@ -642,6 +654,12 @@ class Model:
                 e = error(np.zeros((1, 1)), np.zeros((1, 1)))
             if not isinstance(e, float) and (not isinstance(e, np.ndarray) or e.size != 1):
                 raise ValueError("error function must return a float")
+
+        if objective not in ("lml", "loo"):
+            raise ValueError("objective must be 'lml' or 'loo'")
+        if objective == "loo":
+            self._exact_only("train(objective='loo')")
+        loss_fn = self.loss if objective == "lml" else (lambda: float(self.gpr.loo_loss()))
 
         if method.lower() in ("l-bfgs", "lbfgs", "l-bfgs-b", "lbfgsb"):
             method = "LBFGS"
@@ -707,7 +725,7 @@ class Model:
 
             def closure():
                 i = int(optimizer.state["func_evals"])
-                value = self.loss()
+                value = loss_fn()
                 progress(i, value)
                 return value
             optimizer.step(closure)
@@ -720,9 +738,9 @@ class Model:
             else:
                 optimizer = _Adagrad(params, **kwargs)
             for i in range(iters):
-                progress(i, self.loss())
+                progress(i, loss_fn())
                 optimizer.step()
-        progress(iters, self.loss(), last=True)
+        progress(iters, loss_fn(), last=True)
 
         if verbose:
             print("Optimization finished in %s" % _format_duration(time.time() - t_start))
