@@ -203,7 +203,27 @@ int  mogp_exact_eval(mogp_model* m, const double* noise_var, const double* data_
  * moments / diagG / trG may be NULL without MOGP_EVAL_GRAD, jitter_abs always.  Not sharded.  On MOGP_ENOTPD *info as for mogp_exact_eval. */
 int  mogp_exact_loo(mogp_model* m, const double* noise_var, const double* data_var, double jitter, int flags,
                     double* loo, double* mu, double* var, double* moments, double* diagG, double* trG, double* jitter_abs, int64_t* info);
-/* bytes of device memory the handle holds for mogp_exact_loo alone: 0 until its first call (no reference seam) */
+/* Leave-fold-out cross-validation of the exact model and its gradient: the predictive log-likelihood of whole index sets given every other
+ * point.  No reference seam: mogptk has no such score -- the formulas are the block form of the leave-one-out ones (Rasmussen & Williams 5.4.2
+ * with a set in the point's place), checked against the conditional Gaussians formed directly from Kj and torch's autograd through them
+ * (tests/golden/gen_cv.py).  fold: N labels in the caller's row order, -1 (the point is never held out) or 0 .. nfolds - 1; the folds are
+ * disjoint by construction, each must hold 1 .. 128 points (MOGP_EINVAL names the fold and its size otherwise).  With Kj, r, alpha as in
+ * mogp_exact_loo, P = Kj^-1 and B the points of one fold,
+ *   Sigma_B = (P_BB)^-1   (the predictive covariance of y_B given all OTHER points, noise included),   mu_B = y_B - Sigma_B alpha_B,
+ *   *cv = L = sum over the folds of [ -1/2 alpha_B^T Sigma_B alpha_B + 1/2 log det P_BB - |B|/2 log 2 pi ];
+ * mu, var: N each, in the caller's row order, var the diagonal of Sigma_B, both NaN at a point in no fold; y as for mogp_exact_loo.  With
+ * MOGP_EVAL_GRAD, b_B = Sigma_B alpha_B (0 outside the folds), E the matrix with the blocks 1/2 Sigma_B + 1/2 b_B b_B^T at (B, B) and
+ * rho = P b give
+ *   dL/dKj = G_cv = - P E P + 1/2 (alpha rho^T + rho alpha^T),      dL/dr = -rho,
+ * and moments, diagG, *trG are those of G_cv in the layout of mogp_exact_eval, as mogp_exact_loo returns G_loo's (folds of one point each
+ * give exactly that call's numbers); mogp_model_mean_grad and mogp_model_fetch(3) then refer to L.  Factorisation, inversion and what is valid
+ * afterwards: as for mogp_exact_loo (the inverse is formed whole; after a gradient call mogp_model_fetch(0) has nothing to return).  The
+ * workspace is mogp_exact_loo's plus the fold lists and sum |B|^2 doubles of per-fold factors; repeated calls give identical bits.
+ * moments / diagG / trG may be NULL without MOGP_EVAL_GRAD, jitter_abs always.  Not sharded.  On MOGP_ENOTPD *info as for mogp_exact_eval, or,
+ * where Kj factored and a fold's block of its inverse did not, the fold. */
+int  mogp_exact_cv(mogp_model* m, const double* noise_var, const double* data_var, double jitter, int flags, const int32_t* fold, int64_t nfolds,
+                   double* cv, double* mu, double* var, double* moments, double* diagG, double* trG, double* jitter_abs, int64_t* info);
+/* bytes of device memory the handle holds for mogp_exact_loo and mogp_exact_cv alone: 0 until the first call of either (no reference seam) */
 int  mogp_model_loo_bytes(mogp_model* m, int64_t* bytes);
 
 /* replaces Exact.predict_f (gpr/model.py:455-483): mu = Kfs^T Kj^-1 y, var = Kss_diag - colsum((L^-1 Kfs)^2)
@@ -403,7 +423,9 @@ int  mogp_flow_trace(mogp_model* m, int64_t* out, int64_t cap, int64_t* count);
  *        2 = alpha (N), 3 = dp/dr (N), r = y - m(X), of a MOGP_EVAL_GRAD evaluation of the exact, Titsias or Snelson model when it was the
  *        LAST evaluation or prediction on the handle (any later one ends it: EINVAL) -- the vector a mean function's own backward needs (it
  *        replaces autograd through mean(self.X), gpr/model.py:445-448).
- *        Output in the caller's original row order, full N x N (symmetrised / lower-filled). */
+ *        Output in the caller's original row order, full N x N (symmetrised / lower-filled).
+ *        4 = measurement only (tools/cv_time.py): out[0], out[1] = ms of the per-fold kernel and of the zero fill + column kernel of the last
+ *        mogp_exact_cv(MOGP_EVAL_GRAD) that ran with profiling on. */
 int  mogp_model_fetch(mogp_model* m, int which, double* out);
 
 /* The pseudo-input sparse GP of Snelson & Ghahramani (FITC) on the model's data: reference gpr/model.py:516-541

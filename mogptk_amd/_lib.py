@@ -57,6 +57,8 @@ SIGNATURES = {
                                        c_dp, c_dp, c_dp, c_dp, c_dp, c_i64p]),
     "mogp_exact_loo": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.c_double, ctypes.c_int,
                                       c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_i64p]),
+    "mogp_exact_cv": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.c_double, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64,
+                                     c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_i64p]),
     "mogp_model_loo_bytes": (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
     "mogp_exact_predict": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.c_double, c_dp, ctypes.c_int64, c_dp,
                                           ctypes.c_int, c_dp, c_dp, c_i64p]),
@@ -339,8 +341,28 @@ class ExactHandle:
         check(code, info.value)
         return dict(loo=loo.value, mu=mu, var=var, moments=moments, diagG=diagG, trG=trG.value, jitter_abs=jit.value)
 
+    def cv(self, noise_var, jitter, fold, nfolds, grad=True, data_var=None):
+        """leave-fold-out cross-validation (mogp_exact_cv) -> dict(cv, mu[N], var[N], moments[P,T,W], diagG[C], trG, jitter_abs).  fold: N labels in
+        the model's row order, -1 or 0 .. nfolds - 1; mu and var are NaN where the label is -1.  The gradient outputs are those of dL/dKj in the
+        layout of `eval`; never sharded (gpr.Exact refuses before it gets here)"""
+        noise_var = _f64(noise_var)
+        data_var = _f64(data_var)
+        fold = np.ascontiguousarray(fold, dtype=np.int32)
+        if fold.shape != (self.N,):
+            raise ValueError("fold must hold one label per training point")
+        C, T, W = self.C, self.T, self.W
+        cv, trG, jit, info = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int64(0)
+        mu, var = np.empty(self.N), np.empty(self.N)
+        moments = np.zeros((C * (C + 1) // 2, T, W)) if grad else None
+        diagG = np.zeros(C) if grad else None
+        code = lib().mogp_exact_cv(self._h, _dp(noise_var), _dp(data_var), float(jitter), MOGP_EVAL_GRAD if grad else 0,
+                                   fold.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(nfolds), ctypes.byref(cv),
+                                   _dp(mu), _dp(var), _dp(moments), _dp(diagG), ctypes.byref(trG), ctypes.byref(jit), ctypes.byref(info))
+        check(code, info.value)
+        return dict(cv=cv.value, mu=mu, var=var, moments=moments, diagG=diagG, trG=trG.value, jitter_abs=jit.value)
+
     def loo_bytes(self):
-        """device memory held for `loo` alone (mogp_model_loo_bytes): 0 on a handle that never called it"""
+        """device memory held for `loo` and `cv` alone (mogp_model_loo_bytes): 0 on a handle that never called either"""
         b = ctypes.c_int64(0)
         check(lib().mogp_model_loo_bytes(self._h, ctypes.byref(b)))
         return int(b.value)
@@ -620,6 +642,6 @@ class ExactHandle:
         return float(f[0])
 
     def fetch(self, which):
-        out = np.empty(self.N if which in (2, 3) else (self.N, self.N))
+        out = np.empty(2 if which == 4 else self.N if which in (2, 3) else (self.N, self.N))
         check(lib().mogp_model_fetch(self._h, which, _dp(out)))
         return out

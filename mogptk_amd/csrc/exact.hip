@@ -635,9 +635,71 @@ int mogp_exact_loo(mogp_model* m, const double* noise_var, const double* data_va
     return MOGP_OK;
 }
 
+int mogp_exact_cv(mogp_model* m, const double* noise_var, const double* data_var, double jitter, int flags, const int32_t* fold, int64_t nfolds,
+                  double* cv, double* mu, double* var, double* moments, double* diagG, double* trG, double* jitter_abs, int64_t* info) {
+    if (!m) return fail(MOGP_EINVAL, "mogp_exact_cv: model is null");
+    if (!fold || !cv || !mu || !var) return fail(MOGP_EINVAL, "mogp_exact_cv: fold, cv, mu or var is null");
+    const bool grad = (flags & MOGP_EVAL_GRAD) != 0;
+    if (grad && (!moments || !diagG || !trG)) return fail(MOGP_EINVAL, "mogp_exact_cv: gradient outputs are null");
+    int rc;
+    if ((rc = begin_call(m, info, true))) return rc;
+    auto again = [&]() { return mogp_exact_cv(m, noise_var, data_var, jitter, flags, fold, nfolds, cv, mu, var, moments, diagG, trG, jitter_abs, info); };
+    const int C = m->C, W = m->Wt, T = m->T, P = C * (C + 1) / 2;
+    const int64_t N = m->N, Npad = m->Npad;
+    // every allocation and the fold lists before the co-operating kernels are enqueued (see factorize); the pinned block as mogp_exact_loo lays it
+    // out, with the pivot word as it stands BEHIND the folds' factorisations at its end
+    if ((rc = ensure_system(m))) return rc;
+    if ((rc = cv_workspace(m, fold, nfolds, grad))) return rc;
+    const PinLayout pl(m);
+    const size_t pin_cv = pl.total, pin_mu = pin_cv + 1, pin_var = pin_mu + (size_t)Npad, pin_info = pin_var + (size_t)Npad;
+    if ((rc = pin_ensure(m, pin_info + 1))) return rc;
+    GramArgs ga{};
+    // the factorisation and inversion of a gradient evaluation, the COMPLETE inverse: the folds' points lie anywhere, and P E P reads every tile
+    if ((rc = enqueue_inverse(m, noise_var, data_var, jitter, true, /*banded=*/false, nullptr, jitter_abs, info, ga))) return retry_on_streams(m, rc, again);
+    double* v = m->loo.vec.p;
+    if ((rc = cv_points(m, m->k.B.p, grad))) return rc;
+    if (grad) {
+        m->have_W = false;                                    // S goes where the factorisation's own matrix was, as in mogp_exact_loo
+        if ((rc = cv_adjoint(m, m->k.B.p, m->k.A.p))) return rc;
+        if ((rc = loo_moment_pass(m))) return rc;
+        HIP_TRY(hipMemcpyAsync(m->h_pin + pl.moments, m->d_moments.p, (size_t)P * T * W * sizeof(double), hipMemcpyDeviceToHost, m->st));
+        HIP_TRY(hipMemcpyAsync(m->h_pin + pl.diagG, m->d_diagG.p, C * sizeof(double), hipMemcpyDeviceToHost, m->st));
+    }
+    HIP_TRY(hipMemcpyAsync(m->h_pin + pin_cv, v + LOO_SUM * Npad, sizeof(double), hipMemcpyDeviceToHost, m->st));
+    HIP_TRY(hipMemcpyAsync(m->h_pin + pin_mu, v + LOO_MU * Npad, N * sizeof(double), hipMemcpyDeviceToHost, m->st));
+    HIP_TRY(hipMemcpyAsync(m->h_pin + pin_var, v + LOO_VAR * Npad, N * sizeof(double), hipMemcpyDeviceToHost, m->st));
+    HIP_TRY(hipMemcpyAsync(m->h_pin + pin_info, m->d_info.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, m->st));
+    if ((rc = wait_stream(m->st))) return rc;
+    if ((rc = factorize_finish(m, ga, nullptr, info))) return retry_on_streams(m, rc, again);
+    if (grad) m->have_W = false;                              // (factorize_finish set it: k.A holds S now)
+    unsigned long long finfo = 0;
+    std::memcpy(&finfo, m->h_pin + pin_info, sizeof(finfo));
+    if (finfo != std::numeric_limits<unsigned long long>::max()) {          // Kj itself factored: a fold's block of its inverse did not
+        if (info) *info = (int64_t)(finfo - 1) / 256;
+        return fail(MOGP_ENOTPD, "mogp_exact_cv: the block of Kj^-1 over fold " + std::to_string((finfo - 1) / 256) + " is not positive definite (pivot " +
+                                 std::to_string((finfo - 1) % 256 + 1) + " of its factorisation): Kj is too ill-conditioned for this fold");
+    }
+    *cv = m->h_pin[pin_cv];
+    for (int64_t pos = 0; pos < N; ++pos)                     // a point in no fold has no prediction
+        if (m->cv.label[pos] < 0) m->h_pin[pin_mu + pos] = m->h_pin[pin_var + pos] = std::numeric_limits<double>::quiet_NaN();
+    scatter_by_perm(m->sx, m->h_pin + pin_mu, mu);
+    scatter_by_perm(m->sx, m->h_pin + pin_var, var);
+    m->have_Kinv = true;                                      // complete and mirrored: mogp_model_fetch(1) copies it as it is
+    m->kinv_in_A = false;
+    if (!grad) { collect_timing(m, 5); return MOGP_OK; }
+    std::memcpy(moments, m->h_pin + pl.moments, (size_t)P * T * W * sizeof(double));
+    std::memcpy(diagG, m->h_pin + pl.diagG, C * sizeof(double));
+    double tr = 0.0;
+    for (int c = 0; c < C; ++c) tr += diagG[c];
+    *trG = tr;
+    mean_grad_collect(m);
+    collect_timing(m, 6);
+    return MOGP_OK;
+}
+
 int mogp_model_loo_bytes(mogp_model* m, int64_t* bytes) {
     if (!m || !bytes) return fail(MOGP_EINVAL, "mogp_model_loo_bytes: bad argument");
-    *bytes = (int64_t)((m->loo.G.n + m->loo.vec.n) * sizeof(double));
+    *bytes = (int64_t)((m->loo.G.n + m->loo.vec.n) * sizeof(double) + cv_bytes(m));
     return MOGP_OK;
 }
 

@@ -111,6 +111,19 @@ int loo_adjoint(mogp_model* m, const double* kinv, double* scratch) {
     return 0;
 }
 
+// k_loo_sum and k_loo_rank2 for the leave-fold-out evaluation (lfo.hip), which adds its per-fold terms and its rank-two term with the same kernels
+int launch_loo_sum(const double* term, int64_t n, double* out, hipStream_t st) {
+    hipLaunchKernelGGL(k_loo_sum, dim3(1), dim3(256), 0, st, term, n, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_loo_rank2(double* G, int64_t ld, int64_t n, const double* alpha, const double* rho, hipStream_t st) {
+    hipLaunchKernelGGL(k_loo_rank2, dim3((unsigned)((n + 255) / 256), (unsigned)n), dim3(256), 0, st, G, ld, n, alpha, rho);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 int loo_moment_pass(mogp_model* m) {
     const int C = m->C, D = m->D, W = m->Wt, T = m->T, P = C * (C + 1) / 2;
     const int64_t Npad = m->Npad;

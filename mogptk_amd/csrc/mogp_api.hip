@@ -777,6 +777,7 @@ int mogp_model_destroy(mogp_model* m) {
     if (m->tw) { m->tw->release(); delete m->tw; m->tw = nullptr; }
     m->oa.release();
     m->loo.release();
+    m->cv.release();
     m->d_x.release(); m->d_y.release(); m->d_table.release(); m->d_kind.release(); m->d_shape.release();
     m->d_noise.release(); m->d_dvar.release(); m->d_z.release(); m->d_alpha.release(); m->d_zz.release();
     m->d_partial.release(); m->d_moments.release(); m->d_diagG.release(); m->d_tiles.release(); m->d_pair_start.release(); m->strip.release(); m->strip_own.release();
@@ -1056,6 +1057,14 @@ int mogp_model_fetch(mogp_model* m, int which, double* out) {
         for (int64_t pos = 0; pos < N; ++pos) out[m->sx.perm[pos]] = m->mean_w_scale * h[pos];
         return MOGP_OK;
     }
+    if (which == 4) {                           // measurement: the two kernels of lfo.hip in the last profiled mogp_exact_cv(MOGP_EVAL_GRAD)
+        if (!m->cv.timed) return fail(MOGP_EINVAL, "mogp_model_fetch: kernel times need a mogp_exact_cv with MOGP_EVAL_GRAD under mogp_model_set_profiling");
+        float a = 0.f, b = 0.f;
+        HIP_TRY(hipEventElapsedTime(&a, m->cv.ev[0], m->cv.ev[1]));
+        HIP_TRY(hipEventElapsedTime(&b, m->cv.ev[2], m->cv.ev[3]));
+        out[0] = a; out[1] = b;
+        return MOGP_OK;
+    }
     if (which == 2) {
         if (!m->have_W && !m->have_Kinv) return fail(MOGP_EINVAL, "mogp_model_fetch: no evaluation has completed yet");
         std::vector<double> h(Npad);
@@ -1065,7 +1074,7 @@ int mogp_model_fetch(mogp_model* m, int which, double* out) {
     }
     if (which == 0 && !m->have_W) return fail(MOGP_EINVAL, "mogp_model_fetch: no evaluation has completed yet");
     if (which == 1 && !m->have_Kinv) return fail(MOGP_EINVAL, "mogp_model_fetch: Kj^-1 needs an evaluation with MOGP_EVAL_GRAD");
-    if (which != 0 && which != 1) return fail(MOGP_EINVAL, "mogp_model_fetch: which must be 0, 1, 2 or 3");
+    if (which != 0 && which != 1) return fail(MOGP_EINVAL, "mogp_model_fetch: which must be 0 .. 4");
     if (m->k.owned_rows) return fail(MOGP_EINVAL, "mogp_model_fetch: this rank of a sharded evaluation holds only its own tile rows of the matrix");
     if (which == 1 && m->kinv_sparse && !m->kinv_in_A) {
         // the evaluation formed only the tiles of Kj^-1 its gradient reads (kinv_plan): form all of them now, W^T W from the W it left

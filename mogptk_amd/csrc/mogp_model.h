@@ -313,6 +313,25 @@ struct LooWork {
     void release() { G.release(); vec.release(); }
 };
 
+// the folds of the leave-fold-out evaluation (lfo.hip) beside it: fold f holds the sorted positions idx[off[f] .. off[f + 1]) and its m x m
+// factor F_B sits at fac + foff[f] -- sum m_f^2 doubles, not 128^2 per fold.  Uploaded when the labels change, released with the handle
+struct CvWork {
+    mogp::DevBuf<int> off, idx;
+    mogp::DevBuf<long long> foff;
+    mogp::DevBuf<double> fac;
+    std::vector<int> label;             // per sorted position, of the lists on the device
+    int64_t nfolds = 0;
+    int mmax = 0;                       // the largest fold: sizes k_cv_folds' LDS
+    size_t fac_doubles = 0;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};      // with profiling on: around k_cv_folds, around the zero fill + k_cv_cols (mogp_model_fetch 4)
+    bool timed = false;                 // the last gradient call recorded all four
+    void release() {
+        off.release(); idx.release(); foff.release(); fac.release(); label.clear(); nfolds = 0; mmax = 0; fac_doubles = 0;
+        for (auto& e : ev) if (e) { hipError_t r = hipEventDestroy(e); (void)r; e = nullptr; }
+        timed = false;
+    }
+};
+
 // right-hand sides of the prediction's dataflow schedule: X L^T = T, `nt` tile rows (row-major, the leading dimension of the N x N matrices), `ready`: T is in place
 struct FlowRhs { double* T; double* X; int nt; hipEvent_t ready; };
 struct mogp_model {
@@ -421,6 +440,7 @@ struct mogp_model {
     TitsiasWork* tw = nullptr;
     OaWork oa;
     LooWork loo;
+    CvWork cv;
 
     // trainable mean (mean.hip, mogp_model_set_mean): with a table set, d_y / hy hold the residual y0 - m(X) and d_y0 / hy0 the raw targets
     bool mean_on = false, mean_g_valid = false, mean_g_pending = false;
@@ -533,6 +553,14 @@ int loo_workspace(mogp_model* m, bool grad);                        // every all
 int loo_points(mogp_model* m, double* kinv);                        // mu, var, a, b, sqrt a, the N terms of L and their fixed-order sum (vec[LOO_SUM])
 int loo_adjoint(mogp_model* m, const double* kinv, double* scratch);  // rho = Kj^-1 b and G_loo (lower) into LooWork::G; scratch: N x N, overwritten
 int loo_moment_pass(mogp_model* m);                                 // moments of G_loo (every row kind), per-channel diagonal sums, dp/dr = -rho
+int launch_loo_sum(const double* term, int64_t n, double* out, hipStream_t st);       // out[0] = sum of n terms: one workgroup, fixed order
+int launch_loo_rank2(double* G, int64_t ld, int64_t n, const double* alpha, const double* rho, hipStream_t st);   // G (lower) += 1/2 (alpha rho^T + rho alpha^T)
+// lfo.hip -- leave-fold-out cross-validation on the same inverse.  It uses LooWork's vectors (LOO_MU, LOO_VAR, LOO_B, LOO_RHO, LOO_SUM; LOO_TERM
+// holds one term per FOLD) and its N x N adjoint, and keeps the fold lists and the packed per-fold factors in CvWork.
+int cv_workspace(mogp_model* m, const int32_t* fold, int64_t nfolds, bool grad);   // labels through the channel sort, validated; every allocation and upload (before the factorisation is enqueued)
+int cv_points(mogp_model* m, double* kinv, bool grad);              // per fold: mu, diag Sigma, b, the term of L, with grad the factor F_B; then the fixed-order sum (vec[LOO_SUM])
+int cv_adjoint(mogp_model* m, const double* kinv, double* scratch);   // rho = Kj^-1 b and G_cv (lower) into LooWork::G; scratch: N x N, overwritten with S
+size_t cv_bytes(const mogp_model* m);                               // device memory of CvWork
 int eval_sweep(mogp_model* m, const double* noise_var, const double* data_var, double jitter, double* lml, double* jitter_abs, int64_t* info);   // shard.hip
 void one_gpu_call(mogp_model* m);   // ownership state of a previous sharded evaluation off (every one-GPU entry point calls this first)
 int ensure_system(mogp_model* m);     // the N x N system of the exact / OA paths and the tile lists over (X, X), on first use (mogp_api.hip)

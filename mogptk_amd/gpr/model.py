@@ -476,23 +476,73 @@ class Exact(Model):
             h.point_diag_set = False
         return h, table, D
 
-    def _refuse_sharded_loo(self):
+    def _refuse_sharded_loo(self, what="the leave-one-out likelihood"):
         comm = getattr(config, "comm", None)
         if comm is not None and (comm.world > 1 or comm.force):
-            raise NotImplementedError("the leave-one-out likelihood is not carried through the sharded exact evaluation (use_distributed): it "
-                                      "reads the whole of Kj^-1, which no rank of a sharded evaluation holds")
+            raise NotImplementedError("%s is not carried through the sharded exact evaluation (use_distributed): it "
+                                      "reads the whole of Kj^-1, which no rank of a sharded evaluation holds" % what)
 
-    def _eval(self, grad, loo=False):
-        """one device evaluation of the marginal likelihood, or -- loo -- of the leave-one-out likelihood: push, guard, conditioning check"""
-        if loo:
+    FOLD_MAX = 128             # points per fold of the leave-fold-out evaluation: one factor tile (csrc/lfo.hip)
+
+    def _fold_labels(self, folds):
+        """`folds` -- an integer label array of length N (-1: never held out), or a sequence of index arrays -- as (labels int32 (N,), number of
+        folds); what the device would refuse is refused here, by name, before any device call"""
+        N = self.X.shape[0]
+        arr = None
+        if isinstance(folds, np.ndarray) or (len(folds) > 0 and all(np.ndim(f) == 0 for f in folds)):
+            arr = np.asarray(folds)
+        if arr is not None and arr.ndim == 1 and (arr.dtype.kind in "iu" or arr.dtype.kind == "f" and np.all(arr == np.floor(arr))):
+            if arr.shape[0] != N:
+                raise ValueError("a fold label array must hold one label per training point: %d labels for %d points" % (arr.shape[0], N))
+            labels = arr.astype(np.int64)
+            if np.any(labels < -1):
+                raise ValueError("fold labels are -1 (never held out) or 0, 1, ...: found %d" % labels.min())
+            F = int(labels.max()) + 1 if N else 0
+        else:
+            labels = np.full(N, -1, dtype=np.int64)
+            F = len(folds)
+            for f, ind in enumerate(folds):
+                ind = np.asarray(ind).reshape(-1)
+                if ind.size and ind.dtype.kind not in "iu":
+                    raise ValueError("fold %d: indices must be integers" % f)
+                ind = ind.astype(np.int64)
+                if np.any(ind < 0) or np.any(ind >= N):
+                    raise ValueError("fold %d: index %d is out of range for %d training points" % (f, ind[(ind < 0) | (ind >= N)][0], N))
+                if np.unique(ind).size != ind.size:
+                    raise ValueError("fold %d holds a point twice" % f)
+                taken = labels[ind] >= 0
+                if np.any(taken):
+                    raise ValueError("folds %d and %d overlap (point %d): folds are disjoint" % (labels[ind][taken][0], f, ind[taken][0]))
+                labels[ind] = f
+        if F == 0:
+            raise ValueError("no folds: at least one point must be held out")
+        sizes = np.bincount(labels[labels >= 0], minlength=F)
+        for f in range(F):
+            if sizes[f] == 0:
+                raise ValueError("fold %d is empty" % f)
+            if sizes[f] > self.FOLD_MAX:
+                raise ValueError("fold %d holds %d points: the limit is %d points per fold, larger folds are not on the device"
+                                 % (f, sizes[f], self.FOLD_MAX))
+        return labels.astype(np.int32), F
+
+    def _eval(self, grad, score="lml", folds=None):
+        """one device evaluation of the marginal likelihood ("lml"), the leave-one-out likelihood ("loo") or the leave-fold-out one ("cv", over
+        `folds`): push, guard, conditioning check"""
+        if score == "loo":
             self._refuse_sharded_loo()              # before any device call
+        elif score == "cv":
+            self._refuse_sharded_loo("leave-fold-out cross-validation")
+            labels, F = self._fold_labels(folds)
         h, table, D = self._push_terms()
         with self._cholesky_guard():
-            call = h.loo if loo else h.eval
-            run = lambda: call(self._noise_var(), self.jitter, grad=grad, data_var=self.data_variance)
+            if score == "cv":
+                run = lambda: h.cv(self._noise_var(), self.jitter, labels, F, grad=grad, data_var=self.data_variance)
+            else:
+                call = h.loo if score == "loo" else h.eval
+                run = lambda: call(self._noise_var(), self.jitter, grad=grad, data_var=self.data_variance)
             res = run()
-            # (the LML alone: the fast factorisation's log-determinant and z are good to ~1e-7 even at 1e8; a LOO evaluation reads the inverse, like a gradient)
-            again = self._check_conditioning(h, run) if grad or loo else None
+            # (the LML alone: the fast factorisation's log-determinant and z are good to ~1e-7 even at 1e8; a LOO / CV evaluation reads the inverse, like a gradient)
+            again = self._check_conditioning(h, run) if grad or score != "lml" else None
             return (res if again is None else again), table, D
 
     CONDITION_WARN = 1e5       # on the pivot-spread estimate (max L_jj / min L_jj)^2, a LOWER bound of cond(Kj) -- 9e5 where cond is 7e7, 9e3 where it is 8e5;
@@ -533,13 +583,13 @@ class Exact(Model):
         res, _, _ = self._eval(grad=False)
         return config.dtype(res["lml"])
 
-    def _loss_impl(self, loo=False):
+    def _loss_impl(self, score="lml", folds=None):
         """reference gpr/model.py:279-292: zero grads, loss = -LML - log prior, fresh `.grad` on every
         parameter in the graph.  Gradients come from the device's moment pass + the host chain rule.
-        loo: the leave-one-out likelihood L in the LML's place -- the device returns the moments, diagonal sums and trace of dL/dKj in the
-        same layout, so the chain rule below is the same."""
+        score "loo" / "cv": the leave-one-out / leave-fold-out likelihood L in the LML's place -- the device returns the moments, diagonal sums
+        and trace of dL/dKj in the same layout, so the chain rule below is the same."""
         self.zero_grad(set_to_none=True)
-        res, table, D = self._eval(grad=True, loo=loo)
+        res, table, D = self._eval(grad=True, score=score, folds=folds)
         counts = self._train_counts()
         jit_rel = self.jitter * res["trG"] / self.X.shape[0]            # d LML / d (mean diag) through the jitter term (:244)
 
@@ -561,12 +611,15 @@ class Exact(Model):
         # noise: d LML / d sigma_c = 2 sigma_c (sum_{k in c} G_kk + jitter n_c/N tr G)
         self._noise_backward(res["diagG"] + jit_rel * counts)
         self._mean_backward(self._handle)
-        return config.dtype(-res["loo" if loo else "lml"] - self.log_prior())
+        return config.dtype(-res[score] - self.log_prior())
 
     # -- leave-one-out predictive likelihood (Rasmussen & Williams 5.4.2; csrc/loo.hip) -----------------------------------------
     def loo(self):
         """-> (mu, var), each (N, 1): mean and variance (noise included) of the prediction of every training target from all the others"""
-        res, _, _ = self._eval(grad=False, loo=True)
+        res, _, _ = self._eval(grad=False, score="loo")
+        return self._held_out(res)
+
+    def _held_out(self, res):
         mu = res["mu"].reshape(-1, 1)
         if self.mean is not None and not (self._trainable_mean() and self._mean_affine()[0] is not None):
             mu = self._add_mean(mu, self.X)         # the device holds y - m(X) as its targets (an affine gpr.Mean is on the device: it holds y)
@@ -574,13 +627,30 @@ class Exact(Model):
 
     def loo_log_likelihood(self):
         """sum_i log p(y_i | X, y_-i): one device evaluation without gradients"""
-        res, _, _ = self._eval(grad=False, loo=True)
+        res, _, _ = self._eval(grad=False, score="loo")
         return config.dtype(res["loo"])
 
     def loo_loss(self):
         """-(leave-one-out log-likelihood) - log prior, and like `loss` a fresh `.grad` on every parameter: kernel, noise, trainable mean"""
         with terms_cache():
-            return self._loss_impl(loo=True)
+            return self._loss_impl(score="loo")
+
+    # -- leave-fold-out cross-validation (DESIGN 1d; csrc/lfo.hip) ----------------------------------------------------------------
+    def cv(self, folds):
+        """-> (mu, var), each (N, 1): mean and variance (noise included) of the prediction of every held-out target from the points outside
+        its fold; NaN for a point in no fold.  `folds`: N integer labels (-1: never held out) or a sequence of index arrays, 1 .. 128 points each"""
+        res, _, _ = self._eval(grad=False, score="cv", folds=folds)
+        return self._held_out(res)
+
+    def cv_log_likelihood(self, folds):
+        """sum_f log p(y_Bf | X, y_-Bf), each fold predicted jointly from the points outside it: one device evaluation without gradients"""
+        res, _, _ = self._eval(grad=False, score="cv", folds=folds)
+        return config.dtype(res["cv"])
+
+    def cv_loss(self, folds):
+        """-(leave-fold-out log-likelihood) - log prior, and like `loss` a fresh `.grad` on every parameter: kernel, noise, trainable mean"""
+        with terms_cache():
+            return self._loss_impl(score="cv", folds=folds)
 
     def predict_f(self, X, full=False):
         """reference gpr/model.py:455-483"""

@@ -592,13 +592,40 @@ class Model:
 
     def _exact_only(self, what):
         if not isinstance(self.gpr, gpr.Exact):
-            raise ValueError("%s needs exact inference (mogptk_amd.Exact): %s has no leave-one-out likelihood" % (what, self.gpr.name()))
+            raise ValueError("%s needs exact inference (mogptk_amd.Exact): %s has no leave-one-out or leave-fold-out likelihood" % (what, self.gpr.name()))
 
     def loo_log_likelihood(self):
         """Leave-one-out predictive log-likelihood sum_i log p(y_i | X, y_-i) in transformed space (Rasmussen & Williams 5.4.2): a score for
         comparing kernels on the same data without setting points aside; exact inference only."""
         self._exact_only("loo_log_likelihood()")
         return float(self.gpr.loo_log_likelihood())
+
+    def cv_log_likelihood(self, folds):
+        """Leave-fold-out predictive log-likelihood sum_f log p(y_Bf | X, y_-Bf) in transformed space: every fold -- a set of 1 .. 128 training
+        points, as integer labels over the training points (-1: never held out) or as a sequence of index arrays -- is predicted jointly from
+        the points outside it.  On a densely sampled series, where the two neighbours of a single held-out point interpolate it, this asks
+        what `error` on removed ranges asks, without refitting; `block_folds` makes such ranges.  Exact inference only."""
+        self._exact_only("cv_log_likelihood()")
+        return float(self.gpr.cv_log_likelihood(folds))
+
+    def block_folds(self, size):
+        """Fold labels over the training points, in the model's row order (channels stacked): within each channel, consecutive runs of `size`
+        points in input order form one fold each; the last run of a channel may be shorter.  1 <= size <= 128; one input dimension only."""
+        if self.dataset.get_input_dims()[0] != 1:
+            raise ValueError("block_folds orders the points of a channel by their input: one input dimension only")
+        size = int(size)
+        if not 1 <= size <= gpr.Exact.FOLD_MAX:
+            raise ValueError("block_folds: size must be 1 .. %d points" % gpr.Exact.FOLD_MAX)
+        X = np.asarray(self.gpr.X, dtype=np.float64)
+        chan = X[:, 0].astype(np.int64) if self.is_multioutput else np.zeros(X.shape[0], dtype=np.int64)
+        labels = np.empty(X.shape[0], dtype=np.int32)
+        first = 0
+        for c in np.unique(chan):
+            rows = np.flatnonzero(chan == c)
+            rows = rows[np.argsort(X[rows, -1], kind="stable")]
+            labels[rows] = first + np.arange(rows.size) // size
+            first += -(-rows.size // size)
+        return labels
 
     _ERROR_MEASURES = {"mae": mean_absolute_error, "mape": mean_absolute_percentage_error,
                        "smape": symmetric_mean_absolute_percentage_error, "mse": mean_squared_error,
@@ -625,7 +652,7 @@ class Model:
                      for channel, part, x in zip(self.dataset, np.split(flat, ends[:-1]), X)]
         return measure(np.concatenate(truth), np.concatenate(predicted))
 
-    def train(self, method="Adam", iters=500, verbose=False, error=None, plot=False, jit=None, objective="lml", **kwargs):
+    def train(self, method="Adam", iters=500, verbose=False, error=None, plot=False, jit=None, objective="lml", folds=None, **kwargs):
         """
         Optimise the hyper-parameters (reference mogptk/model.py:441-579): `iters` optimiser steps and
         `iters+1` loss evaluations; `times/losses/errors` are continued across calls, the optimiser state is not.
@@ -638,7 +665,8 @@ class Model:
             plot (bool): accepted; plotting is out of scope.
             jit (bool): accepted and ignored (one native call per evaluation already).
             objective (str): "lml" minimises -(log marginal likelihood) - log prior; "loo" the negative leave-one-out predictive
-                log-likelihood - log prior (exact inference only).
+                log-likelihood - log prior; "cv" the negative leave-fold-out log-likelihood over `folds` - log prior (both exact inference only).
+            folds: the folds of objective="cv", as `cv_log_likelihood` takes them (`block_folds` makes them).
             **kwargs: passed to the optimiser (lr=..., betas=..., ...).
 
         Returns:
@@ -655,11 +683,17 @@ class Model:
             if not isinstance(e, float) and (not isinstance(e, np.ndarray) or e.size != 1):
                 raise ValueError("error function must return a float")
 
-        if objective not in ("lml", "loo"):
-            raise ValueError("objective must be 'lml' or 'loo'")
+        if objective not in ("lml", "loo", "cv"):
+            raise ValueError("objective must be 'lml', 'loo' or 'cv'")
+        if folds is not None and objective != "cv":
+            raise ValueError("folds belong to objective='cv'")
         if objective == "loo":
             self._exact_only("train(objective='loo')")
-        loss_fn = self.loss if objective == "lml" else (lambda: float(self.gpr.loo_loss()))
+        if objective == "cv":
+            self._exact_only("train(objective='cv')")
+            if folds is None:
+                raise ValueError("objective='cv' needs folds (see block_folds)")
+        loss_fn = {"lml": self.loss, "loo": lambda: float(self.gpr.loo_loss()), "cv": lambda: float(self.gpr.cv_loss(folds))}[objective]
 
         if method.lower() in ("l-bfgs", "lbfgs", "l-bfgs-b", "lbfgsb"):
             method = "LBFGS"
