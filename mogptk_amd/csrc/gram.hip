@@ -1653,15 +1653,21 @@ __global__ __launch_bounds__(256, (DT == 1 && !RAD ? 2 : 1)) void k_moments(Mome
             ++nred;
             for (int w = 0; w < W; ++w) rb[w * RSTRIDE + tid + (tid >> 4)] = mom[w];
             __syncthreads();
-            if (tid < 16 * W) {
-                const int w = tid >> 4, i = tid & 15;
-                const double* src = rb + w * RSTRIDE + i * 17;
-                double v = 0.0;
+            // 256 threads take 16 moments at a time: rows of more than 16 (2 + 3 D from D = 5 on, 2 + 5 D from D = 3 on) need a second pass --
+            // without it moments 16 .. W - 1 were never written, and the pair's sum read whatever the scratch held
+            constexpr int NPASS = (WM + 15) / 16;
 #pragma unroll
-                for (int k = 0; k < 16; ++k) v += src[k];
+            for (int pass = 0; pass < NPASS; ++pass) {
+                const int w = pass * 16 + (tid >> 4), i = tid & 15;
+                if (w < W) {
+                    const double* src = rb + w * RSTRIDE + i * 17;
+                    double v = 0.0;
 #pragma unroll
-                for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-                if (i == 0) outp[(size_t)(t0 + t) * W + w] = v;
+                    for (int k = 0; k < 16; ++k) v += src[k];
+#pragma unroll
+                    for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+                    if (i == 0) outp[(size_t)(t0 + t) * W + w] = v;
+                }
             }
             if (NBUF == 1) __syncthreads();
         }
