@@ -313,53 +313,44 @@ class ExactHandle:
                 return self.eval_sharded(noise_var, jitter, data_var)
             from . import dist as _dist
             return _dist.sharded_eval(self, comm, noise_var, jitter, data_var)
-        C, T, W = self.C, self.T, self.W
-        lml = ctypes.c_double()
-        trG = ctypes.c_double()
-        jit = ctypes.c_double()
-        info = ctypes.c_int64(0)
-        moments = np.zeros((C * (C + 1) // 2, T, W)) if grad else None
-        diagG = np.zeros(C) if grad else None
+        lml, trG, jit, info = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int64(0)
+        moments, diagG = self._grad_outputs(grad)
         code = lib().mogp_exact_eval(self._h, _dp(noise_var), _dp(data_var), float(jitter),
                                      MOGP_EVAL_GRAD if grad else 0, ctypes.byref(lml), _dp(moments), _dp(diagG),
                                      ctypes.byref(trG), ctypes.byref(jit), ctypes.byref(info))
         check(code, info.value)
         return dict(lml=lml.value, moments=moments, diagG=diagG, trG=trG.value, jitter_abs=jit.value)
 
+    def _grad_outputs(self, grad=True):
+        """(moments[P,T,W], diagG[C]) for an entry point to fill; (None, None) without gradients"""
+        C = self.C
+        return (np.zeros((C * (C + 1) // 2, self.T, self.W)), np.zeros(C)) if grad else (None, None)
+
+    def _held_out(self, key, entry, noise_var, jitter, grad, data_var, *score_args):
+        """a held-out score (mogp_exact_loo / mogp_exact_cv; score_args: what the entry point takes in front of its outputs) -> the result dict under `key`"""
+        noise_var = _f64(noise_var)
+        data_var = _f64(data_var)
+        score, trG, jit, info = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int64(0)
+        mu, var = np.empty(self.N), np.empty(self.N)
+        moments, diagG = self._grad_outputs(grad)
+        code = entry(self._h, _dp(noise_var), _dp(data_var), float(jitter), MOGP_EVAL_GRAD if grad else 0, *score_args, ctypes.byref(score),
+                     _dp(mu), _dp(var), _dp(moments), _dp(diagG), ctypes.byref(trG), ctypes.byref(jit), ctypes.byref(info))
+        check(code, info.value)
+        return {key: score.value, "mu": mu, "var": var, "moments": moments, "diagG": diagG, "trG": trG.value, "jitter_abs": jit.value}
+
     def loo(self, noise_var, jitter, grad=True, data_var=None):
         """leave-one-out predictive log-likelihood (mogp_exact_loo) -> dict(loo, mu[N], var[N], moments[P,T,W], diagG[C], trG, jitter_abs): the
         gradient outputs are those of dL/dKj in the layout of `eval`; never sharded (gpr.Exact refuses before it gets here)"""
-        noise_var = _f64(noise_var)
-        data_var = _f64(data_var)
-        C, T, W = self.C, self.T, self.W
-        loo, trG, jit, info = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int64(0)
-        mu, var = np.empty(self.N), np.empty(self.N)
-        moments = np.zeros((C * (C + 1) // 2, T, W)) if grad else None
-        diagG = np.zeros(C) if grad else None
-        code = lib().mogp_exact_loo(self._h, _dp(noise_var), _dp(data_var), float(jitter), MOGP_EVAL_GRAD if grad else 0, ctypes.byref(loo),
-                                    _dp(mu), _dp(var), _dp(moments), _dp(diagG), ctypes.byref(trG), ctypes.byref(jit), ctypes.byref(info))
-        check(code, info.value)
-        return dict(loo=loo.value, mu=mu, var=var, moments=moments, diagG=diagG, trG=trG.value, jitter_abs=jit.value)
+        return self._held_out("loo", lib().mogp_exact_loo, noise_var, jitter, grad, data_var)
 
     def cv(self, noise_var, jitter, fold, nfolds, grad=True, data_var=None):
         """leave-fold-out cross-validation (mogp_exact_cv) -> dict(cv, mu[N], var[N], moments[P,T,W], diagG[C], trG, jitter_abs).  fold: N labels in
         the model's row order, -1 or 0 .. nfolds - 1; mu and var are NaN where the label is -1.  The gradient outputs are those of dL/dKj in the
         layout of `eval`; never sharded (gpr.Exact refuses before it gets here)"""
-        noise_var = _f64(noise_var)
-        data_var = _f64(data_var)
         fold = np.ascontiguousarray(fold, dtype=np.int32)
         if fold.shape != (self.N,):
             raise ValueError("fold must hold one label per training point")
-        C, T, W = self.C, self.T, self.W
-        cv, trG, jit, info = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int64(0)
-        mu, var = np.empty(self.N), np.empty(self.N)
-        moments = np.zeros((C * (C + 1) // 2, T, W)) if grad else None
-        diagG = np.zeros(C) if grad else None
-        code = lib().mogp_exact_cv(self._h, _dp(noise_var), _dp(data_var), float(jitter), MOGP_EVAL_GRAD if grad else 0,
-                                   fold.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(nfolds), ctypes.byref(cv),
-                                   _dp(mu), _dp(var), _dp(moments), _dp(diagG), ctypes.byref(trG), ctypes.byref(jit), ctypes.byref(info))
-        check(code, info.value)
-        return dict(cv=cv.value, mu=mu, var=var, moments=moments, diagG=diagG, trG=trG.value, jitter_abs=jit.value)
+        return self._held_out("cv", lib().mogp_exact_cv, noise_var, jitter, grad, data_var, fold.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(nfolds))
 
     def loo_bytes(self):
         """device memory held for `loo` and `cv` alone (mogp_model_loo_bytes): 0 on a handle that never called either"""
@@ -369,9 +360,8 @@ class ExactHandle:
 
     def eval_sharded(self, noise_var, jitter, data_var=None):
         """mogp_exact_eval_sharded: the evaluation spread over the ranks of the context's communicator (collectives inside the library)"""
-        C, T, W = self.C, self.T, self.W
         lml, trG, jit, info = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int64(0)
-        moments, diagG = np.zeros((C * (C + 1) // 2, T, W)), np.zeros(C)
+        moments, diagG = self._grad_outputs()
         code = lib().mogp_exact_eval_sharded(self._h, _dp(_f64(noise_var)), _dp(_f64(data_var)), float(jitter), ctypes.byref(lml), _dp(moments),
                                              _dp(diagG), ctypes.byref(trG), ctypes.byref(jit), ctypes.byref(info))
         check(code, info.value)
@@ -423,9 +413,8 @@ class ExactHandle:
         return buf.value, count.value
 
     def shard_finish(self):
-        C, T, W = self.C, self.T, self.W
         lml, info = ctypes.c_double(), ctypes.c_int64(0)
-        moments, diagG = np.zeros((C * (C + 1) // 2, T, W)), np.zeros(C)
+        moments, diagG = self._grad_outputs()
         check(lib().mogp_shard_finish(self._h, ctypes.byref(lml), _dp(moments), _dp(diagG), ctypes.byref(info)), info.value)
         return lml.value, moments, diagG
 

@@ -1,7 +1,8 @@
 // exact.hip -- the exact GP path on one GPU, per evaluation:
 //   Gram (lower tiles, noise + jitter fused on the diagonal) -> blocked Cholesky -> level-batched triangular inverse
 //   -> alpha / log-det -> LAUUM (K^-1) -> gradient-moment pass -> a few hundred doubles back to the host,
-// and the prediction on the factor.  What the entry points share is written once: begin_call, exact_begin, test_side, report_not_pd (also used by shard.hip), PinLayout, FactorPlan, retry_on_streams.
+// and the prediction on the factor.  What the entry points share is written once: begin_call, exact_begin, test_side, report_not_pd (also used by shard.hip), PinLayout, FactorPlan, retry_on_streams,
+// grad_enqueue / grad_collect (the gradient outputs' way home) and held_out_eval (the one schedule of mogp_exact_loo and mogp_exact_cv).
 #include "mogp_model.h"
 #include <cstdlib>
 #include <limits>
@@ -119,14 +120,18 @@ static int pin_ensure(mogp_model* m, size_t n) {
     m->h_pin_n = n;
     return 0;
 }
-// The pinned block of an evaluation's scalars, in doubles: [nb log-det parts | nzz z^T z parts | pivot report | P T W moments | C diagG | 2 pivots].  The ONE place
-// that knows the order: factorize sizes and fills it, mogp_exact_eval adds the moments, factorize_finish reads it behind the evaluation's one stream sync.
+// The pinned block of an evaluation's scalars, in doubles: [nb log-det parts | nzz z^T z parts | pivot report | P T W moments | C diagG | 2 pivots], and behind
+// `total` the slots of a held-out evaluation (mogp_exact_loo / mogp_exact_cv): [score | mu, Npad | var, Npad | pivot word of the folds' factorisations].  The ONE
+// place that knows the order: factorize sizes and fills the evaluation's own part, grad_enqueue adds the moments, held_out_eval sizes and fills the held-out
+// slots, factorize_finish reads the block behind the evaluation's one stream sync.
 struct PinLayout {
-    size_t nzz, logdet = 0, zz, info, moments, diagG, pivots, total;
+    size_t nzz, logdet = 0, zz, info, moments, diagG, pivots, total, score, mu, var, fold_info;
     PinLayout(int nb, int64_t Npad, int C, int T, int Wt) : nzz((size_t)((Npad + 3) / 4)) {
         zz = (size_t)nb; info = zz + nzz; moments = info + 1; diagG = moments + (size_t)(C * (C + 1) / 2) * T * Wt; pivots = diagG + C; total = pivots + 2;
+        score = total; mu = score + 1; var = mu + (size_t)Npad; fold_info = var + (size_t)Npad;
     }
     explicit PinLayout(const mogp_model* m) : PinLayout(m->nb, m->Npad, m->C, m->T, m->Wt) {}
+    size_t held_out_total(bool folds) const { return fold_info + (folds ? 1 : 0); }      // (leave-one-out has no folds to report on)
 };
 
 namespace mogp {
@@ -531,6 +536,89 @@ static int enqueue_inverse(mogp_model* m, const double* noise_var, const double*
     return mark(m, 5);
 }
 
+// The gradient outputs of an evaluation on their way home.  grad_enqueue: d_moments and d_diagG into the pinned block, behind whatever pass filled them and in
+// front of the evaluation's one wait.  grad_finish, after that wait: the trace in channel order, dp/dr for the mean table, the stage times up to mark 6;
+// grad_collect: the two results out of the pinned block first.
+static int grad_enqueue(mogp_model* m, const PinLayout& pl) {
+    HIP_TRY(hipMemcpyAsync(m->h_pin + pl.moments, m->d_moments.p, (pl.diagG - pl.moments) * sizeof(double), hipMemcpyDeviceToHost, m->st));
+    HIP_TRY(hipMemcpyAsync(m->h_pin + pl.diagG, m->d_diagG.p, m->C * sizeof(double), hipMemcpyDeviceToHost, m->st));
+    return 0;
+}
+static void grad_finish(mogp_model* m, const double* diagG, double* trG) {
+    double tr = 0.0;
+    for (int c = 0; c < m->C; ++c) tr += diagG[c];
+    *trG = tr;
+    mean_grad_collect(m);
+    collect_timing(m, 6);
+}
+static void grad_collect(mogp_model* m, const PinLayout& pl, double* moments, double* diagG, double* trG) {
+    std::memcpy(moments, m->h_pin + pl.moments, (pl.diagG - pl.moments) * sizeof(double));
+    std::memcpy(diagG, m->h_pin + pl.diagG, m->C * sizeof(double));
+    grad_finish(m, diagG, trG);
+}
+
+// The held-out scores of the exact path are ONE schedule: the COMPLETE inverse of a gradient evaluation (the adjoint Kj^-1 E Kj^-1 reads every tile), the
+// score's points pass, with gradients its adjoint where G = 1/2 (alpha alpha^T - Kj^-1) stands for the marginal likelihood (rho, S, -S S^T, the rank-two term;
+// loo.hip) and the moment pass in the marginal likelihood's layout -- and score, mu, var and the gradient outputs home through the pinned block behind ONE wait.
+// fold null: leave-one-out (loo.hip).  fold, the caller's labels: leave-fold-out (lfo.hip), which adds the fold lists to the workspace, the pivot word as it
+// stands BEHIND the folds' own factorisations, and NaN for the points in no fold.  The two entry points have checked their arguments.
+static int held_out_eval(mogp_model* m, const double* noise_var, const double* data_var, double jitter, int flags, const int32_t* fold, int64_t nfolds,
+                         double* score, double* mu, double* var, double* moments, double* diagG, double* trG, double* jitter_abs, int64_t* info) {
+    const bool grad = (flags & MOGP_EVAL_GRAD) != 0, folds = fold != nullptr;
+    int rc;
+    if ((rc = begin_call(m, info, true))) return rc;
+    auto again = [&]() {                                      // the public entry point, with the same arguments
+        return folds ? mogp_exact_cv(m, noise_var, data_var, jitter, flags, fold, nfolds, score, mu, var, moments, diagG, trG, jitter_abs, info)
+                     : mogp_exact_loo(m, noise_var, data_var, jitter, flags, score, mu, var, moments, diagG, trG, jitter_abs, info);
+    };
+    // every allocation (and the fold lists) before the co-operating kernels are enqueued (see factorize): the score's workspace, and the pinned block with the
+    // held-out slots behind the evaluation's own scalars
+    if ((rc = ensure_system(m))) return rc;
+    if ((rc = folds ? cv_workspace(m, fold, nfolds, grad) : loo_workspace(m, grad))) return rc;
+    const PinLayout pl(m);
+    if ((rc = pin_ensure(m, pl.held_out_total(folds)))) return rc;
+    const int64_t N = m->N, Npad = m->Npad;
+    GramArgs ga{};
+    if ((rc = enqueue_inverse(m, noise_var, data_var, jitter, true, /*banded=*/false, nullptr, jitter_abs, info, ga))) return retry_on_streams(m, rc, again);
+    if ((rc = held_out_points(m, m->k.B.p, folds, grad))) return rc;
+    if (grad) {
+        // S goes where the factorisation's own matrix was (k.A: the Gram matrix, then L or W): nothing reads it after alpha, and the next evaluation
+        // builds it anew -- so the handle no longer holds W for mogp_model_fetch(0)
+        m->have_W = false;
+        if ((rc = held_out_adjoint(m, m->k.B.p, m->k.A.p, folds))) return rc;
+        if ((rc = loo_moment_pass(m))) return rc;
+        if ((rc = grad_enqueue(m, pl))) return rc;
+    }
+    const double* v = m->loo.vec.p;
+    double* h = m->h_pin;
+    HIP_TRY(hipMemcpyAsync(h + pl.score, v + LOO_SUM * Npad, sizeof(double), hipMemcpyDeviceToHost, m->st));
+    HIP_TRY(hipMemcpyAsync(h + pl.mu, v + LOO_MU * Npad, N * sizeof(double), hipMemcpyDeviceToHost, m->st));
+    HIP_TRY(hipMemcpyAsync(h + pl.var, v + LOO_VAR * Npad, N * sizeof(double), hipMemcpyDeviceToHost, m->st));
+    if (folds) HIP_TRY(hipMemcpyAsync(h + pl.fold_info, m->d_info.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, m->st));
+    if ((rc = wait_stream(m->st))) return rc;
+    if ((rc = factorize_finish(m, ga, nullptr, info))) return retry_on_streams(m, rc, again);
+    if (grad) m->have_W = false;                              // (factorize_finish set it: k.A holds S now)
+    if (folds) {
+        unsigned long long finfo = 0;
+        std::memcpy(&finfo, h + pl.fold_info, sizeof(finfo));
+        if (finfo != std::numeric_limits<unsigned long long>::max()) {          // Kj itself factored: a fold's block of its inverse did not
+            if (info) *info = (int64_t)(finfo - 1) / 256;
+            return fail(MOGP_ENOTPD, "mogp_exact_cv: the block of Kj^-1 over fold " + std::to_string((finfo - 1) / 256) + " is not positive definite (pivot " +
+                                     std::to_string((finfo - 1) % 256 + 1) + " of its factorisation): Kj is too ill-conditioned for this fold");
+        }
+        for (int64_t pos = 0; pos < N; ++pos)                 // a point in no fold has no prediction
+            if (m->cv.label[pos] < 0) h[pl.mu + pos] = h[pl.var + pos] = std::numeric_limits<double>::quiet_NaN();
+    }
+    *score = h[pl.score];
+    scatter_by_perm(m->sx, h + pl.mu, mu);
+    scatter_by_perm(m->sx, h + pl.var, var);
+    m->have_Kinv = true;                                      // complete and mirrored: mogp_model_fetch(1) copies it as it is
+    m->kinv_in_A = false;
+    if (!grad) { collect_timing(m, 5); return MOGP_OK; }
+    grad_collect(m, pl, moments, diagG, trG);
+    return MOGP_OK;
+}
+
 extern "C" {
 
 int mogp_exact_eval(mogp_model* m, const double* noise_var, const double* data_var, double jitter, int flags,
@@ -553,32 +641,24 @@ int mogp_exact_eval(mogp_model* m, const double* noise_var, const double* data_v
     else if ((rc = enqueue_inverse(m, noise_var, data_var, jitter, grad, /*banded=*/true, lml, jitter_abs, info, ga))) return retry_on_streams(m, rc, again);
     if (!grad) { collect_timing(m, 4); return MOGP_OK; }
 
-    const int C = m->C, W = m->Wt, T = m->T, P = C * (C + 1) / 2;
-
     // K^-1: the sweep left -Kj^-1 in k.A; the POTRF path W^T W (lower tiles, full diagonal tiles) in k.B
     const double* kinv = sweep ? m->k.A.p : m->k.B.p;
     const double ksign = sweep ? -1.0 : 1.0;
+    const PinLayout pl(m);
     if (sweep && (rc = mark(m, 5))) return rc;
     if (sweep) {
         if ((rc = moment_pass(m, kinv, ksign, moments, diagG))) return rc;
     } else {
         // everything of this evaluation is enqueued before the host waits ONCE: scalars and moments come back through the pinned block
         if ((rc = moment_pass_device(m, kinv, ksign))) return rc;
-        const PinLayout pl(m);
-        HIP_TRY(hipMemcpyAsync(m->h_pin + pl.moments, m->d_moments.p, (size_t)P * T * W * sizeof(double), hipMemcpyDeviceToHost, m->st));
-        HIP_TRY(hipMemcpyAsync(m->h_pin + pl.diagG, m->d_diagG.p, C * sizeof(double), hipMemcpyDeviceToHost, m->st));
+        if ((rc = grad_enqueue(m, pl))) return rc;
         if ((rc = wait_stream(m->st))) return rc;
         if ((rc = factorize_finish(m, ga, lml, info))) return retry_on_streams(m, rc, again);
-        std::memcpy(moments, m->h_pin + pl.moments, (size_t)P * T * W * sizeof(double));
-        std::memcpy(diagG, m->h_pin + pl.diagG, C * sizeof(double));
     }
-    double tr = 0.0;
-    for (int c = 0; c < C; ++c) tr += diagG[c];
-    *trG = tr;
     m->have_Kinv = true;
     m->kinv_in_A = sweep;
-    mean_grad_collect(m);
-    collect_timing(m, 6);
+    if (sweep) grad_finish(m, diagG, trG);
+    else grad_collect(m, pl, moments, diagG, trG);
     return MOGP_OK;
 }
 
@@ -586,115 +666,16 @@ int mogp_exact_loo(mogp_model* m, const double* noise_var, const double* data_va
                    double* loo, double* mu, double* var, double* moments, double* diagG, double* trG, double* jitter_abs, int64_t* info) {
     if (!m) return fail(MOGP_EINVAL, "mogp_exact_loo: model is null");
     if (!loo || !mu || !var) return fail(MOGP_EINVAL, "mogp_exact_loo: loo, mu or var is null");
-    const bool grad = (flags & MOGP_EVAL_GRAD) != 0;
-    if (grad && (!moments || !diagG || !trG)) return fail(MOGP_EINVAL, "mogp_exact_loo: gradient outputs are null");
-    int rc;
-    if ((rc = begin_call(m, info, true))) return rc;
-    auto again = [&]() { return mogp_exact_loo(m, noise_var, data_var, jitter, flags, loo, mu, var, moments, diagG, trG, jitter_abs, info); };
-    const int C = m->C, W = m->Wt, T = m->T, P = C * (C + 1) / 2;
-    const int64_t N = m->N, Npad = m->Npad;
-    // every allocation before the co-operating kernels are enqueued (see factorize): the LOO workspace, and the pinned block with L, mu and var behind the evaluation's own scalars
-    if ((rc = ensure_system(m))) return rc;
-    if ((rc = loo_workspace(m, grad))) return rc;
-    const PinLayout pl(m);
-    const size_t pin_loo = pl.total, pin_mu = pin_loo + 1, pin_var = pin_mu + (size_t)Npad;
-    if ((rc = pin_ensure(m, pin_var + (size_t)Npad))) return rc;
-    GramArgs ga{};
-    // the factorisation and inversion of a gradient evaluation, the COMPLETE inverse: Kj^-1 diag(a) Kj^-1 reads every tile
-    if ((rc = enqueue_inverse(m, noise_var, data_var, jitter, true, /*banded=*/false, nullptr, jitter_abs, info, ga))) return retry_on_streams(m, rc, again);
-    double* v = m->loo.vec.p;
-    if ((rc = loo_points(m, m->k.B.p))) return rc;
-    if (grad) {
-        // S = Kj^-1 diag(sqrt a) goes where the factorisation's own matrix was (k.A: the Gram matrix, then L or W): nothing reads it after alpha,
-        // and the next evaluation builds it anew -- so the handle no longer holds W for mogp_model_fetch(0)
-        m->have_W = false;
-        if ((rc = loo_adjoint(m, m->k.B.p, m->k.A.p))) return rc;
-        if ((rc = loo_moment_pass(m))) return rc;
-        HIP_TRY(hipMemcpyAsync(m->h_pin + pl.moments, m->d_moments.p, (size_t)P * T * W * sizeof(double), hipMemcpyDeviceToHost, m->st));
-        HIP_TRY(hipMemcpyAsync(m->h_pin + pl.diagG, m->d_diagG.p, C * sizeof(double), hipMemcpyDeviceToHost, m->st));
-    }
-    HIP_TRY(hipMemcpyAsync(m->h_pin + pin_loo, v + LOO_SUM * Npad, sizeof(double), hipMemcpyDeviceToHost, m->st));
-    HIP_TRY(hipMemcpyAsync(m->h_pin + pin_mu, v + LOO_MU * Npad, N * sizeof(double), hipMemcpyDeviceToHost, m->st));
-    HIP_TRY(hipMemcpyAsync(m->h_pin + pin_var, v + LOO_VAR * Npad, N * sizeof(double), hipMemcpyDeviceToHost, m->st));
-    if ((rc = wait_stream(m->st))) return rc;
-    if ((rc = factorize_finish(m, ga, nullptr, info))) return retry_on_streams(m, rc, again);
-    if (grad) m->have_W = false;                              // (factorize_finish set it: k.A holds S now)
-    *loo = m->h_pin[pin_loo];
-    scatter_by_perm(m->sx, m->h_pin + pin_mu, mu);
-    scatter_by_perm(m->sx, m->h_pin + pin_var, var);
-    m->have_Kinv = true;                                      // complete and mirrored: mogp_model_fetch(1) copies it as it is
-    m->kinv_in_A = false;
-    if (!grad) { collect_timing(m, 5); return MOGP_OK; }
-    std::memcpy(moments, m->h_pin + pl.moments, (size_t)P * T * W * sizeof(double));
-    std::memcpy(diagG, m->h_pin + pl.diagG, C * sizeof(double));
-    double tr = 0.0;
-    for (int c = 0; c < C; ++c) tr += diagG[c];
-    *trG = tr;
-    mean_grad_collect(m);
-    collect_timing(m, 6);
-    return MOGP_OK;
+    if ((flags & MOGP_EVAL_GRAD) && (!moments || !diagG || !trG)) return fail(MOGP_EINVAL, "mogp_exact_loo: gradient outputs are null");
+    return held_out_eval(m, noise_var, data_var, jitter, flags, nullptr, 0, loo, mu, var, moments, diagG, trG, jitter_abs, info);
 }
 
 int mogp_exact_cv(mogp_model* m, const double* noise_var, const double* data_var, double jitter, int flags, const int32_t* fold, int64_t nfolds,
                   double* cv, double* mu, double* var, double* moments, double* diagG, double* trG, double* jitter_abs, int64_t* info) {
     if (!m) return fail(MOGP_EINVAL, "mogp_exact_cv: model is null");
     if (!fold || !cv || !mu || !var) return fail(MOGP_EINVAL, "mogp_exact_cv: fold, cv, mu or var is null");
-    const bool grad = (flags & MOGP_EVAL_GRAD) != 0;
-    if (grad && (!moments || !diagG || !trG)) return fail(MOGP_EINVAL, "mogp_exact_cv: gradient outputs are null");
-    int rc;
-    if ((rc = begin_call(m, info, true))) return rc;
-    auto again = [&]() { return mogp_exact_cv(m, noise_var, data_var, jitter, flags, fold, nfolds, cv, mu, var, moments, diagG, trG, jitter_abs, info); };
-    const int C = m->C, W = m->Wt, T = m->T, P = C * (C + 1) / 2;
-    const int64_t N = m->N, Npad = m->Npad;
-    // every allocation and the fold lists before the co-operating kernels are enqueued (see factorize); the pinned block as mogp_exact_loo lays it
-    // out, with the pivot word as it stands BEHIND the folds' factorisations at its end
-    if ((rc = ensure_system(m))) return rc;
-    if ((rc = cv_workspace(m, fold, nfolds, grad))) return rc;
-    const PinLayout pl(m);
-    const size_t pin_cv = pl.total, pin_mu = pin_cv + 1, pin_var = pin_mu + (size_t)Npad, pin_info = pin_var + (size_t)Npad;
-    if ((rc = pin_ensure(m, pin_info + 1))) return rc;
-    GramArgs ga{};
-    // the factorisation and inversion of a gradient evaluation, the COMPLETE inverse: the folds' points lie anywhere, and P E P reads every tile
-    if ((rc = enqueue_inverse(m, noise_var, data_var, jitter, true, /*banded=*/false, nullptr, jitter_abs, info, ga))) return retry_on_streams(m, rc, again);
-    double* v = m->loo.vec.p;
-    if ((rc = cv_points(m, m->k.B.p, grad))) return rc;
-    if (grad) {
-        m->have_W = false;                                    // S goes where the factorisation's own matrix was, as in mogp_exact_loo
-        if ((rc = cv_adjoint(m, m->k.B.p, m->k.A.p))) return rc;
-        if ((rc = loo_moment_pass(m))) return rc;
-        HIP_TRY(hipMemcpyAsync(m->h_pin + pl.moments, m->d_moments.p, (size_t)P * T * W * sizeof(double), hipMemcpyDeviceToHost, m->st));
-        HIP_TRY(hipMemcpyAsync(m->h_pin + pl.diagG, m->d_diagG.p, C * sizeof(double), hipMemcpyDeviceToHost, m->st));
-    }
-    HIP_TRY(hipMemcpyAsync(m->h_pin + pin_cv, v + LOO_SUM * Npad, sizeof(double), hipMemcpyDeviceToHost, m->st));
-    HIP_TRY(hipMemcpyAsync(m->h_pin + pin_mu, v + LOO_MU * Npad, N * sizeof(double), hipMemcpyDeviceToHost, m->st));
-    HIP_TRY(hipMemcpyAsync(m->h_pin + pin_var, v + LOO_VAR * Npad, N * sizeof(double), hipMemcpyDeviceToHost, m->st));
-    HIP_TRY(hipMemcpyAsync(m->h_pin + pin_info, m->d_info.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, m->st));
-    if ((rc = wait_stream(m->st))) return rc;
-    if ((rc = factorize_finish(m, ga, nullptr, info))) return retry_on_streams(m, rc, again);
-    if (grad) m->have_W = false;                              // (factorize_finish set it: k.A holds S now)
-    unsigned long long finfo = 0;
-    std::memcpy(&finfo, m->h_pin + pin_info, sizeof(finfo));
-    if (finfo != std::numeric_limits<unsigned long long>::max()) {          // Kj itself factored: a fold's block of its inverse did not
-        if (info) *info = (int64_t)(finfo - 1) / 256;
-        return fail(MOGP_ENOTPD, "mogp_exact_cv: the block of Kj^-1 over fold " + std::to_string((finfo - 1) / 256) + " is not positive definite (pivot " +
-                                 std::to_string((finfo - 1) % 256 + 1) + " of its factorisation): Kj is too ill-conditioned for this fold");
-    }
-    *cv = m->h_pin[pin_cv];
-    for (int64_t pos = 0; pos < N; ++pos)                     // a point in no fold has no prediction
-        if (m->cv.label[pos] < 0) m->h_pin[pin_mu + pos] = m->h_pin[pin_var + pos] = std::numeric_limits<double>::quiet_NaN();
-    scatter_by_perm(m->sx, m->h_pin + pin_mu, mu);
-    scatter_by_perm(m->sx, m->h_pin + pin_var, var);
-    m->have_Kinv = true;                                      // complete and mirrored: mogp_model_fetch(1) copies it as it is
-    m->kinv_in_A = false;
-    if (!grad) { collect_timing(m, 5); return MOGP_OK; }
-    std::memcpy(moments, m->h_pin + pl.moments, (size_t)P * T * W * sizeof(double));
-    std::memcpy(diagG, m->h_pin + pl.diagG, C * sizeof(double));
-    double tr = 0.0;
-    for (int c = 0; c < C; ++c) tr += diagG[c];
-    *trG = tr;
-    mean_grad_collect(m);
-    collect_timing(m, 6);
-    return MOGP_OK;
+    if ((flags & MOGP_EVAL_GRAD) && (!moments || !diagG || !trG)) return fail(MOGP_EINVAL, "mogp_exact_cv: gradient outputs are null");
+    return held_out_eval(m, noise_var, data_var, jitter, flags, fold, nfolds, cv, mu, var, moments, diagG, trG, jitter_abs, info);
 }
 
 int mogp_model_loo_bytes(mogp_model* m, int64_t* bytes) {

@@ -13,10 +13,11 @@
 //                  F_B = (W^T + c b_B u^T) / sqrt 2      (m x m, dense; F_B F_B^T = E_B exactly, SPD for every u: no pivot can fail)
 //                A non-positive pivot of P_BB goes to the evaluation's pivot word (atomicMin, as every factorisation here reports) and the fold
 //                goes on with a unit pivot: no NaN travels.
-//   the sum      loo.hip's one-workgroup fixed tree over the per-fold terms (launch_loo_sum): no atomics, the same bits every time
+//   the sum      loo.hip's one-workgroup fixed tree over the per-fold terms (held_out_points): no atomics, the same bits every time
 //   k_cv_cols    S[:, B] = P[:, B] F_B: one workgroup per (fold, 32 rows), the gathered columns staged in LDS, plain FMAs (DESIGN 1d has the
 //                measurement behind that choice); the other columns of S are zero-filled before it
-//   rho, -S S^T, the rank-two term, the moment pass: loo.hip's and linalg.hip's, unchanged
+//   the schedule around these two kernels -- the mirrored inverse, rho, -S S^T, the rank-two term, the moment pass -- is loo.hip's, written once for both
+//   scores (held_out_points, held_out_adjoint): this file supplies cv_folds and cv_fill_S to it
 #include "mogp_model.h"
 
 using namespace mogp;
@@ -207,16 +208,14 @@ size_t cv_bytes(const mogp_model* m) {
     return (w.off.n + w.idx.n) * sizeof(int) + w.foff.n * sizeof(long long) + w.fac.n * sizeof(double);
 }
 
-int cv_points(mogp_model* m, double* kinv, bool grad) {
+int cv_folds(mogp_model* m, const double* kinv, const double* y, bool grad) {
     CvWork& w = m->cv;
     w.timed = m->profiling && grad;
     if (w.timed) for (auto& e : w.ev) if (!e) HIP_TRY(hipEventCreate(&e));
     const int64_t Npad = m->Npad;
     double* v = m->loo.vec.p;
-    RC(launch_symmetrize(kinv, Npad, Npad, m->st));             // every tile of the inverse is read from here on, row by row
     // mu, var and b of points in no fold: zero on the device (b = 0 is the formula; the entry point makes mu and var NaN on the host)
     HIP_TRY(hipMemsetAsync(v, 0, (size_t)LOO_COUNT * Npad * sizeof(double), m->st));
-    const double* y = m->mean_on ? m->d_y0.p : m->d_y.p;        // the targets as the caller gave them (d_y: the residual under a mean table)
     const size_t lds = cv_lds_doubles(w.mmax) * sizeof(double);
     RC(set_max_dynamic_lds(reinterpret_cast<const void*>(k_cv_folds), (int)(cv_lds_doubles(MOGP_TILE) * sizeof(double)), folds_attr_done));
     if (w.timed) HIP_TRY(hipEventRecord(w.ev[0], m->st));
@@ -224,23 +223,18 @@ int cv_points(mogp_model* m, double* kinv, bool grad) {
                        grad ? 1 : 0, Npad, v, w.fac.p, m->d_info.p);
     HIP_TRY(hipGetLastError());
     if (w.timed) HIP_TRY(hipEventRecord(w.ev[1], m->st));
-    return launch_loo_sum(v + LOO_TERM * Npad, w.nfolds, v + LOO_SUM * Npad, m->st);
+    return 0;
 }
 
-int cv_adjoint(mogp_model* m, const double* kinv, double* scratch) {
+int cv_fill_S(mogp_model* m, const double* kinv, double* scratch) {
     const CvWork& w = m->cv;
-    const int64_t N = m->N, Npad = m->Npad;
-    double* v = m->loo.vec.p;
-    double* rho = v + LOO_RHO * Npad;
-    RC(launch_gemv_rows(kinv, Npad, Npad, Npad, v + LOO_B * Npad, rho, m->st));
+    const int64_t Npad = m->Npad;
     if (w.timed) HIP_TRY(hipEventRecord(w.ev[2], m->st));
     HIP_TRY(hipMemsetAsync(scratch, 0, (size_t)Npad * Npad * sizeof(double), m->st));      // the columns of points in no fold, and the padding
     hipLaunchKernelGGL(k_cv_cols, dim3((unsigned)w.nfolds, (unsigned)(Npad / CV_ROWS)), dim3(256), 0, m->st, kinv, scratch, Npad, w.off.p, w.idx.p, w.foff.p, w.fac.p);
     HIP_TRY(hipGetLastError());
     if (w.timed) HIP_TRY(hipEventRecord(w.ev[3], m->st));
-    GemmArgs g = make_gemm(scratch, Npad, 0, scratch, Npad, 0, m->loo.G.p, Npad, -1.0, GM_LOWER, m->nb, m->nb, Npad);
-    RC(gemm_call(m, g, gemm_flops(g, nullptr)));
-    return launch_loo_rank2(m->loo.G.p, Npad, N, m->d_alpha.p, rho, m->st);
+    return 0;
 }
 
 }  // namespace mogp

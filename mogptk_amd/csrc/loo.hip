@@ -14,6 +14,7 @@
 //                   symmetrised rank-two term entry by entry (the moment kernel's rider ru rw^T is ONE outer product: under the symmetric
 //                   double count it would give alpha rho^T alone, not its symmetric part)
 //   k_loo_diag      per-channel sums of the diagonal of G_loo
+// Leave-fold-out cross-validation (lfo.hip) is the same schedule with its own points kernel and its own S: held_out_points and held_out_adjoint carry both.
 #include "mogp_model.h"
 
 using namespace mogp;
@@ -87,39 +88,32 @@ int loo_workspace(mogp_model* m, bool grad) {
     return 0;
 }
 
-int loo_points(mogp_model* m, double* kinv) {
+// The points pass of both held-out scores: the inverse mirrored, the score's own kernel over the targets as the caller gave them -- per point here, per
+// fold in lfo.hip (cv_folds) -- and the fixed-order sum of its terms, one per point or one per fold
+int held_out_points(mogp_model* m, double* kinv, bool folds, bool grad) {
     const int64_t N = m->N, Npad = m->Npad;
     double* v = m->loo.vec.p;
     RC(launch_symmetrize(kinv, Npad, Npad, m->st));             // every tile of the inverse is read from here on, row by row
     const double* y = m->mean_on ? m->d_y0.p : m->d_y.p;        // the targets as the caller gave them (d_y: the residual under a mean table)
-    hipLaunchKernelGGL(k_loo_points, dim3((unsigned)((Npad + 255) / 256)), dim3(256), 0, m->st, kinv, Npad, m->d_alpha.p, y, N, Npad, v);
-    hipLaunchKernelGGL(k_loo_sum, dim3(1), dim3(256), 0, m->st, v + LOO_TERM * Npad, N, v + LOO_SUM * Npad);
+    if (folds) RC(cv_folds(m, kinv, y, grad));
+    else hipLaunchKernelGGL(k_loo_points, dim3((unsigned)((Npad + 255) / 256)), dim3(256), 0, m->st, kinv, Npad, m->d_alpha.p, y, N, Npad, v);
+    hipLaunchKernelGGL(k_loo_sum, dim3(1), dim3(256), 0, m->st, v + LOO_TERM * Npad, folds ? m->cv.nfolds : N, v + LOO_SUM * Npad);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-int loo_adjoint(mogp_model* m, const double* kinv, double* scratch) {
+// The adjoint of both held-out scores: rho = Kj^-1 b, S into scratch, -S S^T over the lower tiles into G, the symmetrised rank-two term.  Only S differs:
+// Kj^-1 diag(sqrt a) for leave-one-out, the folds' columns Kj^-1[:, B] F_B (lfo.hip: cv_fill_S) for leave-fold-out
+int held_out_adjoint(mogp_model* m, const double* kinv, double* scratch, bool folds) {
     const int64_t N = m->N, Npad = m->Npad;
     double* v = m->loo.vec.p;
     double* rho = v + LOO_RHO * Npad;
     RC(launch_gemv_rows(kinv, Npad, Npad, Npad, v + LOO_B * Npad, rho, m->st));
-    RC(launch_scale_cols(kinv, scratch, Npad, Npad, Npad, v + LOO_SA * Npad, m->st));
+    if (folds) RC(cv_fill_S(m, kinv, scratch));
+    else RC(launch_scale_cols(kinv, scratch, Npad, Npad, Npad, v + LOO_SA * Npad, m->st));
     GemmArgs g = make_gemm(scratch, Npad, 0, scratch, Npad, 0, m->loo.G.p, Npad, -1.0, GM_LOWER, m->nb, m->nb, Npad);
     RC(gemm_call(m, g, gemm_flops(g, nullptr)));
     hipLaunchKernelGGL(k_loo_rank2, dim3((unsigned)((N + 255) / 256), (unsigned)N), dim3(256), 0, m->st, m->loo.G.p, Npad, N, m->d_alpha.p, rho);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// k_loo_sum and k_loo_rank2 for the leave-fold-out evaluation (lfo.hip), which adds its per-fold terms and its rank-two term with the same kernels
-int launch_loo_sum(const double* term, int64_t n, double* out, hipStream_t st) {
-    hipLaunchKernelGGL(k_loo_sum, dim3(1), dim3(256), 0, st, term, n, out);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int launch_loo_rank2(double* G, int64_t ld, int64_t n, const double* alpha, const double* rho, hipStream_t st) {
-    hipLaunchKernelGGL(k_loo_rank2, dim3((unsigned)((n + 255) / 256), (unsigned)n), dim3(256), 0, st, G, ld, n, alpha, rho);
     HIP_TRY(hipGetLastError());
     return 0;
 }

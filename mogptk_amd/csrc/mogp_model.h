@@ -550,16 +550,15 @@ void collect_timing(mogp_model* m, int last_mark);
 // loo.hip -- the leave-one-out predictive likelihood on Kj^-1 (lower tiles in kinv, mirrored in place here) and alpha.  Vector slots of LooWork::vec, Npad each:
 enum { LOO_MU = 0, LOO_VAR, LOO_A, LOO_B, LOO_SA, LOO_TERM, LOO_RHO, LOO_SUM, LOO_COUNT };
 int loo_workspace(mogp_model* m, bool grad);                        // every allocation of a LOO evaluation (before the factorisation is enqueued)
-int loo_points(mogp_model* m, double* kinv);                        // mu, var, a, b, sqrt a, the N terms of L and their fixed-order sum (vec[LOO_SUM])
-int loo_adjoint(mogp_model* m, const double* kinv, double* scratch);  // rho = Kj^-1 b and G_loo (lower) into LooWork::G; scratch: N x N, overwritten
-int loo_moment_pass(mogp_model* m);                                 // moments of G_loo (every row kind), per-channel diagonal sums, dp/dr = -rho
-int launch_loo_sum(const double* term, int64_t n, double* out, hipStream_t st);       // out[0] = sum of n terms: one workgroup, fixed order
-int launch_loo_rank2(double* G, int64_t ld, int64_t n, const double* alpha, const double* rho, hipStream_t st);   // G (lower) += 1/2 (alpha rho^T + rho alpha^T)
+// The schedule of both held-out scores (folds: leave-fold-out, which must have had its cv_workspace), around the score's own kernels:
+int held_out_points(mogp_model* m, double* kinv, bool folds, bool grad);   // inverse mirrored; mu, var, b and the terms of L per point (with a, sqrt a) or per fold (cv_folds); their fixed-order sum (vec[LOO_SUM])
+int held_out_adjoint(mogp_model* m, const double* kinv, double* scratch, bool folds);   // rho = Kj^-1 b; S into scratch (N x N, overwritten: scaled columns, or cv_fill_S); G = -S S^T + 1/2 (alpha rho^T + rho alpha^T) (lower) into LooWork::G
+int loo_moment_pass(mogp_model* m);                                 // moments of that G (every row kind), per-channel diagonal sums, dp/dr = -rho
 // lfo.hip -- leave-fold-out cross-validation on the same inverse.  It uses LooWork's vectors (LOO_MU, LOO_VAR, LOO_B, LOO_RHO, LOO_SUM; LOO_TERM
 // holds one term per FOLD) and its N x N adjoint, and keeps the fold lists and the packed per-fold factors in CvWork.
 int cv_workspace(mogp_model* m, const int32_t* fold, int64_t nfolds, bool grad);   // labels through the channel sort, validated; every allocation and upload (before the factorisation is enqueued)
-int cv_points(mogp_model* m, double* kinv, bool grad);              // per fold: mu, diag Sigma, b, the term of L, with grad the factor F_B; then the fixed-order sum (vec[LOO_SUM])
-int cv_adjoint(mogp_model* m, const double* kinv, double* scratch);   // rho = Kj^-1 b and G_cv (lower) into LooWork::G; scratch: N x N, overwritten with S
+int cv_folds(mogp_model* m, const double* kinv, const double* y, bool grad);   // vec zeroed, then per fold: mu, diag Sigma, b, the term of L, with grad the factor F_B (events 0, 1 around the kernel)
+int cv_fill_S(mogp_model* m, const double* kinv, double* scratch);    // S = 0, then S[:, B] = Kj^-1[:, B] F_B fold by fold (events 2, 3 around both)
 size_t cv_bytes(const mogp_model* m);                               // device memory of CvWork
 int eval_sweep(mogp_model* m, const double* noise_var, const double* data_var, double jitter, double* lml, double* jitter_abs, int64_t* info);   // shard.hip
 void one_gpu_call(mogp_model* m);   // ownership state of a previous sharded evaluation off (every one-GPU entry point calls this first)
