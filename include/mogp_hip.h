@@ -495,6 +495,44 @@ int  mogp_mosm_terms_backward(int C, int Q, int D, const double* w, const double
                               double twopi, double phase_scale, const double* gtable, double* gw, double* gmu, double* gv, double* gth,
                               double* gph);
 
+/* ---- the host side of one exact-GP training step of the plain MOSM kernel (csrc/hoststep.hip, csrc/step.hip) ----------------------- */
+/* All vectors are FLAT over [ weight C Q | mean C Q D | variance C Q D | delay C Q D | phase C Q | noise scale nscale ], nscale = C (one
+ * scale per channel) or 1 (one shared scale).  Per element: tkind (below), lower, upper, beta, threshold -- the fields of the parameter's
+ * transform (reference gpr/parameter.py:30-59 Softplus, :61-96 Sigmoid; an untransformed element reads none of them).
+ * mogp_mosm_step_forward (replaces Parameter.constrained, gpr/parameter.py:186-201, for every parameter of the step, the table algebra of
+ * gpr/multioutput.py:178-204 and the noise of gpr/model.py:183-186): raw -> cons (the constrained values), dcons = d cons / d raw (what
+ * autograd takes through the transform), table [C][C][Q][2+3D] (mogp_mosm_terms) and noise_var[C] = scale^2.  Same operation order as the
+ * Python mirror.  lp[k] = log1p(exp(beta x)) and en[k] = exp(-beta x) (softplus; sigmoid: en[k] = exp(-x); read only where the element's branch
+ * needs them) let the caller supply the transcendental values, so that they are the mirror's own to the last bit -- the Python package always
+ * does; both NULL: libm's, up to 2 - 4 ulp from numpy's (a C caller without numpy, the stand-alone host check).  These three host-only entry
+ * points and mogp_adam_step return MOGP_EINVAL without setting mogp_last_error. */
+#define MOGP_TRANSFORM_IDENTITY 0
+#define MOGP_TRANSFORM_SOFTPLUS 1      /* lower + log1p(exp(beta x)) / beta;  lower + x where beta x > threshold */
+#define MOGP_TRANSFORM_SIGMOID  2      /* lower + (upper - lower) / (1 + exp(-x)) */
+int  mogp_mosm_step_forward(int C, int Q, int D, int nscale, const double* raw, const int* tkind, const double* lower, const double* upper,
+                            const double* beta, const double* threshold, const double* lp, const double* en, double twopi, double phase_scale,
+                            double* cons, double* dcons, double* table, double* noise_var);
+/* mogp_mosm_step_backward (replaces the autograd backward of Model.loss, gpr/model.py:279-292, from the kernel matrix down to the raw
+ * parameters): the outputs of mogp_exact_eval(MOGP_EVAL_GRAD) -- moments, diagG, trG -- with the relative jitter, the training points per
+ * channel counts[C] and N -> graw = d (-LML) / d raw.  trained[6]: one flag per block of the flat vector; the entries of a block whose
+ * flag is 0 are left as they are (a block that is not in the reference's graph: delay and phase with one channel). */
+int  mogp_mosm_step_backward(int C, int Q, int D, int nscale, const double* cons, const double* dcons, const double* table, const double* moments,
+                             const double* diagG, double trG, double jitter, const double* counts, int64_t N, double twopi, double phase_scale,
+                             const int* trained, double* graw);
+/* One training step's evaluation behind one call (replaces Model.loss, gpr/model.py:279-292, for gpr.Exact with the plain MOSM kernel):
+ * mogp_mosm_step_forward, mogp_model_set_terms, mogp_exact_eval(MOGP_EVAL_GRAD) -- unchanged, the same launches in the same order --,
+ * mogp_mosm_step_backward.  cons, dcons, table, noise_var, moments, diagG are the caller's buffers and hold those stages' results
+ * afterwards; out5 = [ LML, trG, jitter_abs, lmin, lmax ] (the last two: mogp_model_pivot_range); *info as for mogp_exact_eval. */
+int  mogp_exact_step(mogp_model* m, int C, int Q, int D, int nscale, const double* raw, const int* tkind, const double* lower, const double* upper,
+                     const double* beta, const double* threshold, const double* lp, const double* en, double twopi, double phase_scale,
+                     const double* data_var, double jitter, const double* counts, const int* trained, double* cons, double* dcons, double* table, double* noise_var, double* moments,
+                     double* diagG, double* out5, double* graw, int64_t* info);
+/* One Adam update of a flat float64 vector (replaces torch.optim.Adam.step as the reference's training loop calls it, mogptk/model.py:557-566):
+ * `nseg` tensors end to end, ends[s] one past the last element of tensor s, bc1[s] = 1 - beta1^t and bc2[s] = 1 - beta2^t for tensor s's own
+ * step count t (formed by the caller).  x, m, v and -- with amsgrad -- vmax are updated in place; weight_decay adds weight_decay * x to g. */
+int  mogp_adam_step(int nseg, const int64_t* ends, double* x, const double* g, double* m, double* v, double* vmax, double lr, double beta1,
+                    double beta2, double eps, double weight_decay, int amsgrad, const double* bc1, const double* bc2);
+
 #ifdef __cplusplus
 }
 #endif

@@ -122,6 +122,13 @@ SIGNATURES = {
     "mogp_mosm_terms": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_dp, c_dp, c_dp, c_dp, c_dp, ctypes.c_double, ctypes.c_double, c_dp]),
     "mogp_mosm_terms_backward": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_dp, c_dp, c_dp, c_dp, c_dp, ctypes.c_double,
                                                 ctypes.c_double, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "mogp_mosm_step_forward": (ctypes.c_int, [ctypes.c_int] * 4 + [c_dp, c_ip, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, ctypes.c_double, ctypes.c_double,
+                                              c_dp, c_dp, c_dp, c_dp]),
+    "mogp_mosm_step_backward": (ctypes.c_int, [ctypes.c_int] * 4 + [c_dp] * 5 + [ctypes.c_double, ctypes.c_double, c_dp, ctypes.c_int64,
+                                                                               ctypes.c_double, ctypes.c_double, c_ip, c_dp]),
+    "mogp_exact_step": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4 + [c_dp, c_ip, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, ctypes.c_double, ctypes.c_double,
+                                                                               c_dp, ctypes.c_double, c_dp, c_ip] + [c_dp] * 8 + [c_i64p]),
+    "mogp_adam_step": (ctypes.c_int, [ctypes.c_int, c_i64p] + [c_dp] * 5 + [ctypes.c_double] * 5 + [ctypes.c_int, c_dp, c_dp]),
 }
 
 
@@ -235,6 +242,131 @@ def shutdown():
 atexit.register(shutdown)
 
 
+TRANSFORM_IDENTITY, TRANSFORM_SOFTPLUS, TRANSFORM_SIGMOID = 0, 1, 2
+
+
+def _check_host(code, name):
+    """the host-only entry points (csrc/hoststep.hip, csrc/hostalg.hip) return a code and leave mogp_last_error alone: the message is made here"""
+    if code != MOGP_OK:
+        raise MogpError(code, "%s failed (%d): a bad argument -- shape, transform kind or null pointer" % (name, code))
+
+
+class StepPlan:
+    """Buffers and ready-made arguments of the native MOSM training step (csrc/hoststep.hip, csrc/step.hip) for one model structure.  Everything
+    is flat over [weight C Q | mean C Q D | variance C Q D | delay C Q D | phase C Q | noise scale nscale].  `transforms`: one
+    (kind, lower, upper, beta, threshold) per block, lower / upper scalars or arrays of the block's shape; `trained`: one flag per block.
+    The plan holds ctypes pointers into its own arrays, so it lives on a device handle (or in a test), never on a model, kernel or
+    parameter: those are pickled and deep-copied."""
+
+    def __init__(self, C, Q, D, nscale, transforms, twopi, phase_scale, counts, N, trained):
+        self.C, self.Q, self.D, self.nscale, self.N = int(C), int(Q), int(D), int(nscale), int(N)
+        sizes = [C * Q, C * Q * D, C * Q * D, C * Q * D, C * Q, nscale]
+        self.ends = np.cumsum(sizes)
+        self.starts = self.ends - sizes
+        self._cuts = [0] + [int(e) for e in self.ends]
+        self._trained = [bool(t) for t in trained]
+        self.params = ()
+        n = int(self.ends[-1])
+        W = 2 + 3 * D
+        self.tkind = np.zeros(n, dtype=np.int32)
+        self.lower, self.upper, self.beta, self.threshold = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n)
+        for (kind, lo, up, beta, thr), a, b in zip(transforms, self.starts, self.ends):
+            self.tkind[a:b] = kind
+            for dst, val in ((self.lower, lo), (self.upper, up), (self.beta, beta), (self.threshold, thr)):
+                dst[a:b] = 0.0 if val is None else np.asarray(val, dtype=np.float64).reshape(-1)       # one value, or one per element
+        self.trained = np.ascontiguousarray(trained, dtype=np.int32)
+        self.counts = _f64(counts)
+        assert self.trained.shape == (6,) and self.counts.shape == (C,)
+        self.raw, self.cons, self.dcons, self.graw = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n)
+        # exp and log1p stay numpy's, so that the constrained values are the numpy form's to the last bit: z = beta x (x itself under a sigmoid),
+        # en = exp(-z), lp = log1p(exp(z)) with z capped at the softplus threshold (beyond it the native code takes the linear branch and reads neither)
+        self._scale = np.where(self.tkind == TRANSFORM_SOFTPLUS, self.beta, np.where(self.tkind == TRANSFORM_SIGMOID, 1.0, 0.0))
+        self._cap = np.where(self.tkind == TRANSFORM_SOFTPLUS, self.threshold, np.inf)
+        self._z, self.lp, self.en = np.zeros(n), np.zeros(n), np.zeros(n)
+        self.table = np.zeros((C, C, Q, W))
+        self.noise_var = np.zeros(C)
+        self.moments = np.zeros((C * (C + 1) // 2, Q, W))
+        self.diagG = np.zeros(C)
+        self.out = np.zeros(5)                      # LML, trG, jitter_abs, smallest and largest pivot
+        self.info = ctypes.c_int64(0)
+        self.twopi, self.phase_scale = float(twopi), float(phase_scale)
+        shape = (self.C, self.Q, self.D, self.nscale)
+        self._fwd = shape + (_dp(self.raw), _ip(self.tkind), _dp(self.lower), _dp(self.upper), _dp(self.beta), _dp(self.threshold), _dp(self.lp), _dp(self.en),
+                             self.twopi, self.phase_scale, _dp(self.cons), _dp(self.dcons), _dp(self.table), _dp(self.noise_var))
+        self._bwd_head = shape + (_dp(self.cons), _dp(self.dcons), _dp(self.table), _dp(self.moments), _dp(self.diagG))
+        self._bwd_tail = (_dp(self.counts), self.N, self.twopi, self.phase_scale, _ip(self.trained), _dp(self.graw))
+        self._step_args = None
+
+    def gather(self, tensors):
+        """the raw tensors (one per block) into the flat buffer"""
+        np.concatenate([t.reshape(-1) for t in tensors], out=self.raw)
+        self.transcendentals()
+
+    def transcendentals(self):
+        """lp and en of the raw values in the buffer, by numpy"""
+        z, lp, en = self._z, self.lp, self.en
+        with np.errstate(over="ignore", invalid="ignore"):
+            np.multiply(self._scale, self.raw, out=z)
+            np.negative(z, out=en)
+            np.exp(en, out=en)
+            np.minimum(z, self._cap, out=z)
+            np.exp(z, out=lp)
+            np.log1p(lp, out=lp)
+
+    def block(self, flat, i, shape):
+        return flat[self._cuts[i]:self._cuts[i + 1]].reshape(shape)
+
+    def scatter_grad(self):
+        """`.grad` of the plan's parameters (`params`, set by the owner) from a fresh copy of graw: arrays of every parameter's own shape,
+        None for a block that is not trained.  The arrays are disjoint views of that ONE fresh vector (they share `.base`), not arrays that
+        each own their memory as the numpy form's do"""
+        g = self.graw.copy()
+        cuts = self._cuts
+        for i, p in enumerate(self.params):
+            p.grad = g[cuts[i]:cuts[i + 1]].reshape(p.data.shape) if self._trained[i] else None
+
+    def forward(self):
+        """raw -> cons, dcons, table, noise_var (mogp_mosm_step_forward)"""
+        _check_host(lib().mogp_mosm_step_forward(*self._fwd), "mogp_mosm_step_forward")
+
+    def backward(self, trG, jitter):
+        """cons, dcons, table, moments, diagG -> graw (mogp_mosm_step_backward)"""
+        _check_host(lib().mogp_mosm_step_backward(*self._bwd_head, float(trG), float(jitter), *self._bwd_tail), "mogp_mosm_step_backward")
+
+    def step_args(self, jitter, data_var):
+        """what mogp_exact_step takes behind the model handle (kept until the jitter or the data variance array changes)"""
+        c = self._step_args
+        if c is None or c[0] != jitter or c[1] is not data_var:
+            dv = _f64(data_var)
+            c = self._step_args = (jitter, data_var, dv, self._fwd[:14] + (_dp(dv), float(jitter), _dp(self.counts), _ip(self.trained)) + self._fwd[14:] +
+                                   (_dp(self.moments), _dp(self.diagG), _dp(self.out), _dp(self.graw), ctypes.byref(self.info)))
+        return c[3]
+
+    def condition_estimate(self):
+        """as ExactHandle.condition_estimate, from the pivots the last step returned"""
+        lo, hi = self.out[3], self.out[4]
+        return float((hi / lo) ** 2) if lo > 0.0 else float("nan")
+
+
+class AdamPlan:
+    """Buffers and ready-made arguments of mogp_adam_step for one flat group of tensors (ends[s]: one past tensor s).  m, v, vmax are the
+    optimiser's flat state and are updated in place; the caller gathers the raw values into x and the gradients into g, sets the bias
+    corrections bc1 / bc2 (one per tensor) and reads the new values from x."""
+
+    def __init__(self, ends, m, v, vmax):
+        self.ends = np.ascontiguousarray(ends, dtype=np.int64)
+        n, k = int(self.ends[-1]), self.ends.shape[0]
+        for a in (m, v, vmax):
+            assert a.dtype == np.float64 and a.flags.c_contiguous and a.shape == (n,)
+        self.m, self.v, self.vmax = m, v, vmax
+        self.x, self.g, self.bc1, self.bc2 = np.empty(n), np.empty(n), np.empty(k), np.empty(k)
+        self._head = (k, self.ends.ctypes.data_as(c_i64p), _dp(self.x), _dp(self.g), _dp(m), _dp(v), _dp(vmax))
+        self._tail = (_dp(self.bc1), _dp(self.bc2))
+
+    def step(self, lr, beta1, beta2, eps, weight_decay, amsgrad):
+        _check_host(lib().mogp_adam_step(*self._head, lr, beta1, beta2, eps, weight_decay, 1 if amsgrad else 0, *self._tail), "mogp_adam_step")
+
+
 class ExactHandle:
     """Owner of one mogp_model (device workspaces for a fixed training set)."""
 
@@ -320,6 +452,14 @@ class ExactHandle:
                                      ctypes.byref(trG), ctypes.byref(jit), ctypes.byref(info))
         check(code, info.value)
         return dict(lml=lml.value, moments=moments, diagG=diagG, trG=trG.value, jitter_abs=jit.value)
+
+    def step(self, plan, jitter, data_var=None):
+        """one training step's evaluation of a plain MOSM model in one native call (mogp_exact_step): plan.raw -> plan.out (LML, trG,
+        jitter_abs, pivots) and plan.graw; the table, moments and diagG of the step stay in the plan's buffers"""
+        assert plan.C == self.C and plan.D == self.D and plan.N == self.N
+        self.T, self.W = plan.Q, 2 + 3 * plan.D
+        code = lib().mogp_exact_step(self._h, *plan.step_args(jitter, data_var))
+        check(code, plan.info.value)
 
     def _grad_outputs(self, grad=True):
         """(moments[P,T,W], diagG[C]) for an entry point to fill; (None, None) without gradients"""

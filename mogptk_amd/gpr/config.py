@@ -7,6 +7,8 @@ device arithmetic itself is fp64 in both cases (the fp64 MFMA path is the produc
 honoured at the boundary -- float32-rounded inputs and parameters go in, float32 results come out -- which is at least as accurate as
 the reference's float32 run.  `config.device` is the HIP device ordinal the C-ABI contexts bind to.
 """
+from os import environ as _environ
+
 import numpy as np
 
 
@@ -16,6 +18,7 @@ class Config:
     positive_minimum = 1e-8
     comm = None          # mogptk_amd.dist.Comm when exact evaluations are sharded over several GPUs
     accurate_fallback = True      # gpr.Exact repeats a gradient evaluation in the backward-stable form when the factor's diagonal says K + noise is ill-conditioned
+    host_fast = _environ.get("MOGP_HOST_FAST", "1") != "0"      # gpr.Exact.loss() of a plain MOSM model and the Adam update run their host algebra in native code (MOGP_HOST_FAST=0: the numpy form)
 
 
 config = Config()

@@ -9,10 +9,11 @@ from contextlib import contextmanager
 from math import erf, sqrt
 
 from .config import config
-from .parameter import Parameter, ParameterHolder
+from .parameter import Parameter, ParameterHolder, Softplus, Sigmoid, _STRUCTURE_EPOCH
 from .kernel import Kernel, MulKernel, ChangePointsKernel, terms_cache, KIND_TIMES, KIND_MASK, KIND_DOT, KIND_GATE, KIND_WDOT, group_diag_grad
 from .likelihood import Likelihood, GaussianLikelihood
 from .mean import Mean
+from .multioutput import MultiOutputSpectralMixtureKernel
 
 
 class CholeskyException(Exception):
@@ -54,6 +55,17 @@ def _channel_counts(Xk, C):
 def _lml_constant(X):
     """N/2 log 2 pi, the attribute the reference's models carry (gpr/model.py:436)"""
     return 0.5 * X.shape[0] * np.log(2.0 * np.pi)
+
+
+_F64 = np.dtype(np.float64)
+_STEP_KINDS = {type(None): 0, Softplus: 1, Sigmoid: 2}        # the transform kinds of the native step (include/mogp_hip.h MOGP_TRANSFORM_*)
+
+
+def _step_signature(p):
+    """what the native step's plan describes of one parameter: its transform's class, the transform and its fields, the shape.  The objects
+    themselves are kept, so `is` decides: a bound changes through Parameter.assign, which makes a new transform"""
+    t = p.transform
+    return (type(t), t, getattr(t, "lower", None), getattr(t, "upper", None), getattr(t, "beta", None), getattr(t, "threshold", None), p.data.shape)
 
 
 _PAIR_INDEX = {}
@@ -548,14 +560,15 @@ class Exact(Model):
     CONDITION_WARN = 1e5       # on the pivot-spread estimate (max L_jj / min L_jj)^2, a LOWER bound of cond(Kj) -- 9e5 where cond is 7e7, 9e3 where it is 8e5;
                                # DESIGN 7 puts the envelope of the fast schedules at cond ~ 1e6 - 1e7
 
-    def _check_conditioning(self, h, redo):
+    def _check_conditioning(self, h, redo, est=None):
         """The reference's torch.linalg.cholesky is backward stable and silent; the fast schedules of this path form their panels with explicit block
         inverses and lose accuracy as K + noise becomes ill-conditioned.  The factor's own diagonal says when: the model then says so
         (once), repeats the evaluation in the backward-stable form (mogp_model_set_accurate; 25 ms against 10 at N = 8192) and stays there until the matrix is
         well-conditioned again.  `config.accurate_fallback = False` keeps the fast form and only warns."""
-        if not hasattr(h, "condition_estimate"):
-            return None
-        est = h.condition_estimate()
+        if est is None:                                     # (the native step hands over the estimate it read with the evaluation)
+            if not hasattr(h, "condition_estimate"):
+                return None
+            est = h.condition_estimate()
         if est != est:
             return None
         accurate = getattr(h, "accurate_mode", False)       # the mode lives in the device handle, so the flag lives ON the handle: a model that is copied,
@@ -583,11 +596,81 @@ class Exact(Model):
         res, _, _ = self._eval(grad=False)
         return config.dtype(res["lml"])
 
+    # -- the native host side of a plain MOSM training step (csrc/hoststep.hip, csrc/step.hip) -----------------------------------
+    def _step_plan(self, score):
+        """the native step's plan (_lib.StepPlan) when this evaluation can take it, else None.  It takes the marginal likelihood of the plain MOSM
+        kernel in float64 under a Gaussian likelihood with no mean function, no prior, no pegged parameter and no communicator, on a handle
+        that has the native step; everything else goes the general way.  The plan lives on the device handle (which is never pickled or
+        copied) and is rebuilt when what it describes changes: the parameters, their transforms and bounds, their shapes, X."""
+        k = self.kernel
+        if (score != "lml" or not getattr(config, "host_fast", True) or config.dtype != np.float64 or getattr(config, "comm", None) is not None
+                or type(k) is not MultiOutputSpectralMixtureKernel or self.mean is not None or type(self.likelihood) is not GaussianLikelihood):
+            return None
+        h = self._device_handle()
+        plan = getattr(h, "_step_plan", None)
+        if plan is not None and plan.kernel is k and plan.likelihood is self.likelihood and plan.X is self.X and plan.epoch == _STRUCTURE_EPOCH[0]:
+            for p, s in zip(plan.params, plan.sigs):
+                t = p.transform
+                if (t is not s[1] or p.pegged_parameter is not None or p.prior is not None or p.data.shape != s[6] or (p.data.dtype is not _F64 and p.data.dtype != _F64)
+                        or (t is not None and (t.lower is not s[2] or getattr(t, "upper", None) is not s[3] or getattr(t, "beta", None) != s[4]
+                                               or getattr(t, "threshold", None) != s[5]))):
+                    break
+            else:
+                return plan
+        return self._new_step_plan(h)
+
+    def _new_step_plan(self, h):
+        """check everything the native step assumes, and build its plan on the handle (None: this model goes the general way)"""
+        k = self.kernel
+        if not hasattr(h, "step") or getattr(h, "radial_kinds", False) or getattr(h, "point_diag_set", False):
+            return None
+        blocks, trained = k._step_blocks()
+        params = blocks + (self.likelihood.scale,)
+        epoch = _STRUCTURE_EPOCH[0]
+        plist = self._parameter_list()
+        if len(plist) != len(params):
+            return None
+        for p, q in zip(plist, params):
+            if p is not q or p.pegged_parameter is not None or p.prior is not None or p.data.dtype != np.float64:
+                return None
+        sigs = [_step_signature(p) for p in params]
+        C, D, Q = k.output_dims, k.input_dims, k.weight.shape[1]
+        scale = params[5]
+        shapes = [(C, Q), (C, Q, D), (C, Q, D), (C, Q, D), (C, Q), scale.shape]
+        if D != self._D or scale.shape not in ((), (C,)) or any(s[6] != shape for s, shape in zip(sigs, shapes)) or any(s[0] not in _STEP_KINDS for s in sigs):
+            return None
+        from .._lib import StepPlan
+        plan = StepPlan(C, Q, D, scale.data.size, [(_STEP_KINDS[s[0]],) + s[2:6] for s in sigs], k.twopi, k._phase_scale, self._train_counts(),
+                        self.X.shape[0], trained + (True,))
+        plan.params, plan.sigs, plan.X, plan.kernel, plan.likelihood, plan.epoch = params, sigs, self.X, k, self.likelihood, epoch
+        h._step_plan = plan
+        h.radial_kinds, h.group_kinds, h.point_kinds = False, None, None       # what _push_terms notes on the handle for an all-Gaussian table
+        return plan
+
+    def _loss_native(self, plan):
+        """`_loss_impl` for the marginal likelihood through the native step: one gather, one native call (raw parameters -> table -> device
+        evaluation -> raw gradient), one scatter.  `.grad` are fresh arrays of every parameter's own shape, None where the general way leaves
+        None; they are disjoint views of one vector made for this step, so `p.grad.base` is shared between the parameters (the general way gives
+        each an array of its own) -- writing into one never reaches another.  (No parameter has a prior here, so the loss is -LML.)"""
+        h = self._handle
+        for p in plan.params:                       # zero_grad(set_to_none=True): an evaluation that raises leaves no stale gradient
+            p.grad = None
+        plan.gather([p.data for p in plan.params])
+        run = lambda: h.step(plan, self.jitter, self.data_variance)
+        with self._cholesky_guard():
+            run()
+            self._check_conditioning(h, run, plan.condition_estimate())
+        plan.scatter_grad()
+        return config.dtype(-plan.out[0])
+
     def _loss_impl(self, score="lml", folds=None):
         """reference gpr/model.py:279-292: zero grads, loss = -LML - log prior, fresh `.grad` on every
         parameter in the graph.  Gradients come from the device's moment pass + the host chain rule.
         score "loo" / "cv": the leave-one-out / leave-fold-out likelihood L in the LML's place -- the device returns the moments, diagonal sums
         and trace of dL/dKj in the same layout, so the chain rule below is the same."""
+        plan = self._step_plan(score)
+        if plan is not None:
+            return self._loss_native(plan)
         self.zero_grad(set_to_none=True)
         res, table, D = self._eval(grad=True, score=score, folds=folds)
         counts = self._train_counts()

@@ -136,6 +136,12 @@ class MultiOutputSpectralMixtureKernel(MultiOutputKernel):
             _accumulate(self.delay, gth)
             _accumulate(self.phase, gph)
 
+    def _step_blocks(self):
+        """what the native training step (csrc/hoststep.hip; gpr.Exact takes it for the plain MOSM kernel only) needs of this kernel: its
+        parameters in the order of the step's flat vector, and which of them enter the graph (`_store`: not delay and phase with one channel)"""
+        multi = self.output_dims > 1
+        return (self.weight, self.mean, self.variance, self.delay, self.phase), (True, True, True, multi, multi)
+
     def _memo_key(self):
         parts = []
         for p in (self.weight, self.mean, self.variance, self.delay, self.phase):

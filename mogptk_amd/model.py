@@ -153,6 +153,9 @@ class Hensman:
 
 
 # ---- optimisers over raw parameters (torch.optim semantics) -----------------------------------------
+_F64 = np.dtype(np.float64)
+
+
 class _Adam:
     """torch.optim.Adam(params, lr=1e-3, betas=(0.9,0.999), eps=1e-8, weight_decay=0, amsgrad=False)"""
 
@@ -160,13 +163,15 @@ class _Adam:
         self.params = list(params)
         self.lr, self.betas, self.eps, self.wd, self.amsgrad = lr, betas, eps, weight_decay, amsgrad
         self.state = {}
+        self._native = None           # _lib.AdamPlan of the flat state (buffers and pointers: kept out of `state`)
 
     def step(self):
         """One Adam update (torch.optim.Adam's arithmetic, element for element).  The raw parameters of a model are a handful of tiny tensors
         (64 numbers at configs[1]): updated tensor by tensor, the ~10 small numpy calls per tensor were a third of the host's share of a training
         step, so the float64 tensors that have a gradient are updated as ONE flat vector -- the same elementwise operations in the same order."""
         b1, b2 = self.betas
-        flat = [p for p in self.params if p.grad is not None and p.data.dtype == np.float64 and p.grad.dtype == np.float64]
+        f64 = _F64           # (the dtype object itself first: `==` between a dtype and a type is a slow comparison, and this runs twice per tensor and step)
+        flat = [p for p in self.params if p.grad is not None and (p.data.dtype is f64 or p.data.dtype == f64) and (p.grad.dtype is f64 or p.grad.dtype == f64)]
         if len(flat) > 1:
             key = tuple(id(p) for p in flat)
             st = self.state.get("flat")
@@ -179,27 +184,45 @@ class _Adam:
                           v=np.concatenate([q["v"].ravel() for q in parts]), vmax=np.concatenate([q["vmax"].ravel() for q in parts]),
                           ends=np.cumsum([p.data.size for p in flat]))
                 self.state["flat"] = st
-            g = np.concatenate([p.grad.ravel() for p in flat])
-            x = np.concatenate([p.data.ravel() for p in flat])
-            if self.wd != 0.0:
-                g = g + self.wd * x
-            st["t"] = [t + 1 for t in st["t"]]
-            st["m"] = b1 * st["m"] + (1.0 - b1) * g
-            st["v"] = b2 * st["v"] + (1.0 - b2) * g * g
-            v = st["v"]
-            if self.amsgrad:
-                st["vmax"] = np.maximum(st["vmax"], v)
-                v = st["vmax"]
-            if len(set(st["t"])) == 1:
-                bc1, bc2 = 1.0 - b1 ** st["t"][0], 1.0 - b2 ** st["t"][0]
-                x = x - (self.lr / bc1) * st["m"] / (np.sqrt(v) / math.sqrt(bc2) + self.eps)
-            else:                                           # tensors that joined later carry their own step counts
-                sizes = np.diff(np.concatenate([[0], st["ends"]]))
-                bc1 = np.repeat([1.0 - b1 ** t for t in st["t"]], sizes)
-                bc2 = np.repeat([1.0 - b2 ** t for t in st["t"]], sizes)
-                x = x - (self.lr / bc1) * st["m"] / (np.sqrt(v) / np.sqrt(bc2) + self.eps)
+            st["t"] = ts = [t + 1 for t in st["t"]]
+            if gpr.config.host_fast:
+                # the same arithmetic in one native call (csrc/hoststep.hip mogp_adam_step), in place on the flat state; the bias corrections
+                # are formed here, per tensor, so that no pow differs
+                plan = self._native
+                if plan is None or plan.m is not st["m"] or plan.v is not st["v"] or plan.vmax is not st["vmax"]:
+                    from . import _lib
+                    plan = self._native = _lib.AdamPlan(st["ends"], st["m"], st["v"], st["vmax"])
+                np.concatenate([p.grad.ravel() for p in flat], out=plan.g)
+                np.concatenate([p.data.ravel() for p in flat], out=plan.x)
+                if ts.count(ts[0]) == len(ts):
+                    plan.bc1.fill(1.0 - b1 ** ts[0])
+                    plan.bc2.fill(1.0 - b2 ** ts[0])
+                else:                                           # tensors that joined later carry their own step counts
+                    plan.bc1[:] = [1.0 - b1 ** t for t in ts]
+                    plan.bc2[:] = [1.0 - b2 ** t for t in ts]
+                plan.step(self.lr, b1, b2, self.eps, self.wd, self.amsgrad)
+                x = plan.x.copy()                               # the tensors' new .data are views of a fresh vector, as below
+            else:
+                g = np.concatenate([p.grad.ravel() for p in flat])
+                x = np.concatenate([p.data.ravel() for p in flat])
+                if self.wd != 0.0:
+                    g = g + self.wd * x
+                st["m"] = b1 * st["m"] + (1.0 - b1) * g
+                st["v"] = b2 * st["v"] + (1.0 - b2) * g * g
+                v = st["v"]
+                if self.amsgrad:
+                    st["vmax"] = np.maximum(st["vmax"], v)
+                    v = st["vmax"]
+                if len(set(st["t"])) == 1:
+                    bc1, bc2 = 1.0 - b1 ** st["t"][0], 1.0 - b2 ** st["t"][0]
+                    x = x - (self.lr / bc1) * st["m"] / (np.sqrt(v) / math.sqrt(bc2) + self.eps)
+                else:                                           # tensors that joined later carry their own step counts
+                    sizes = np.diff(np.concatenate([[0], st["ends"]]))
+                    bc1 = np.repeat([1.0 - b1 ** t for t in st["t"]], sizes)
+                    bc2 = np.repeat([1.0 - b2 ** t for t in st["t"]], sizes)
+                    x = x - (self.lr / bc1) * st["m"] / (np.sqrt(v) / np.sqrt(bc2) + self.eps)
             lo = 0
-            for p, hi in zip(flat, st["ends"]):
+            for p, hi in zip(flat, st["ends"].tolist()):
                 p.data = x[lo:hi].reshape(p.data.shape)
                 lo = hi
             done = set(key)
