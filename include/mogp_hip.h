@@ -234,6 +234,22 @@ int  mogp_exact_predict(mogp_model* m, const double* noise_var, const double* da
                         const double* kss_diag, int64_t S, const double* Xs, int full,
                         double* mu, double* var, int64_t* info);
 
+/* The posterior of every ADDEND of the model's covariance, K = sum_p K_p, at the test points (no reference seam: mogptk has no such call -- the
+ * formulas are the standard additive decomposition of a Gaussian process posterior, Duvenaud et al. 2011 / Rasmussen & Williams 2.7 applied to
+ * one addend; checked against the reference's own kernel objects, one per part, in tests/golden/gen_parts.py):
+ *   mu_p = K_p(Xs, X) Kj^-1 r,     var_p = kss_diag_p - colsum((L^-1 K_p(X, Xs))^2)     (full != 0: K_p(Xs, Xs) - V_p^T V_p, S x S)
+ * Kj, r = y - m(X) and the jitter are exactly those of mogp_exact_predict on the handle's table, kinds and mean table; no noise and no mean is
+ * added to any output.  part_tables: P x C x C x T x W, each the model's table (same T, width, kinds, shapes) except for its AMPLITUDE column and
+ * the bias (Psi slot) of kind-7 rows: a zero amplitude silences a row's product group, a kind-7 row needs amplitude AND bias zero.  Any other
+ * difference is MOGP_EINVAL and names the first differing (pair, row, column); the tables are checked on the host.  kss_diag: P x C, or P x S
+ * per test point (the rule of mogp_exact_predict), the true prior diagonal of each part.  mu: P x S.  var: P x S, or P x S x S with full, where
+ * K_p(Xs, Xs) is a symmetric evaluation (a white row is on its diagonal).  Outputs in the caller's row order.  ONE factorisation and ONE
+ * substitution over the P stacked row blocks [K_1,sf ; .. ; K_P,sf ; y^T], in either form of mogp_exact_predict (tile dataflow or streams,
+ * mogp_model_set_accurate included); P = 1 with the model's own table returns that call's bits.  Sharded contexts are refused (MOGP_EINVAL). */
+int  mogp_exact_predict_parts(mogp_model* m, const double* noise_var, const double* data_var, double jitter,
+                              int P, const double* part_tables, const double* kss_diag, int64_t S, const double* Xs, int full,
+                              double* mu, double* var, int64_t* info);
+
 /* ---- Titsias sparse variational bound (BASELINE.json configs[4]) ------------------------------------------------ */
 /* replaces Titsias.elbo (gpr/model.py:700-724) and, with MOGP_EVAL_GRAD, the autograd backward of gpr.Model.loss():
  *   Z: M x (1+D) inducing inputs (channel id in column 0), sigma: SCALAR noise scale (gpr/model.py:686-689),
@@ -360,7 +376,9 @@ enum { MOGP_ST_GRAM = 0, MOGP_ST_POTRF = 1, MOGP_ST_TRTRI = 2, MOGP_ST_LAUUM = 3
        MOGP_ST_COUNT = 10 };
 int  mogp_set_profiling(mogp_model* m, int on);
 /* ms[MOGP_ST_COUNT]; MOGP_ST_GEMM_KERNEL = summed duration of every launch of the fp64 MFMA GEMM kernel;
- * *gemm_launches / *gemm_flops = their count and algorithmic flop total in the last eval. */
+ * *gemm_launches / *gemm_flops = their count and algorithmic flop total in the last eval.  After mogp_exact_predict /
+ * mogp_exact_predict_parts with profiling on, MOGP_ST_TOTAL is the device's span of that call (training Gram to the last reduction) and the
+ * counts are the call's (factorisation and substitution). */
 int  mogp_stage_ms(mogp_model* m, double* ms, int64_t* gemm_launches, double* gemm_flops);
 
 /* How the last mogp_exact_eval(MOGP_EVAL_GRAD) of this model was scheduled -- so that a silent degradation is visible (bench.py prints it,

@@ -62,6 +62,8 @@ SIGNATURES = {
     "mogp_model_loo_bytes": (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
     "mogp_exact_predict": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.c_double, c_dp, ctypes.c_int64, c_dp,
                                           ctypes.c_int, c_dp, c_dp, c_i64p]),
+    "mogp_exact_predict_parts": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.c_double, ctypes.c_int, c_dp, c_dp, ctypes.c_int64, c_dp,
+                                                ctypes.c_int, c_dp, c_dp, c_i64p]),
     "mogp_titsias_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_dp, ctypes.c_double, ctypes.c_double, c_dp, ctypes.c_int,
                                          c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_i64p]),
     "mogp_titsias_fetch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_dp]),
@@ -528,6 +530,29 @@ class ExactHandle:
                                         1 if full else 0, _dp(mu), _dp(var), ctypes.byref(info))
         check(code, info.value)
         return mu.reshape(-1, 1), (var if full else var.reshape(-1, 1))
+
+    def predict_parts(self, noise_var, jitter, part_tables, kss_diag, Xs, full=False, data_var=None):
+        """the posterior of every addend of the covariance behind one factorisation (mogp_exact_predict_parts): part_tables (P, C, C, T, W) are the
+        table last set with other amplitudes (and biases of dot-product rows), kss_diag (P, C) or (P, S) each part's prior diagonal
+        -> mu (P, S, 1), var (P, S, 1) or (P, S, S) with full; no noise, no mean.  Never sharded (gpr.Exact refuses before it gets here)"""
+        noise_var = _f64(noise_var)
+        data_var = _f64(data_var)
+        part_tables = _f64(part_tables)
+        kss_diag = _f64(kss_diag)
+        Xs = _f64(Xs)
+        S = Xs.shape[0]
+        if part_tables.ndim != 5 or part_tables.shape[1:] != (self.C, self.C, self.T, self.W):
+            raise ValueError("part_tables must be (P, C, C, T, W) with the shape of the table last set")
+        P = part_tables.shape[0]
+        if kss_diag.ndim != 2 or kss_diag.shape[0] != P or kss_diag.shape[1] not in (self.C, S):
+            raise ValueError("kss_diag must hold one row per part, per channel or per test point")
+        mu = np.empty((P, S))
+        var = np.empty((P, S, S) if full else (P, S))
+        info = ctypes.c_int64(0)
+        code = lib().mogp_exact_predict_parts(self._h, _dp(noise_var), _dp(data_var), float(jitter), P, _dp(part_tables), _dp(kss_diag), S, _dp(Xs),
+                                              1 if full else 0, _dp(mu), _dp(var), ctypes.byref(info))
+        check(code, info.value)
+        return mu.reshape(P, S, 1), (var if full else var.reshape(P, S, 1))
 
     # -- sharded evaluation stages (mogp_shard_*): buffers are raw device pointers, counts are in doubles ------------------
     def shard_begin(self, rank, world, noise_var, jitter, data_var=None):

@@ -467,27 +467,30 @@ int moment_pass(mogp_model* m, const double* kinv, double ksign, double* moments
     return 0;
 }
 
-int test_side(mogp_model* m, int64_t S, const double* Xs, const double* kss_diag, int64_t extra_rows, hipStream_t st, TestSide& ts, GramArgs& ga) {
+int test_side(mogp_model* m, int64_t S, const double* Xs, const double* kss_diag, int64_t extra_rows, hipStream_t st, TestSide& ts, GramArgs& ga, int R) {
     const int C = m->C, D = m->D;
     const int64_t Npad = m->Npad;
     SortedX& ss = ts.ss;
     int rc;
     if ((rc = sort_inputs(Xs, S, D, C, MOGP_TILE, ss))) return rc;
-    const int64_t Spad = ts.Spad = ss.Mpad, Srow = Spad + extra_rows;
+    const int64_t Spad = ts.Spad = ss.Mpad, Srow = R * Spad + extra_rows;      // R row blocks of Spad rows each over ONE sorted copy of Xs (R = 1: a plain prediction)
     std::vector<GTile> pt;
     build_rect_tiles(ss.off, m->sx.off, C, pt);
     ts.ntiles = (int)pt.size();
     if ((rc = m->d_xs.ensure((size_t)D * Spad))) return rc;
     if ((rc = m->d_Ksf.ensure((size_t)Srow * Npad))) return rc;
-    if ((rc = m->d_mu.ensure(Spad))) return rc;
-    if ((rc = m->d_kdiag.ensure(Spad))) return rc;
+    if ((rc = m->d_mu.ensure((size_t)R * Spad))) return rc;
+    if ((rc = m->d_kdiag.ensure((size_t)R * Spad))) return rc;
     if ((rc = m->d_ptiles.ensure(std::max<size_t>(pt.size(), 1)))) return rc;
-    std::vector<double> kd(Spad, 0.0);
+    std::vector<double> kd((size_t)R * Spad, 0.0);
     const bool per_point = m->Wt > 2 + 3 * D || (m->radial && m->point_kinds);      // terms with an envelope, dot-product or gate rows: kss_diag holds one value per test point (caller order)
-    for (int c = 0; c < C; ++c)
-        for (int pos = ss.off[c]; pos < ss.off[c + 1]; ++pos) kd[pos] = per_point ? kss_diag[ss.perm[pos]] : kss_diag[c];
+    for (int r = 0; r < R; ++r) {                                                   // (block r's diagonal: row r of kss_diag, C or S values)
+        const double* kr = kss_diag + (size_t)r * (per_point ? S : C);
+        for (int c = 0; c < C; ++c)
+            for (int pos = ss.off[c]; pos < ss.off[c + 1]; ++pos) kd[(size_t)r * Spad + pos] = per_point ? kr[ss.perm[pos]] : kr[c];
+    }
     HIP_TRY(hipMemcpyAsync(m->d_xs.p, ss.xs.data(), (size_t)D * Spad * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(m->d_kdiag.p, kd.data(), Spad * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m->d_kdiag.p, kd.data(), (size_t)R * Spad * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(m->d_ptiles.p, pt.data(), pt.size() * sizeof(GTile), hipMemcpyHostToDevice, st));
     // padded rows/columns of Ksf must be zero: rows >= S and columns >= N are never written by the Gram kernel
     HIP_TRY(hipMemsetAsync(m->d_Ksf.p, 0, (size_t)Srow * Npad * sizeof(double), st));
@@ -686,11 +689,17 @@ int mogp_model_loo_bytes(mogp_model* m, int64_t* bytes) {
 
 // mean_w (caller order, may be null): the predictive mean is K_sf mean_w instead of K_sf Kj^-1 y (the Opper-Archambeau model, whose mean
 // weights are variational parameters; its variance is the exact one with the per-point variances 1 / lambda^2)
+// parts (may be null: ONE row block built from the model's own table, a plain prediction): R amplitude-masked tables (host, R x C x C x T x W; checked by
+// mogp_exact_predict_parts) -- block p of [K_sf ; y^T] is K_p(Xs, X) from table p, the R blocks share the sorted Xs, the tile list, the factorisation and the ONE
+// substitution; kss_diag, mu and var then hold R rows.  psi_same[p] (p >= 1): table p has the Psi column of table p - 1, so its launch keeps the phase tables.
+struct PartTables { int R; const double* tables; const char* psi_same; };
 static int predict_core(mogp_model* m, const double* noise_var, const double* data_var, double jitter,
                         const double* kss_diag, int64_t S, const double* Xs, int full,
-                        double* mu, double* var, int64_t* info, const double* mean_w) {
+                        double* mu, double* var, int64_t* info, const double* mean_w, const PartTables* parts = nullptr) {
     int rc;
     if ((rc = begin_call(m, info, true))) return rc;
+    const int R = parts ? parts->R : 1;
+    const size_t tab_n = (size_t)m->C * m->C * m->T * m->Wt;
     // Cholesky factor only: the predictive equations need V = L^-1 K_fs and z = L^-1 y, never L^-1 itself (reference gpr/model.py:470-472 solves).
     // Round 1 / 2a formed W = L^-1 (N^3/3 flop) and multiplied; here [V | z] comes from ONE blocked forward substitution, N^2 (S+1) flop,
     // streamed behind the factorisation: block column K is solved as soon as the factorisation's chain has finished block K.
@@ -701,13 +710,21 @@ static int predict_core(mogp_model* m, const double* noise_var, const double* da
     HIP_TRY(hipEventRecord(m->pred_ev[0], m->st));                  // whatever the model's stream still holds comes first
     HIP_TRY(hipStreamWaitEvent(sv, m->pred_ev[0], 0));
     TestSide ts; GramArgs ga{};
-    if ((rc = test_side(m, S, Xs, kss_diag, MOGP_TILE, sv, ts, ga))) return rc;      // one more tile row of K_sf: its first row carries y^T through the same solve
+    if ((rc = test_side(m, S, Xs, kss_diag, MOGP_TILE, sv, ts, ga, R))) return rc;   // one more tile row of K_sf: its first row carries y^T through the same solve
     const SortedX& ss = ts.ss;
-    const int64_t Spad = ts.Spad, Srow = Spad + MOGP_TILE;
+    const int64_t Spad = ts.Spad, Sall = R * Spad, Srow = Sall + MOGP_TILE;          // R row blocks, the y^T tile row last
     if ((rc = m->d_Vt.ensure((size_t)Srow * Npad))) return rc;
-    if ((rc = m->d_var.ensure(Spad))) return rc;
-    HIP_TRY(hipMemcpyAsync(m->d_Ksf.p + Spad * Npad, m->d_y.p, Npad * sizeof(double), hipMemcpyDeviceToDevice, sv));
-    if ((rc = launch_gram(ga, ts.ntiles, sv, m->radial ? m->gate_kinds : 0))) return rc;
+    if ((rc = m->d_var.ensure(Sall))) return rc;
+    if (parts) {
+        if ((rc = m->d_parts.ensure(R * tab_n))) return rc;
+        HIP_TRY(hipMemcpyAsync(m->d_parts.p, parts->tables, R * tab_n * sizeof(double), hipMemcpyHostToDevice, sv));      // (pageable source: staged before the call returns)
+    }
+    HIP_TRY(hipMemcpyAsync(m->d_Ksf.p + Sall * Npad, m->d_y.p, Npad * sizeof(double), hipMemcpyDeviceToDevice, sv));
+    for (int p = 0; p < R; ++p) {                                    // block p: K_p(Xs, X) from table p into its Spad rows
+        GramArgs gp = ga;
+        if (parts) { gp.table = m->d_parts.p + p * tab_n; gp.out = m->d_Ksf.p + (int64_t)p * Spad * Npad; gp.phases_ready = p > 0 && parts->psi_same[p]; }
+        if ((rc = launch_gram(gp, ts.ntiles, sv, m->radial ? m->gate_kinds : 0))) return rc;
+    }
     if (mean_w) {                                                    // mu = K_sf w, before the substitution consumes K_sf
         std::vector<double> hw(Npad, 0.0);
         for (int64_t pos = 0; pos < m->N; ++pos) hw[pos] = mean_w[m->sx.perm[pos]];
@@ -792,44 +809,55 @@ static int predict_core(mogp_model* m, const double* noise_var, const double* da
         HIP_TRY(hipStreamWaitEvent(m->st, m->pred_ev[1], 0));
     }
     // mu = V^T z: the rows of X against its last row (z^T)
-    if (!mean_w && (rc = launch_gemv_rows(m->d_Vt.p, Npad, Spad, Npad, m->d_Vt.p + Spad * Npad, m->d_mu.p, m->st))) return rc;
+    if (!mean_w && (rc = launch_gemv_rows(m->d_Vt.p, Npad, Sall, Npad, m->d_Vt.p + Sall * Npad, m->d_mu.p, m->st))) return rc;
 
-    std::vector<double> hmu(Spad);
-    HIP_TRY(hipMemcpyAsync(hmu.data(), m->d_mu.p, Spad * sizeof(double), hipMemcpyDeviceToHost, m->st));
+    std::vector<double> hmu(Sall);
+    HIP_TRY(hipMemcpyAsync(hmu.data(), m->d_mu.p, Sall * sizeof(double), hipMemcpyDeviceToHost, m->st));
     // a hand-off of the dataflow schedule timed out: again, on streams
-    auto again = [&]() { return predict_core(m, noise_var, data_var, jitter, kss_diag, S, Xs, full, mu, var, info, mean_w); };
+    auto again = [&]() { return predict_core(m, noise_var, data_var, jitter, kss_diag, S, Xs, full, mu, var, info, mean_w, parts); };
     if (!full) {
-        if ((rc = launch_row_sqnorm_sub(m->d_Vt.p, Npad, Spad, Npad, m->d_kdiag.p, m->d_var.p, m->st))) return rc;
-        std::vector<double> hv(Spad);
-        HIP_TRY(hipMemcpyAsync(hv.data(), m->d_var.p, Spad * sizeof(double), hipMemcpyDeviceToHost, m->st));
+        if ((rc = launch_row_sqnorm_sub(m->d_Vt.p, Npad, Sall, Npad, m->d_kdiag.p, m->d_var.p, m->st))) return rc;
+        std::vector<double> hv(Sall);
+        HIP_TRY(hipMemcpyAsync(hv.data(), m->d_var.p, Sall * sizeof(double), hipMemcpyDeviceToHost, m->st));
+        if ((rc = mark(m, 5))) return rc;                      // (profiling: MOGP_ST_TOTAL of a prediction is the device's span of the whole call)
         HIP_TRY(hipStreamSynchronize(m->st));
         if ((rc = factorize_finish(m, gaK, nullptr, info))) return retry_on_streams(m, rc, again);      // the pivot report of the factorisation
-        scatter_by_perm(ss, hmu.data(), mu); scatter_by_perm(ss, hv.data(), var);
+        collect_timing(m, 5);
+        for (int p = 0; p < R; ++p) { scatter_by_perm(ss, hmu.data() + p * Spad, mu + p * S); scatter_by_perm(ss, hv.data() + p * Spad, var + p * S); }
         return MOGP_OK;
     }
-    // full covariance: K_ss - V^T V   (reference gpr/model.py:476-478)
+    // full covariance: K_ss - V^T V   (reference gpr/model.py:476-478), block by block
     std::vector<GTile> st_tiles;
     std::vector<int> ps;
     build_sym_tiles(ss.off, C, st_tiles, ps);
-    if ((rc = m->d_Kss.ensure((size_t)Spad * Spad))) return rc;
+    const size_t SS = (size_t)Spad * Spad;
+    if ((rc = m->d_Kss.ensure(R * SS))) return rc;
     if ((rc = m->d_ptiles.ensure(st_tiles.size()))) return rc;
-    HIP_TRY(hipMemsetAsync(m->d_Kss.p, 0, (size_t)Spad * Spad * sizeof(double), m->st));
+    HIP_TRY(hipMemsetAsync(m->d_Kss.p, 0, R * SS * sizeof(double), m->st));
     HIP_TRY(hipMemcpyAsync(m->d_ptiles.p, st_tiles.data(), st_tiles.size() * sizeof(GTile), hipMemcpyHostToDevice, m->st));
     ga.tiles = m->d_ptiles.p; ga.xc = m->d_xs.p; ga.ldxc = Spad; ga.ncols = S; ga.out = m->d_Kss.p; ga.ldo = Spad; ga.mirror = 1;
     if ((rc = m->ph_ss.prepare(ss.off, ss.off, C, m->T, Spad, Spad, m->st, ga.ph))) return rc;
-    if ((rc = launch_gram(ga, (int)st_tiles.size(), m->st, m->radial ? m->gate_kinds : 0))) return rc;
-    GemmArgs c{};
-    c.A = m->d_Vt.p; c.lda = Npad; c.a_kmajor = 0; c.B = m->d_Vt.p; c.ldb = Npad; c.b_kmajor = 0;
-    c.C = m->d_Kss.p; c.ldc = Spad; c.alpha = -1.0; c.beta = 1.0;
-    c.mode = GM_RECT; c.mt = c.nt = (int)(Spad / MOGP_TILE); c.K = (int)Npad; c.tasks = nullptr; c.ntasks = 0;
-    if ((rc = gemm_call(m, c, gemm_flops(c, nullptr)))) return rc;
-    std::vector<double> hc((size_t)Spad * Spad);
+    for (int p = 0; p < R; ++p) {
+        GramArgs gp = ga;
+        if (parts) { gp.table = m->d_parts.p + p * tab_n; gp.out = m->d_Kss.p + p * SS; gp.phases_ready = p > 0 && parts->psi_same[p]; }
+        if ((rc = launch_gram(gp, (int)st_tiles.size(), m->st, m->radial ? m->gate_kinds : 0))) return rc;
+        GemmArgs c{};
+        c.A = m->d_Vt.p + (int64_t)p * Spad * Npad; c.lda = Npad; c.a_kmajor = 0; c.B = c.A; c.ldb = Npad; c.b_kmajor = 0;
+        c.C = m->d_Kss.p + p * SS; c.ldc = Spad; c.alpha = -1.0; c.beta = 1.0;
+        c.mode = GM_RECT; c.mt = c.nt = (int)(Spad / MOGP_TILE); c.K = (int)Npad; c.tasks = nullptr; c.ntasks = 0;
+        if ((rc = gemm_call(m, c, gemm_flops(c, nullptr)))) return rc;
+    }
+    std::vector<double> hc(R * SS);
     HIP_TRY(hipMemcpyAsync(hc.data(), m->d_Kss.p, hc.size() * sizeof(double), hipMemcpyDeviceToHost, m->st));
+    if ((rc = mark(m, 5))) return rc;
     HIP_TRY(hipStreamSynchronize(m->st));
     if ((rc = factorize_finish(m, gaK, nullptr, info))) return retry_on_streams(m, rc, again);
-    scatter_by_perm(ss, hmu.data(), mu);
-    for (int64_t a = 0; a < S; ++a)
-        for (int64_t b = 0; b < S; ++b) var[ss.perm[a] * S + ss.perm[b]] = hc[(size_t)a * Spad + b];
+    collect_timing(m, 5);
+    for (int p = 0; p < R; ++p) {
+        scatter_by_perm(ss, hmu.data() + p * Spad, mu + p * S);
+        for (int64_t a = 0; a < S; ++a)
+            for (int64_t b = 0; b < S; ++b) var[(size_t)p * S * S + ss.perm[a] * S + ss.perm[b]] = hc[p * SS + (size_t)a * Spad + b];
+    }
     return MOGP_OK;
 }
 
@@ -838,6 +866,40 @@ int mogp_exact_predict(mogp_model* m, const double* noise_var, const double* dat
                        double* mu, double* var, int64_t* info) {
     if (!m || !Xs || !mu || !var || !kss_diag || S <= 0) return fail(MOGP_EINVAL, "mogp_exact_predict: bad argument");
     return predict_core(m, noise_var, data_var, jitter, kss_diag, S, Xs, full, mu, var, info, nullptr);
+}
+
+// The posterior of every addend of the model's covariance behind ONE factorisation and ONE substitution: predict_core with P row blocks.
+int mogp_exact_predict_parts(mogp_model* m, const double* noise_var, const double* data_var, double jitter, int P, const double* part_tables,
+                             const double* kss_diag, int64_t S, const double* Xs, int full, double* mu, double* var, int64_t* info) {
+    if (!m || !part_tables || !Xs || !mu || !var || !kss_diag || S <= 0 || P <= 0) return fail(MOGP_EINVAL, "mogp_exact_predict_parts: bad argument (null pointer, S <= 0 or P <= 0)");
+    if (m->T <= 0) return fail(MOGP_EINVAL, "mogp_model_set_terms must be called before an evaluation");
+    if (m->ctx->comm.kind != MOGP_COMM_NONE && m->ctx->comm.n > 1) return fail(MOGP_EINVAL, "mogp_exact_predict_parts: not sharded (the handle's context has a communicator of more than one rank)");
+    // a part's table is the model's but for the amplitudes and the bias of dot-product rows (their Psi slot): everything the phase tables, the kinds and the
+    // shapes depend on is the model's own
+    const int C = m->C, T = m->T, W = m->Wt;
+    const size_t n = (size_t)C * C * T * W;
+    std::vector<char> psi_same(P, 0);
+    for (int p = 0; p < P; ++p) {
+        const double* tp = part_tables + p * n;
+        bool same = p > 0;
+        for (int pair = 0; pair < C * C; ++pair)
+            for (int t = 0; t < T; ++t) {
+                const size_t row = ((size_t)pair * T + t) * W;
+                const bool dot = m->radial && (m->hkind[(size_t)pair * T + t] & MOGP_KIND_MASK) == MOGP_KIND_DOT;
+                if (!std::isfinite(tp[row])) return fail(MOGP_ENONFINITE, "mogp_exact_predict_parts: part " + std::to_string(p) + " has a non-finite amplitude");
+                if (p > 0 && std::memcmp(tp + row + 1, tp - n + row + 1, sizeof(double)) != 0) same = false;
+                for (int w = 1; w < W; ++w) {
+                    if (w == 1 && dot) { if (!std::isfinite(tp[row + 1])) return fail(MOGP_ENONFINITE, "mogp_exact_predict_parts: part " + std::to_string(p) + " has a non-finite bias"); continue; }
+                    if (std::memcmp(tp + row + w, m->table.data() + row + w, sizeof(double)) != 0)
+                        return fail(MOGP_EINVAL, "mogp_exact_predict_parts: part " + std::to_string(p) + " differs from the model's table at pair (" + std::to_string(pair / C) + ", " +
+                                                 std::to_string(pair % C) + "), row " + std::to_string(t) + ", column " + std::to_string(w) +
+                                                 ": only amplitudes and the bias of dot-product rows may differ");
+                }
+            }
+        psi_same[p] = same;
+    }
+    const PartTables parts{P, part_tables, psi_same.data()};
+    return predict_core(m, noise_var, data_var, jitter, kss_diag, S, Xs, full, mu, var, info, nullptr, &parts);
 }
 
 // OpperArchambeau.predict_f (reference gpr/model.py:640-668):  mu = K_sf nu,  var = K_ss - K_sf (K + diag(1 / lambda^2))^-1 K_fs, no jitter

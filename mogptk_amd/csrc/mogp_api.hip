@@ -792,7 +792,7 @@ int mogp_model_destroy(mogp_model* m) {
     if (m->gram_tail_ev) { hipError_t r = hipEventDestroy(m->gram_tail_ev); (void)r; m->gram_tail_ev = nullptr; }
     m->d_chan_off.release(); m->d_flag.release(); m->d_info.release(); m->d_pivots.release(); m->acc_rhs.release();
     m->d_xs.release(); m->d_Ksf.release(); m->d_Vt.release(); m->d_mu.release(); m->d_var.release(); m->d_kdiag.release();
-    m->d_Kss.release(); m->d_ptiles.release(); m->d_pred_tasks.release();
+    m->d_Kss.release(); m->d_parts.release(); m->d_ptiles.release(); m->d_pred_tasks.release();
     m->ph_xx.release(); m->ph_sx.release(); m->ph_ss.release();
     if (m->h_pin) { hipError_t e = hipHostFree(m->h_pin); (void)e; m->h_pin = nullptr; }
     mean_release(m);

@@ -322,6 +322,21 @@ class Kernel(ParameterHolder):
             gt[c, c, :, 0] = gc[c]
         self._spectral_backward(gt * _table_diag_weights(table, self._spectral_kinds(D)[0]))
 
+    def _parts(self, D):
+        """[(name, mask)]: the default partition of the kernel into addends, one level deep -- mask boolean (C, C, T) over the rows of
+        `_spectral_terms(D)`.  Default: one part, the whole kernel"""
+        return [(self.name(), np.ones(self._spectral_terms(D).shape[:3], dtype=bool))]
+
+    def _row_parts(self, D, names, bounds):
+        """parts that are consecutive row ranges of the table, the same in every channel pair: part i holds rows bounds[i] .. bounds[i + 1] - 1"""
+        shape = self._spectral_terms(D).shape[:3]
+        out = []
+        for i, name in enumerate(names):
+            mask = np.zeros(shape, dtype=bool)
+            mask[:, :, bounds[i]:bounds[i + 1]] = True
+            out.append(("%d:%s" % (i, name), mask))
+        return out
+
     def _product_refusal(self):
         """why this kernel cannot be a factor of a MulKernel on this path (None: it can)"""
         if self.output_dims is not None:
@@ -499,6 +514,11 @@ class AddKernel(Kernels):
     def _spectral_kinds(self, D):
         parts = [k._spectral_kinds(D) for k in self.kernels]       # along T, as the tables
         return np.concatenate([p[0] for p in parts], axis=2), np.concatenate([p[1] for p in parts], axis=2)
+
+    def _parts(self, D):
+        """one part per sub-kernel: its slice along T"""
+        T = [k._spectral_terms(D).shape[2] for k in self.kernels]
+        return self._row_parts(D, [k.name() for k in self.kernels], np.concatenate([[0], np.cumsum(T)]).astype(int))
 
     def _spectral_backward(self, gtable):
         t0 = 0

@@ -10,7 +10,7 @@ from math import erf, sqrt
 
 from .config import config
 from .parameter import Parameter, ParameterHolder, Softplus, Sigmoid, _STRUCTURE_EPOCH
-from .kernel import Kernel, MulKernel, ChangePointsKernel, terms_cache, KIND_TIMES, KIND_MASK, KIND_DOT, KIND_GATE, KIND_WDOT, group_diag_grad
+from .kernel import Kernel, MulKernel, ChangePointsKernel, terms_cache, KIND_TIMES, KIND_MASK, KIND_DOT, KIND_GATE, KIND_WDOT, group_diag_grad, group_diag, group_slices
 from .likelihood import Likelihood, GaussianLikelihood
 from .mean import Mean
 from .multioutput import MultiOutputSpectralMixtureKernel
@@ -749,6 +749,90 @@ class Exact(Model):
                 mu, var = again
         mu = self._add_mean(mu, X)
         return mu.astype(config.dtype, copy=False), var.astype(config.dtype, copy=False)
+
+    # -- the posterior by kernel part (mogp_exact_predict_parts) -----------------------------------------------------
+    PART_ROWS = 65536          # stacked test rows (parts x points) of one device call without the full covariance
+
+    def _refuse_sharded_parts(self):
+        comm = getattr(config, "comm", None)
+        if comm is not None and (comm.world > 1 or comm.force):
+            raise NotImplementedError("the posterior by kernel part is not carried through the sharded exact evaluation (use_distributed): "
+                                      "the parts share one factorisation on one device")
+
+    def parts(self):
+        """-> [(name, mask)]: the default partition of the kernel into addends, one level deep (`Kernel._parts`), each mask a boolean
+        (C, C, T) array over the rows of the device table"""
+        with terms_cache():
+            return self.kernel._parts(self._D)
+
+    def _part_masks(self, masks, kind):
+        """`masks` (P, T) or (P, C, C, T) as boolean (P, C, C, T); a mask that keeps part of a product group is refused by the group's rows"""
+        C, _, T = kind.shape
+        masks = np.asarray(masks)
+        if masks.dtype != np.bool_:
+            raise ValueError("masks must be boolean")
+        if masks.ndim == 2 and masks.shape[1] == T:
+            masks = np.broadcast_to(masks[:, None, None, :], (masks.shape[0], C, C, T))
+        if masks.ndim != 4 or masks.shape[1:] != (C, C, T) or masks.shape[0] < 1:
+            raise ValueError("masks must have shape (P, %d) or (P, %d, %d, %d): one flag per row of the device table" % (T, C, C, T))
+        for a, b in group_slices(kind[0, 0]):
+            if b - a > 1:
+                g = masks[..., a:b]
+                if np.any(np.any(g, axis=-1) != np.all(g, axis=-1)):
+                    p = int(np.argwhere(np.any(g, axis=-1) != np.all(g, axis=-1))[0][0])
+                    raise ValueError("mask %d keeps a part of the product group of rows %d .. %d: a part holds whole groups (the factors of "
+                                     "a product are not addends)" % (p, a, b - 1))
+        return np.ascontiguousarray(masks)
+
+    def predict_terms(self, X, masks, full=False):
+        """The posterior of the latent function of every addend K_p of the covariance, K = sum_p K_p, given ALL the data:
+            mu_p = K_p(X*, X) Kj^-1 r,    var_p = diag K_p(X*, X*) - diag(K_p(X*, X) Kj^-1 K_p(X, X*))     (full: the whole matrix)
+        with Kj and r = y - mean(X) the whole model's -- one factorisation and one substitution on the device for all parts.  `masks`: boolean
+        (P, T) over the rows of the device table (`_device_terms`), the same in every channel pair, or (P, C, C, T); a part keeps or drops
+        product groups whole.  -> (mu (P, S, 1), var (P, S, 1) or (P, S, S)).  No likelihood noise and no mean: the mean function belongs to
+        no part, and sum_p mu_p + mean(X*) is `predict_f`'s mean when the masks partition the rows.  A part's prior diagonal is the TRUE
+        diagonal of its masked table; the reference's `K_diag` of SpectralMixtureKernel at D > 1 (which is not diag K) is not reproduced
+        for parts."""
+        self._refuse_sharded_parts()                     # before any device call
+        X = self._check_input(X)
+        with terms_cache():
+            h, table, D = self._push_terms()
+            kind = self.kernel._device_terms(D)[1]
+            masks = self._part_masks(masks, kind)
+            P = masks.shape[0]
+            tabs = np.repeat(np.asarray(table, dtype=np.float64)[None], P, axis=0)
+            tabs[..., 0] = np.where(masks, tabs[..., 0], 0.0)
+            tabs[..., 1] = np.where(~masks & ((kind & KIND_MASK) == KIND_DOT)[None], 0.0, tabs[..., 1])      # (0 <x, x'> + 0)^n = 0
+            Xk = self.kernel._kernel_format(X)
+            per_point = _enveloped(table, D) or self.kernel._pointwise(self._D)
+            if per_point:
+                kss = np.stack([self.kernel._point_diag(tabs[p], Xk, D) for p in range(P)])
+            else:
+                C = kind.shape[0]
+                kss = np.array([[group_diag(tabs[p, c, c, :, 0], kind[c, c]) for c in range(C)] for p in range(P)])
+        S = Xk.shape[0]
+        step = S if full else max(1, self.PART_ROWS // P)
+        mus, vs = [], []
+        with self._cholesky_guard():
+            for s0 in range(0, S, step):
+                kc = kss[:, s0:s0 + step] if per_point else kss
+                run = lambda: h.predict_parts(self._noise_var(), self.jitter, tabs, kc, Xk[s0:s0 + step], full=full, data_var=self.data_variance)
+                mu, var = run()
+                again = self._check_conditioning(h, run)
+                if again is not None:
+                    mu, var = again
+                mus.append(mu)
+                vs.append(var)
+        mu = mus[0] if len(mus) == 1 else np.concatenate(mus, axis=1)
+        var = vs[0] if len(vs) == 1 else np.concatenate(vs, axis=1)
+        return mu.astype(config.dtype, copy=False), var.astype(config.dtype, copy=False)
+
+    def predict_parts(self, X, full=False):
+        """`predict_terms` over the default partition `parts()` -> (names, mu (P, S, 1), var (P, S, 1) or (P, S, S))"""
+        self._refuse_sharded_parts()
+        named = self.parts()
+        mu, var = self.predict_terms(X, np.stack([m for _, m in named]), full=full)
+        return [n for n, _ in named], mu, var
 
 
 # ---- inducing-point initialisation (reference gpr/model.py:11-69) ---------------------------------------------------

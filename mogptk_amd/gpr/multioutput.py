@@ -75,6 +75,23 @@ class IndependentMultiOutputKernel(MultiOutputKernel):
             shape[c, c, starts[c]:starts[c] + sh.shape[2]] = sh[0, 0]
         return kind | flags[None, None, :], shape
 
+    def _parts(self, D):
+        """part i: the union over the channels c of channel c's i-th part, on the pair (c, c) only; every channel must yield as many parts"""
+        subs = [k._parts(D) for k in self.kernels]
+        if len(set(len(s) for s in subs)) != 1:
+            raise NotImplementedError("the channels of %s split into different numbers of parts (%s): there is no default partition, pass masks "
+                                      "of your own to predict_terms" % (self.__class__.__name__, ", ".join(str(len(s)) for s in subs)))
+        starts, T, _ = self._layout(D)
+        C = self.output_dims
+        out = []
+        for i in range(len(subs[0])):
+            mask = np.zeros((C, C, T), dtype=bool)
+            for c, s in enumerate(subs):
+                rows = s[i][1][0, 0]
+                mask[c, c, starts[c]:starts[c] + rows.shape[0]] = rows
+            out.append(("%d:%s" % (i, ",".join(s[i][0].split(":", 1)[-1] for s in subs)), mask))
+        return out
+
     def _spectral_diag(self, D):
         return np.array([k._spectral_diag(D)[0] for k in self.kernels])   # reference :36-39
 
@@ -171,6 +188,11 @@ class MultiOutputSpectralMixtureKernel(MultiOutputKernel):
         inv = 1.0 / s
         dmu = mi - mj
         return w, mu, v, th, ph, vi, vj, mi, mj, s, inv, dmu
+
+    def _parts(self, D):
+        """one part per component q: its row in every channel pair"""
+        T = self._spectral_terms(D).shape[2]
+        return self._row_parts(D, [self.name()] * T, np.arange(T + 1))
 
     @cached_terms
     def _spectral_terms(self, D):
@@ -496,6 +518,11 @@ class LinearModelOfCoregionalizationKernel(MultiOutputKernel):
         kind = np.concatenate([np.broadcast_to(kd, (C, C) + kd.shape) for kd, _ in subs], axis=2)
         shape = np.concatenate([np.broadcast_to(sh, (C, C) + sh.shape) for _, sh in subs], axis=2)
         return np.ascontiguousarray(kind, dtype=np.int32), np.ascontiguousarray(shape)
+
+    def _parts(self, D):
+        """one part per base kernel q: its rows in every channel pair (`_rows`: the leading coregionalization row included)"""
+        T = [self._rows(k, D)[0].shape[0] for k in self.kernels]
+        return self._row_parts(D, [k.name() for k in self.kernels], np.concatenate([[0], np.cumsum(T)]).astype(int))
 
     def _spectral_diag(self, D):
         """reference :497-502: sum_q (sum_r w_cqr^2) K_diag_q -- with the base kernel's own K_diag convention"""

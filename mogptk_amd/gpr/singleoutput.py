@@ -43,6 +43,11 @@ class SpectralMixtureKernel(Kernel):
                 table[0, 0, t, 2 + D + d] = mu[q, d]
         return table
 
+    def _parts(self, D):
+        """one part per component q: its D rows"""
+        Q = self.magnitude.shape[0]
+        return self._row_parts(D, [self.name()] * Q, np.arange(Q + 1) * D)
+
     def _spectral_diag(self, D):
         return np.array([np.sum(self.magnitude())])                      # reference :602-605 (not x D)
 

@@ -848,6 +848,26 @@ class Model:
         mu, lower, upper = ([c[k] for c in per_channel] for k in range(3))
         return X, mu, lower, upper
 
+    def predict_parts(self, X=None, sigma=2):
+        """The posterior of every addend of the kernel (the default partition of `gpr.Exact.parts`: the sub-kernels of a sum or mixture, the
+        components of MOSM / SM, the base kernels of an LMC) given all the data: what each piece explains at X.  Returns
+        (X, names, mu, lower, upper); mu, lower and upper are one list per part, each a list per channel.  All values are in the model's
+        TRANSFORMED space and stay there: a part is a latent function, its parts sum to the latent posterior mean (less the mean function), and
+        `Y_transformer.backward` is not additive, so a part has no meaning in the data's own space.  lower / upper = mu -/+ sigma sqrt(var)
+        of the latent part, without likelihood noise.  Exact inference only."""
+        if not isinstance(self.gpr, gpr.Exact):
+            raise ValueError("predict_parts() needs exact inference (mogptk_amd.Exact): %s has no posterior by kernel part" % self.gpr.name())
+        X = self.dataset.get_prediction_data() if X is None else self.dataset._format_X(X)
+        names, mus, var = self.gpr.predict_parts(self._to_kernel_format(X))
+        edges = np.cumsum([0] + [Xj.shape[0] for Xj in X])
+        mu, lower, upper = [], [], []
+        for p in range(len(names)):
+            m, s = mus[p].reshape(-1), sigma * np.sqrt(var[p].reshape(-1))
+            mu.append([m[edges[j]:edges[j + 1]] for j in range(len(X))])
+            lower.append([(m - s)[edges[j]:edges[j + 1]] for j in range(len(X))])
+            upper.append([(m + s)[edges[j]:edges[j + 1]] for j in range(len(X))])
+        return X, names, mu, lower, upper
+
     def sample(self, X=None, n=None, prior=False, transformed=False):
         """Draws of y at X (the behaviour of reference mogptk/model.py:692-734; the posterior's full covariance comes from the device).  As in
         the reference `prior` is accepted and unused, and the stacked draws are cut into channels along their FIRST axis whatever n is."""
