@@ -261,6 +261,7 @@ struct StripTiles {
 // workspaces of the Titsias sparse bound (config 5): two M x M SPD systems and three M x N panels
 struct TitsiasWork {
     int64_t Mpad = 0;
+    int64_t Mrows = 0;                                  // rows of B and v that may hold values: the inducing count of the last evaluation (sparse_workspace)
     Spd a, q;                                           // Kuu (+jitter) and Qs = v v^T / s2 + I
     DevBuf<double> zx, B, v, GB, Qs, E, R, T1, GA, Hm;  // inputs [D][Mpad]; Kuf, W Kuf, dELBO/dKuf (Mpad x Npad); M x M temporaries
     DevBuf<double> vec, scratch, gz, partial_uu, partial_uf, mom_uu, mom_uf, zero_noise;
@@ -500,7 +501,7 @@ int mm_lower_splitk(mogp_model* m, TitsiasWork& t, const double* A, const double
                     double alpha = 1.0);
 // The scaffold of the three inducing-point models (sparse.hip); t is *m->tw, sz the channel-sorted inducing inputs.
 int launch_scale_cols(const double* in, double* out, int64_t ld, int64_t rows, int64_t n, const double* s, hipStream_t st);   // out[r][j] = in[r][j] * s[j]
-int sparse_workspace(mogp_model* m, TitsiasWork& t, int64_t Mpad);         // everything sized by Mpad alone, (re)allocated when Mpad changes
+int sparse_workspace(mogp_model* m, TitsiasWork& t, int64_t Mpad, int64_t M);      // everything sized by Mpad alone, (re)allocated when Mpad changes; the panels' rows from M on zero
 // device tile lists over (Z, Z) and -- want_uf -- (Z, X) with their pair starts and strip runs, rebuilt only when the channel offsets change
 int sparse_tiles(mogp_model* m, TitsiasWork& t, const SortedX& sz, bool want_uf);
 // Sorts Z (need_grouped: the refusal for inducing inputs that are not grouped by channel, for callers that cannot take them), sizes the

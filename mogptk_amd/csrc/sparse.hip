@@ -159,7 +159,7 @@ int mm_lower_splitk(mogp_model* m, TitsiasWork& t, const double* A, const double
     return 0;
 }
 
-int sparse_workspace(mogp_model* m, TitsiasWork& t, int64_t Mpad) {
+int sparse_workspace(mogp_model* m, TitsiasWork& t, int64_t Mpad, int64_t M) {
     const int C = m->C, D = m->D;
     const int64_t Npad = m->Npad;
     if (t.Mpad != Mpad) {
@@ -174,7 +174,16 @@ int sparse_workspace(mogp_model* m, TitsiasWork& t, int64_t Mpad) {
         RC(dev_fill_zero(t.zero_noise.p, C * sizeof(double)));
         RC(dev_fill_zero(t.B.p, (size_t)Mpad * Npad * sizeof(double)));      // padding of Kuf stays zero: the Gram kernel never writes it
         RC(dev_fill_zero(t.v.p, (size_t)Mpad * Npad * sizeof(double)));      // ... nor that of its working copy (the solves keep zeros zero)
+        t.Mrows = 0;
     }
+    // A smaller inducing set under the same Mpad (256 points, then 192): rows M .. Mrows - 1 of both panels still hold the larger set's K_uf and
+    // v.  Snelson and the Hensman models clear B themselves; Titsias writes both panels with one Gram kernel and relies on the padding here --
+    // without this its v v^T took 64 rows of the previous set along (tests/test_sparse_sweep_gpu.py: one handle, several inducing sets)
+    if (M < t.Mrows) {
+        HIP_TRY(hipMemsetAsync(t.B.p + (size_t)M * Npad, 0, (size_t)(t.Mrows - M) * Npad * sizeof(double), m->st));
+        HIP_TRY(hipMemsetAsync(t.v.p + (size_t)M * Npad, 0, (size_t)(t.Mrows - M) * Npad * sizeof(double), m->st));
+    }
+    t.Mrows = M;
     return 0;
 }
 
@@ -215,7 +224,7 @@ int sparse_kuu(mogp_model* m, int64_t M, const double* Z, double jitter, bool wa
     const int64_t Mpad = sz.Mpad;
     if (!m->tw) m->tw = new TitsiasWork();
     TitsiasWork& t = *m->tw;
-    RC(sparse_workspace(m, t, Mpad));
+    RC(sparse_workspace(m, t, Mpad, M));
     m->gemm_ev_used = 0; m->gemm_launches = 0; m->gemm_flops = 0.0;
     HIP_TRY(hipMemcpyAsync(t.zx.p, sz.xs.data(), (size_t)D * Mpad * sizeof(double), hipMemcpyHostToDevice, m->st));
     RC(sparse_tiles(m, t, sz, want_uf));

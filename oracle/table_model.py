@@ -360,6 +360,7 @@ def titsias_eval(self, Z, sigma, jitter, kff_diag, grad=True, sharded=False):
     ds2 = (-0.5 * N / s2 + 0.5 * np.trace(Pq @ Q) / s2 ** 2 + 0.5 * yy / s2 ** 2
            - (vy.T @ Pq @ vy).item() / s2 ** 3 + 0.5 * (vy.T @ Pq @ Q @ Pq @ vy).item() / s2 ** 4
            + 0.5 * (kff - np.trace(Q)) / s2 ** 2)
+    self._adjoints = (GA, GB)                               # d bound / d K_uu, d bound / d K_uf of the last evaluation, for the tests
     mom_uu = moments_dense(table, GA, Z, Z, sym=True)
     mom_uf = red(moments_dense(table, GB, Z, X, sym=False))
     gZ_uf, gZ_uu = np.zeros((M, D)), np.zeros((M, D))
@@ -462,6 +463,7 @@ def snelson_eval(self, Z, noise_var, jitter, kff_diag, grad=True, sharded=False)
     GB = W.T @ (np.outer(r, alpha) - R1 * G - 2.0 * v * h)
     GA = 0.5 * W.T @ (np.eye(M) - Pq + 2.0 * red((v * h) @ v.T)) @ W - 0.5 * np.outer(beta, beta)
     GA = 0.5 * (GA + GA.T)
+    self._adjoints = (GA, GB)
     mom_uu = moments_dense(table, GA, Z, Z, sym=True)
     mom_uf = red(moments_dense(table, GB, Z, X, sym=False))
     gZ = np.zeros((M, D))
@@ -573,6 +575,7 @@ def svgp_backward(self, e, f, sharded=False):
         GB = W.T @ Gv
         GA = -0.5 * W.T @ psi(red(np.tril(Gv @ v.T))) @ W
     GA = 0.5 * (GA + GA.T)
+    self._adjoints = (GA, GB)
     mom_uu = moments_dense(table, GA, Z, Z, sym=True)
     mom_uf = red(moments_dense(table, GB, Z, X, sym=False))
     gZ = np.zeros((M, D))
