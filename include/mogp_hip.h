@@ -250,6 +250,28 @@ int  mogp_exact_predict_parts(mogp_model* m, const double* noise_var, const doub
                               int P, const double* part_tables, const double* kss_diag, int64_t S, const double* Xs, int full,
                               double* mu, double* var, int64_t* info);
 
+/* The posterior of the DERIVATIVE of the latent function, df/dx_d, at the test points (no reference seam: mogptk has no such call -- the derivative of
+ * a Gaussian process is a Gaussian process, Rasmussen & Williams 9.4; checked against torch autograd of the reference's own kernel objects in
+ * tests/golden/gen_deriv.py).  With x* a test point on channel c and d an input dimension:
+ *   dmu_d(x*)  = j_d(x*)^T Kj^-1 r,               j_d(x*)_b = dK(x*, x_b)/dx*_d
+ *   dvar_d(x*) = kappa_d(x*) - |L^-1 j_d(x*)|^2,   kappa_d(x*) = d^2 K(x, x')/dx_d dx'_d at x = x' = x*   (dkss_diag, from the caller)
+ * Kj, r = y - m(X) and the jitter are exactly those of mogp_exact_predict on the handle's table, kinds and mean table; no noise is added, and the
+ * derivative of the mean function is the caller's to add.  Per table row, u = x_a - x_b + Delta, theta = 2 pi (M.u + Psi), s = sum_d V_d u_d^2,
+ * psi = -2 dphi/ds:
+ *   Gaussian rows (kind 0; any D, delay, phase)    dk/dx_a,d = A E [ -V_d u_d cos theta - 2 pi M_d sin theta ]
+ *   ... with an envelope (width 2 + 5 D)           - 1/2 L_d a_d k,  a = midpoint - centre
+ *   kinds 1, 3, 4, 6 (RQ, Matern 3/2, 5/2, sinc)   A [ -psi(s) V_d u_d cos theta - 2 pi M_d phi(s) sin theta ]   (u psi = 0 at r = 0)
+ *   kind 5 (periodic)                              -A 2 pi M_d V_0 sin theta exp(V_0 (cos theta - 1))
+ *   kind 7 (dot product)                           n b^(n-1) A x_b,d,  b = A <x_a, x_b> + c
+ *   a product group                                sum_h dk_h prod_{g != h} k_g
+ * Refused by name (MOGP_EINVAL, before any device work): kind 2 (Matern 1/2, the exponential kernel) and kind 10 (white) -- their sample paths
+ * are not differentiable and kappa is infinite; kind 8 (gate) and kind 9 (weighted dot) -- not yet; a sharded context.  dkss_diag, dmu, dvar:
+ * D x S, one row per input dimension, in the caller's row order.  ONE factorisation and ONE substitution over the D stacked row blocks
+ * [J_1 ; .. ; J_D ; y^T] written by one Gram launch, in either form of mogp_exact_predict (tile dataflow or streams, mogp_model_set_accurate
+ * included).  There is no covariance between derivatives. */
+int  mogp_exact_predict_grad(mogp_model* m, const double* noise_var, const double* data_var, double jitter,
+                             const double* dkss_diag, int64_t S, const double* Xs, double* dmu, double* dvar, int64_t* info);
+
 /* ---- Titsias sparse variational bound (BASELINE.json configs[4]) ------------------------------------------------ */
 /* replaces Titsias.elbo (gpr/model.py:700-724) and, with MOGP_EVAL_GRAD, the autograd backward of gpr.Model.loss():
  *   Z: M x (1+D) inducing inputs (channel id in column 0), sigma: SCALAR noise scale (gpr/model.py:686-689),

@@ -467,7 +467,7 @@ int moment_pass(mogp_model* m, const double* kinv, double ksign, double* moments
     return 0;
 }
 
-int test_side(mogp_model* m, int64_t S, const double* Xs, const double* kss_diag, int64_t extra_rows, hipStream_t st, TestSide& ts, GramArgs& ga, int R) {
+int test_side(mogp_model* m, int64_t S, const double* Xs, const double* kss_diag, int64_t extra_rows, hipStream_t st, TestSide& ts, GramArgs& ga, int R, bool point_diag) {
     const int C = m->C, D = m->D;
     const int64_t Npad = m->Npad;
     SortedX& ss = ts.ss;
@@ -483,7 +483,7 @@ int test_side(mogp_model* m, int64_t S, const double* Xs, const double* kss_diag
     if ((rc = m->d_kdiag.ensure((size_t)R * Spad))) return rc;
     if ((rc = m->d_ptiles.ensure(std::max<size_t>(pt.size(), 1)))) return rc;
     std::vector<double> kd((size_t)R * Spad, 0.0);
-    const bool per_point = m->Wt > 2 + 3 * D || (m->radial && m->point_kinds);      // terms with an envelope, dot-product or gate rows: kss_diag holds one value per test point (caller order)
+    const bool per_point = point_diag || m->Wt > 2 + 3 * D || (m->radial && m->point_kinds);      // terms with an envelope, dot-product or gate rows (or the caller says so): kss_diag holds one value per test point (caller order)
     for (int r = 0; r < R; ++r) {                                                   // (block r's diagonal: row r of kss_diag, C or S values)
         const double* kr = kss_diag + (size_t)r * (per_point ? S : C);
         for (int c = 0; c < C; ++c)
@@ -692,13 +692,19 @@ int mogp_model_loo_bytes(mogp_model* m, int64_t* bytes) {
 // parts (may be null: ONE row block built from the model's own table, a plain prediction): R amplitude-masked tables (host, R x C x C x T x W; checked by
 // mogp_exact_predict_parts) -- block p of [K_sf ; y^T] is K_p(Xs, X) from table p, the R blocks share the sorted Xs, the tile list, the factorisation and the ONE
 // substitution; kss_diag, mu and var then hold R rows.  psi_same[p] (p >= 1): table p has the Psi column of table p - 1, so its launch keeps the phase tables.
-struct PartTables { int R; const double* tables; const char* psi_same; };
+// The row blocks of a call are one of two descriptions.  tables != null: block p is the Gram from table p (above).  jacobian (mogp_exact_predict_grad):
+// block d is the Jacobian dK(Xs, X)/dx*_d of the model's OWN table in input dimension d, R = D, all blocks written by ONE launch (gram.hip:k_gram_dx); kss_diag
+// then holds one value per block and test point whatever the table (D x S, caller order), and there is no full covariance.
+struct RowBlocks { int R; const double* tables; const char* psi_same; bool jacobian; };
 static int predict_core(mogp_model* m, const double* noise_var, const double* data_var, double jitter,
                         const double* kss_diag, int64_t S, const double* Xs, int full,
-                        double* mu, double* var, int64_t* info, const double* mean_w, const PartTables* parts = nullptr) {
+                        double* mu, double* var, int64_t* info, const double* mean_w, const RowBlocks* blocks = nullptr) {
     int rc;
     if ((rc = begin_call(m, info, true))) return rc;
-    const int R = parts ? parts->R : 1;
+    const int R = blocks ? blocks->R : 1;
+    const bool jac = blocks && blocks->jacobian;
+    const RowBlocks* parts = blocks && blocks->tables ? blocks : nullptr;      // blocks that bring tables of their own
+    if (jac && (full || mean_w)) return fail(MOGP_EINVAL, "predict_core: Jacobian row blocks have no full covariance and no mean weights");
     const size_t tab_n = (size_t)m->C * m->C * m->T * m->Wt;
     // Cholesky factor only: the predictive equations need V = L^-1 K_fs and z = L^-1 y, never L^-1 itself (reference gpr/model.py:470-472 solves).
     // Round 1 / 2a formed W = L^-1 (N^3/3 flop) and multiplied; here [V | z] comes from ONE blocked forward substitution, N^2 (S+1) flop,
@@ -710,7 +716,7 @@ static int predict_core(mogp_model* m, const double* noise_var, const double* da
     HIP_TRY(hipEventRecord(m->pred_ev[0], m->st));                  // whatever the model's stream still holds comes first
     HIP_TRY(hipStreamWaitEvent(sv, m->pred_ev[0], 0));
     TestSide ts; GramArgs ga{};
-    if ((rc = test_side(m, S, Xs, kss_diag, MOGP_TILE, sv, ts, ga, R))) return rc;   // one more tile row of K_sf: its first row carries y^T through the same solve
+    if ((rc = test_side(m, S, Xs, kss_diag, MOGP_TILE, sv, ts, ga, R, jac))) return rc;   // one more tile row of K_sf: its first row carries y^T through the same solve
     const SortedX& ss = ts.ss;
     const int64_t Spad = ts.Spad, Sall = R * Spad, Srow = Sall + MOGP_TILE;          // R row blocks, the y^T tile row last
     if ((rc = m->d_Vt.ensure((size_t)Srow * Npad))) return rc;
@@ -720,6 +726,9 @@ static int predict_core(mogp_model* m, const double* noise_var, const double* da
         HIP_TRY(hipMemcpyAsync(m->d_parts.p, parts->tables, R * tab_n * sizeof(double), hipMemcpyHostToDevice, sv));      // (pageable source: staged before the call returns)
     }
     HIP_TRY(hipMemcpyAsync(m->d_Ksf.p + Sall * Npad, m->d_y.p, Npad * sizeof(double), hipMemcpyDeviceToDevice, sv));
+    if (jac) {                                                       // block d: dK(Xs, X)/dx*_d, every block from the one launch
+        if ((rc = launch_gram_dx(ga, ts.ntiles, Spad * Npad, sv))) return rc;
+    } else
     for (int p = 0; p < R; ++p) {                                    // block p: K_p(Xs, X) from table p into its Spad rows
         GramArgs gp = ga;
         if (parts) { gp.table = m->d_parts.p + p * tab_n; gp.out = m->d_Ksf.p + (int64_t)p * Spad * Npad; gp.phases_ready = p > 0 && parts->psi_same[p]; }
@@ -814,7 +823,7 @@ static int predict_core(mogp_model* m, const double* noise_var, const double* da
     std::vector<double> hmu(Sall);
     HIP_TRY(hipMemcpyAsync(hmu.data(), m->d_mu.p, Sall * sizeof(double), hipMemcpyDeviceToHost, m->st));
     // a hand-off of the dataflow schedule timed out: again, on streams
-    auto again = [&]() { return predict_core(m, noise_var, data_var, jitter, kss_diag, S, Xs, full, mu, var, info, mean_w, parts); };
+    auto again = [&]() { return predict_core(m, noise_var, data_var, jitter, kss_diag, S, Xs, full, mu, var, info, mean_w, blocks); };
     if (!full) {
         if ((rc = launch_row_sqnorm_sub(m->d_Vt.p, Npad, Sall, Npad, m->d_kdiag.p, m->d_var.p, m->st))) return rc;
         std::vector<double> hv(Sall);
@@ -898,8 +907,27 @@ int mogp_exact_predict_parts(mogp_model* m, const double* noise_var, const doubl
             }
         psi_same[p] = same;
     }
-    const PartTables parts{P, part_tables, psi_same.data()};
+    const RowBlocks parts{P, part_tables, psi_same.data(), false};
     return predict_core(m, noise_var, data_var, jitter, kss_diag, S, Xs, full, mu, var, info, nullptr, &parts);
+}
+
+// The posterior of df/dx_d at the test points: predict_core over D Jacobian row blocks [J_1 ; .. ; J_D ; y^T], J_d = dK(Xs, X)/dx*_d.
+int mogp_exact_predict_grad(mogp_model* m, const double* noise_var, const double* data_var, double jitter,
+                            const double* dkss_diag, int64_t S, const double* Xs, double* dmu, double* dvar, int64_t* info) {
+    if (!m || !dkss_diag || !Xs || !dmu || !dvar || S <= 0) return fail(MOGP_EINVAL, "mogp_exact_predict_grad: bad argument (null pointer or S <= 0)");
+    if (m->T <= 0) return fail(MOGP_EINVAL, "mogp_model_set_terms must be called before an evaluation");
+    if (m->ctx->comm.kind != MOGP_COMM_NONE && m->ctx->comm.n > 1) return fail(MOGP_EINVAL, "mogp_exact_predict_grad: not sharded (the handle's context has a communicator of more than one rank)");
+    if (m->radial)
+        for (size_t k = 0; k < (size_t)m->C * m->C * m->T; ++k) {
+            const int kd = m->hkind[k] & MOGP_KIND_MASK;
+            const std::string row = "row " + std::to_string(k % m->T) + " of pair (" + std::to_string(k / m->T / m->C) + ", " + std::to_string(k / m->T % m->C) + ") is ";
+            if (kd == MOGP_KIND_MATERN12) return fail(MOGP_EINVAL, "mogp_exact_predict_grad: " + row + "a Matern 1/2 (exponential) row (kind 2): its sample paths are not differentiable");
+            if (kd == MOGP_KIND_WHITE) return fail(MOGP_EINVAL, "mogp_exact_predict_grad: " + row + "a white row (kind 10): its sample paths are not differentiable");
+            if (kd == MOGP_KIND_GATE) return fail(MOGP_EINVAL, "mogp_exact_predict_grad: " + row + "a gate row (kind 8): its input derivative is not yet carried on the device");
+            if (kd == MOGP_KIND_WDOT) return fail(MOGP_EINVAL, "mogp_exact_predict_grad: " + row + "a weighted-dot row (kind 9): its input derivative is not yet carried on the device");
+        }
+    const RowBlocks blocks{m->D, nullptr, nullptr, true};
+    return predict_core(m, noise_var, data_var, jitter, dkss_diag, S, Xs, 0, dmu, dvar, info, nullptr, &blocks);
 }
 
 // OpperArchambeau.predict_f (reference gpr/model.py:640-668):  mu = K_sf nu,  var = K_ss - K_sf (K + diag(1 / lambda^2))^-1 K_fs, no jitter

@@ -229,7 +229,8 @@ __device__ __forceinline__ void stage_item_load(StageItem<DM>& I, int which, int
 // factors are the plain phase factors (times the amplitude; not for the periodic profile, whose phase is the profile's argument).
 // `kinds`: the pair's kind row (RAD only).  GATE: 1 = the instantiation that carries the gate row, 2 = the one that carries the gate,
 // weighted-dot and white rows (all below); an instantiation holds none of the code of the rows it does not carry
-template <int DM, bool AMP, bool RAD = false, int GATE = 0>
+// SPLIT = false (k_gram_dx): no tile-centred split -- a Gaussian term is GT_SKIP or GT_GENERAL and the staged factors are the plain phase factors
+template <int DM, bool AMP, bool RAD = false, int GATE = 0, bool SPLIT = true>
 __device__ __forceinline__ void stage_item_compute(TileLds<DM>& L, const StageItem<DM>& I, const TileCtx<DM>& X, const double* tab, int W,
                                                    int which, int t, int pnt, int D, int t0, const int* kinds = nullptr) {
     const double* row = tab + (size_t)(t0 + t) * W;
@@ -284,7 +285,7 @@ __device__ __forceinline__ void stage_item_compute(TileLds<DM>& L, const StageIt
     }
     int deg;
     if ((AMP && A == 0.0) || 0.5 * emin > GT_SKIP_EXPONENT) deg = GT_SKIP;
-    else if (!(zmax <= 0.45) || !(0.5 * es < 600.0) || !(0.5 * efac < 600.0)) deg = GT_GENERAL;
+    else if (!SPLIT || !(zmax <= 0.45) || !(0.5 * es < 600.0) || !(0.5 * efac < 600.0)) deg = GT_GENERAL;
     else deg = GT_DEGREE(zmax);
     if (pnt == 0 && which == 0) {
         L.deg[t] = deg; L.A[t] = A;
@@ -328,7 +329,7 @@ __device__ __forceinline__ void stage_item_compute(TileLds<DM>& L, const StageIt
 #define STAGE_MAP(tid) const int st_wave = __builtin_amdgcn_readfirstlane((tid) >> 6), st_which = st_wave & 1, st_tb = st_wave >> 1, st_pnt = (tid) & 63
 
 // one chunk of terms into LDS; BATCH: all items' loads first (one memory round trip), else item by item (large D: registers)
-template <int DM, bool AMP, bool BATCH, bool RAD = false, int GATE = 0>
+template <int DM, bool AMP, bool BATCH, bool RAD = false, int GATE = 0, bool SPLIT = true>
 __device__ __forceinline__ void stage_chunk(TileLds<DM>& L, const TileCtx<DM>& X, const GTile& tl, const double* tab, int W, int D,
                                             int C, int T, int t0, int nt, const PhaseView& v, const double* __restrict__ xr, int64_t ldxr,
                                             const double* __restrict__ xc, int64_t ldxc, int tid, const int* kinds = nullptr) {
@@ -340,12 +341,12 @@ __device__ __forceinline__ void stage_chunk(TileLds<DM>& L, const TileCtx<DM>& X
             if (st_tb + 2 * k < nt) stage_item_load<DM>(I[k], st_which, st_tb + 2 * k, st_pnt, tl, D, C, T, t0, v, xr, ldxr, xc, ldxc);
 #pragma unroll
         for (int k = 0; k < STAGE_ITEMS; ++k)
-            if (st_tb + 2 * k < nt) stage_item_compute<DM, AMP, RAD, GATE>(L, I[k], X, tab, W, st_which, st_tb + 2 * k, st_pnt, D, t0, kinds);
+            if (st_tb + 2 * k < nt) stage_item_compute<DM, AMP, RAD, GATE, SPLIT>(L, I[k], X, tab, W, st_which, st_tb + 2 * k, st_pnt, D, t0, kinds);
     } else {
         for (int t = st_tb; t < nt; t += 2) {
             StageItem<DM> I;
             stage_item_load<DM>(I, st_which, t, st_pnt, tl, D, C, T, t0, v, xr, ldxr, xc, ldxc);
-            stage_item_compute<DM, AMP, RAD, GATE>(L, I, X, tab, W, st_which, t, st_pnt, D, t0, kinds);
+            stage_item_compute<DM, AMP, RAD, GATE, SPLIT>(L, I, X, tab, W, st_which, t, st_pnt, D, t0, kinds);
         }
     }
 }
@@ -1332,6 +1333,248 @@ int launch_gram(const GramArgs& a0, int ntiles, hipStream_t s, int rows) {
         case 3: hipLaunchKernelGGL(k_gram<3>, dim3(grid), dim3(256), dyn, s, a, ntiles); break;
         default: hipLaunchKernelGGL(k_gram<0>, dim3(grid), dim3(256), dyn, s, a, ntiles); break;
     }
+    if (a.ev1) HIP_TRY(hipEventRecord(a.ev1, s));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- the Jacobian of a rectangular Gram with respect to its ROW inputs ----------------------------------------------------
+// J_d[a][b] = dK(x_a, x_b)/dx_a,d for every input dimension d, WRITTEN as D row blocks (block d at out + d * dstride): the right-hand sides of
+// the posterior of df/dx (exact.hip: mogp_exact_predict_grad).  The entry formula is the one moment_term<.., ZG> contracts against an adjoint,
+// here for every row kind the exact path differentiates:
+//   Gaussian (and enveloped) rows   A E [ -V_d u_d cos - 2 pi M_d sin ]  ( - 1/2 L_d a_d k,  a = midpoint - centre )
+//   profile rows (1, 3, 4, 6)       A [ -psi(s) V_d u_d cos - 2 pi M_d phi(s) sin ],  psi = -2 dphi/ds (radial_profile<true>: u psi = 0 at r = 0)
+//   periodic rows                   -A 2 pi M_d V_0 sin exp(V_0 (cos - 1))
+//   dot-product rows                n b^(n-1) A x_b,d,  b = A <x_a, x_b> + c
+//   a product group                 sum_h dk_h prod_{g != h} k_g   (the other rows recomputed, never divided out: group_factor_radial)
+// One 64 x 64 tile per workgroup, 4 x 4 entries per thread (the rg / cg mapping of k_moments), staged by tile_context / stage_chunk without the
+// tile-centred split (SPLIT = false): every term entry by entry.  A plain launch: nothing accumulates across tiles, no flags, no atomics.  A thread
+// keeps 16 DB running sums: DB = D for D <= 3, and the generic instantiation walks the dimensions two at a time (the terms are staged and evaluated
+// again for every pair of dimensions) instead of holding 128 sums.  Kinds 2, 8, 9 and 10 never get here: the entry point refuses them by name.
+template <int DM, int DB, bool ENV>
+__device__ __forceinline__ void dx_term(double (&acc)[DB][4][4], const double (&p)[4][DM], const double (&q)[4][DM],
+                                        const TileLds<DM>& L, int t, int D, int d0,
+                                        const double (&cu)[4], const double (&su)[4], const double (&cw)[4], const double (&sw)[4]) {
+    const double* V = L.V[t];
+    const double* s = L.s[t];
+    const double* Mv = L.M[t];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        __builtin_amdgcn_sched_barrier(0);                  // one row of four library exps at a time (see gram_term_radial)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            const double e = gauss_general<DM>(p[m], q[n], V, s, L.L[t], L.e[t], D);
+            const double kc = e * fma(cu[m], cw[n], su[m] * sw[n]);
+            const double ks = e * fma(su[m], cw[n], -cu[m] * sw[n]);
+            for (int d = 0; d < D; ++d) {
+                if (d < d0 || d >= d0 + DB) continue;
+                const double u = (p[m][d] - q[n][d]) + s[d];
+                double j = -fma(V[d] * u, kc, 6.283185307179586476925286766559 * Mv[d] * ks);
+                if (ENV) j = fma(-0.5 * L.L[t][d] * (0.5 * (p[m][d] + q[n][d]) + L.e[t][d]), kc, j);      // the envelope sits on the MIDPOINT
+#pragma unroll
+                for (int dd = 0; dd < DB; ++dd) acc[dd][m][n] += (d - d0 == dd) ? j : 0.0;
+            }
+        }
+    }
+}
+
+// w (WT): the entry's weight, the product of the group's other rows
+template <int DM, int DB, bool WT>
+__device__ __forceinline__ void dx_term_radial(double (&acc)[DB][4][4], const double (&w)[4][4], const double (&p)[4][DM], const double (&q)[4][DM],
+                                               const TileLds<DM>& L, int t, int D, int d0, int kind, double shape, int rg, int cg) {
+    const double* V = L.V[t];
+    const double* s = L.s[t];
+    const double* Mv = L.M[t];
+    const double A = L.A[t];
+    if (kind == MOGP_KIND_DOT) {                            // x_b = q + the column centre the staging left in L.L
+        const int n = dot_row_degree(shape);
+        const double c = L.e[t][0];
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int nn = 0; nn < 4; ++nn) {
+                const double b = fma(A, dot_row_inner<DM>(p[m], q[nn], L, t, D), c);
+                double g = (double)n * A * (n > 1 ? dot_row_power(b, n - 1) : 1.0);
+                if (WT) g *= w[m][nn];
+                for (int d = 0; d < D; ++d) {
+                    if (d < d0 || d >= d0 + DB) continue;
+                    const double j = g * (q[nn][d] + L.L[t][d]);
+#pragma unroll
+                    for (int dd = 0; dd < DB; ++dd) acc[dd][m][nn] += (d - d0 == dd) ? j : 0.0;
+                }
+            }
+        return;
+    }
+    const bool per = kind == MOGP_KIND_PERIODIC;
+    double cw[4], sw[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) { cw[n] = L.cw[t][cg * 4 + n]; sw[n] = L.sw[t][cg * 4 + n]; }
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const double cu = L.cu[t][rg * 4 + m], su = L.su[t][rg * 4 + m];      // (times the amplitude, but for the periodic row: stage_item_compute)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            if ((n & 1) == 0) __builtin_amdgcn_sched_barrier(0);      // two entries' profiles at a time (see moment_term_radial)
+            const double cc = fma(cu, cw[n], su * sw[n]), sn = fma(su, cw[n], -cu * sw[n]);
+            double phi, psi, kc, ks;
+            if (per) {                                      // k = A exp(V_0 (cos - 1)): dk/dtheta = -A V_0 sin exp(..), nothing through s
+                radial_profile<false>(MOGP_KIND_GAUSS, shape, periodic_s(V[0], cc), phi, psi);
+                kc = 0.0;
+                ks = A * V[0] * sn * phi;
+            } else {
+                radial_profile<true>(kind, shape, radial_s<DM>(p[m], q[n], V, s, D), phi, psi);
+                kc = psi * cc;
+                ks = phi * sn;
+            }
+            if (WT) { kc *= w[m][n]; ks *= w[m][n]; }
+            for (int d = 0; d < D; ++d) {
+                if (d < d0 || d >= d0 + DB) continue;
+                const double u = (p[m][d] - q[n][d]) + s[d];
+                const double j = -fma(V[d] * u, kc, 6.283185307179586476925286766559 * Mv[d] * ks);
+#pragma unroll
+                for (int dd = 0; dd < DB; ++dd) acc[dd][m][n] += (d - d0 == dd) ? j : 0.0;
+            }
+        }
+    }
+}
+
+template <int DT, bool ENV, bool RAD>
+__global__ __launch_bounds__(256) void k_gram_dx(GramArgs a, int ntiles, int64_t dstride) {
+    static_assert(!(ENV && RAD), "radial rows carry no envelope");
+    constexpr int DM = DT > 0 ? DT : MOGP_MAXD;
+    constexpr int DB = RAD ? 1 : (DT > 0 ? DT : 2);          // (the profiles' library calls leave a radial thread registers for one block of sums)
+    const int D = DT > 0 ? DT : a.D;
+    const int W = a.W;
+    const int tid = threadIdx.x;
+    const int cg = tid & 15, rg = tid >> 4;
+    if ((int)blockIdx.x >= ntiles) return;
+    const GTile tl = a.tiles[blockIdx.x];
+    const double* tab = a.table + (size_t)tl.pair * a.T * W;
+    const int* kinds = RAD ? a.kind + (size_t)tl.pair * a.T : nullptr;
+    __shared__ TileLds<DM> L;
+    const PhaseView v = phase_view(a.ph.ws, a.C, a.T, D, a.ldxr, a.ldxc);
+    TileCtx<DM> X;
+    double p[4][DM], q[4][DM];
+    tile_context<DM>(X, p, q, tl, D, v, a.xr, a.ldxr, a.xc, a.ldxc, rg, cg);
+    double one[4][4];                                        // (the weight of a group of one: never read, WT = false)
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) one[m][n] = 1.0;
+    const bool full = tl.nr == MOGP_GT && tl.nc == MOGP_GT && ((tl.c0 & 1) == 0) && ((a.ldo & 1) == 0) && ((dstride & 1) == 0);
+
+    for (int d0 = 0; d0 < D; d0 += DB) {
+        double acc[DB][4][4];
+#pragma unroll
+        for (int dd = 0; dd < DB; ++dd)
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int n = 0; n < 4; ++n) acc[dd][m][n] = 0.0;
+        for (int t0 = 0, nt; t0 < a.T; t0 += nt) {
+            if constexpr (RAD) nt = radial_chunk(a.kind, a.T, t0); else nt = min(MOGP_TC, a.T - t0);
+            if (t0 > 0 || d0 > 0) __syncthreads();           // the chunk before this one has been consumed
+            stage_chunk<DM, true, false, RAD, 0, false>(L, X, tl, tab, W, D, a.C, a.T, t0, nt, v, a.xr, a.ldxr, a.xc, a.ldxc, tid, kinds);
+            __syncthreads();
+            if constexpr (RAD) {
+                const int* kd = kinds + t0;
+                const double* sh = a.shape + (size_t)tl.pair * a.T + t0;
+                for (int t = 0, te; t < nt; t = te + 1) {    // group by group, as k_gram walks them
+                    bool skip = false;
+                    for (te = t;; ++te) {
+                        skip |= L.deg[te] == GT_SKIP;
+                        if (te == nt - 1 || !(__builtin_amdgcn_readfirstlane(kd[te]) & MOGP_KIND_TIMES)) break;
+                    }
+                    if (skip) continue;                      // a row of zero amplitude: the group and every term of its derivative are zero
+                    if (te == t) {
+                        dx_term_radial<DM, DB, false>(acc, one, p, q, L, t, D, d0, __builtin_amdgcn_readfirstlane(kd[t]) & MOGP_KIND_MASK, sh[t], rg, cg);
+                        continue;
+                    }
+                    for (int h = t; h <= te; ++h) {
+                        double prod[4][4];
+#pragma unroll
+                        for (int m = 0; m < 4; ++m)
+#pragma unroll
+                            for (int n = 0; n < 4; ++n) prod[m][n] = 1.0;
+                        for (int f = t; f <= te; ++f)
+                            if (f != h) group_factor_radial<DM, true, 0>(prod, p, q, L, f, D, __builtin_amdgcn_readfirstlane(kd[f]) & MOGP_KIND_MASK, sh[f], rg, cg);
+                        dx_term_radial<DM, DB, true>(acc, prod, p, q, L, h, D, d0, __builtin_amdgcn_readfirstlane(kd[h]) & MOGP_KIND_MASK, sh[h], rg, cg);
+                    }
+                }
+            } else {
+                for (int t = 0; t < nt; ++t) {
+                    if (L.deg[t] == GT_SKIP) continue;
+                    double cu[4], su[4], cw[4], sw[4];
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) {
+                        cu[m] = L.cu[t][rg * 4 + m]; su[m] = L.su[t][rg * 4 + m];
+                        cw[m] = L.cw[t][cg * 4 + m]; sw[m] = L.sw[t][cg * 4 + m];
+                    }
+                    dx_term<DM, DB, ENV>(acc, p, q, L, t, D, d0, cu, su, cw, sw);
+                }
+            }
+        }
+        // block d0 + dd: a thread's four consecutive columns of a row are 32 bytes, sixteen neighbouring lanes cover 512 contiguous bytes of it
+#pragma unroll
+        for (int dd = 0; dd < DB; ++dd) {
+            if (d0 + dd >= D) continue;
+            double* out = a.out + (int64_t)(d0 + dd) * dstride;
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                const int lr = rg * 4 + m;
+                if (lr >= tl.nr) continue;
+                double* o = out + (int64_t)(tl.r0 + lr) * a.ldo + tl.c0 + cg * 4;
+                if (full) {
+                    *reinterpret_cast<d2_t*>(o) = (d2_t){acc[dd][m][0], acc[dd][m][1]};
+                    *reinterpret_cast<d2_t*>(o + 2) = (d2_t){acc[dd][m][2], acc[dd][m][3]};
+                } else {
+#pragma unroll
+                    for (int n = 0; n < 4; ++n)
+                        if (cg * 4 + n < tl.nc) o[n] = acc[dd][m][n];
+                }
+            }
+        }
+    }
+}
+
+// every row block of the Jacobian in one launch: block d at a.out + d * dstride.  The table's kinds must hold no gate, weighted-dot, white or
+// Matern 1/2 row (the caller has refused them: mogp_exact_predict_grad)
+int launch_gram_dx(const GramArgs& a0, int ntiles, int64_t dstride, hipStream_t s) {
+    if (ntiles <= 0) return 0;
+    GramArgs a = a0;
+    if (a.W <= 0) a.W = 2 + 3 * a.D;
+    a.dbg = 0; a.tab_lds = 0;
+    if (a.D < 1 || a.D > MOGP_MAXD) { set_error("launch_gram_dx: input dimension out of range"); return -1; }
+    const bool env = a.W > 2 + 3 * a.D;
+    if (a.kind && (!a.shape || env)) { set_error("launch_gram_dx: kinds without shapes, or with enveloped term rows"); return -1; }
+    if (a.W != 2 + 3 * a.D && a.W != 2 + 5 * a.D) { set_error("launch_gram_dx: table rows of an unknown width"); return -1; }
+    int rc = a.phases_ready ? 0 : launch_phase_tables(a.ph, a.xr, a.ldxr, a.nrows, a.xc, a.ldxc, a.ncols, a.table, a.T, a.D, a.C, a.W, s);
+    if (rc) return rc;
+    if (a.ev0) HIP_TRY(hipEventRecord(a.ev0, s));
+#define DX_LAUNCH(DT, ENV, RAD) hipLaunchKernelGGL((k_gram_dx<DT, ENV, RAD>), dim3(ntiles), dim3(256), 0, s, a, ntiles, dstride)
+    if (a.kind) {
+        switch (a.D) {
+            case 1: DX_LAUNCH(1, false, true); break;
+            case 2: DX_LAUNCH(2, false, true); break;
+            case 3: DX_LAUNCH(3, false, true); break;
+            default: DX_LAUNCH(0, false, true); break;
+        }
+    } else if (env) {
+        switch (a.D) {
+            case 1: DX_LAUNCH(1, true, false); break;
+            case 2: DX_LAUNCH(2, true, false); break;
+            case 3: DX_LAUNCH(3, true, false); break;
+            default: DX_LAUNCH(0, true, false); break;
+        }
+    } else {
+        switch (a.D) {
+            case 1: DX_LAUNCH(1, false, false); break;
+            case 2: DX_LAUNCH(2, false, false); break;
+            case 3: DX_LAUNCH(3, false, false); break;
+            default: DX_LAUNCH(0, false, false); break;
+        }
+    }
+#undef DX_LAUNCH
     if (a.ev1) HIP_TRY(hipEventRecord(a.ev1, s));
     HIP_TRY(hipGetLastError());
     return 0;

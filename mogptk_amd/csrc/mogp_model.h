@@ -544,9 +544,9 @@ int report_not_pd(unsigned long long hinfo, int64_t* info);      // the referenc
 // The test side of a prediction: Xs sorted, uploaded on st with kss_diag (expanded per point) and the (Xs, X) tile list; d_mu sized, K_sf (Spad + extra_rows rows)
 // zero-filled; ga = the Gram K_sf = K(Xs, X), which the caller launches over ts.ntiles tiles.  R > 1 (mogp_exact_predict_parts): R stacked row blocks of Spad
 // rows over the one sorted Xs and tile list -- K_sf, d_mu and the diagonal are sized R Spad (+ extra_rows), kss_diag holds R rows, and the caller launches ga once per
-// block with its table and ga.out moved on by Spad rows
+// block with its table and ga.out moved on by Spad rows.  point_diag: kss_diag holds one value per block and test point whatever the table (mogp_exact_predict_grad)
 struct TestSide { SortedX ss; int64_t Spad = 0; int ntiles = 0; };
-int test_side(mogp_model* m, int64_t S, const double* Xs, const double* kss_diag, int64_t extra_rows, hipStream_t st, TestSide& ts, GramArgs& ga, int R = 1);
+int test_side(mogp_model* m, int64_t S, const double* Xs, const double* kss_diag, int64_t extra_rows, hipStream_t st, TestSide& ts, GramArgs& ga, int R = 1, bool point_diag = false);
 inline void scatter_by_perm(const SortedX& ss, const double* sorted, double* out) { for (int64_t pos = 0; pos < ss.M; ++pos) out[ss.perm[pos]] = sorted[pos]; }   // back to the caller's order
 int moment_pass_device(mogp_model* m, const double* kinv, double ksign);      // gradient moments over this rank's rows of Kj^-1 into d_moments / d_diagG
 int moment_pass(mogp_model* m, const double* kinv, double ksign, double* moments, double* diagG);      // ... and to the host, with a stream sync

@@ -82,6 +82,55 @@ def group_diag_grad(A, kind_row):
     return g
 
 
+PROFILE_PSI0 = {0: 1.0, 1: 1.0, 3: 3.0, 4: 5.0 / 3.0, 6: np.pi ** 2 / 3.0}      # psi(0) = -2 dphi/ds at s = 0: Gaussian, RQ, Matern 3/2, Matern 5/2, sinc
+KIND_NAMES = {2: "Matern 1/2 (exponential)", KIND_GATE: "gate (change-point)", KIND_WDOT: "weighted-dot (FunctionKernel)", KIND_WHITE: "white"}
+
+
+def deriv_diag(table, kind, shape, Xk, D):
+    """kappa (S, D): the prior variance of df/dx_d at every point of Xk (channel column first), kappa_d(x) = d^2 K(x, x')/dx_d dx'_d at x = x'
+    (DESIGN 1f), from the diagonal pair (c, c) of the point's channel.  Each row brings its quadruple (k, d_a k, d_b k, d_a d_b k) at coincident
+    inputs and a product group multiplies them by the product rule -- the cross terms d_a k_h d_b k_g, which vanish unless two point rows share
+    a group, included.  The diagonal pairs carry no delay and no phase (u = 0, theta = 0 at coincident inputs)."""
+    table, Xk = np.asarray(table, dtype=np.float64), np.asarray(Xk, dtype=np.float64)
+    S, env = Xk.shape[0], table.shape[3] > 2 + 3 * D
+    x, ch = Xk[:, 1:1 + D], Xk[:, 0].astype(np.int64)
+    out = np.zeros((S, D))
+    for c in np.unique(ch):
+        rows = np.nonzero(ch == c)[0]
+        xc, tab, kd = x[rows], table[c, c], np.asarray(kind[c, c])
+        if np.any(tab[:, 1][(kd & KIND_MASK) != KIND_DOT] != 0.0) or np.any(tab[:, 2 + 2 * D:2 + 3 * D] != 0.0):
+            raise NotImplementedError("the derivative's prior variance is written for diagonal channel pairs without a delay or a phase")
+        for a, b in group_slices(kd):
+            quad = None
+            for t in range(a, b):
+                r, k = tab[t], int(kd[t]) & KIND_MASK
+                A, V, M = r[0], r[2:2 + D], r[2 + D:2 + 2 * D]
+                if k == KIND_DOT:
+                    n = int(shape[c, c, t])
+                    bb = A * np.sum(xc * xc, axis=1, keepdims=True) + r[1]
+                    p1 = n * bb ** (n - 1) if n > 1 else np.ones_like(bb)
+                    p2 = n * (n - 1) * bb ** (n - 2) if n > 1 else np.zeros_like(bb)
+                    q = (np.broadcast_to(bb ** n, xc.shape), p1 * A * xc, p1 * A * xc, p2 * A * A * xc * xc + p1 * A)
+                elif k == 5:                                # periodic: exp(V_0 (cos theta - 1))
+                    one = np.ones_like(xc)
+                    q = (A * one, 0.0 * one, 0.0 * one, A * V[0] * (2.0 * np.pi * M) ** 2 * one)
+                elif k in PROFILE_PSI0:
+                    kv = A * np.ones((len(rows), 1))
+                    d1, d2 = np.zeros_like(xc), V * PROFILE_PSI0[k] + (2.0 * np.pi * M) ** 2
+                    if env:                                 # the envelope sits on the midpoint: a = x - c at coincident inputs
+                        Lv, mid = r[2 + 3 * D:2 + 4 * D], xc - r[2 + 4 * D:2 + 5 * D]
+                        kv = kv * np.exp(-0.5 * np.sum(Lv * mid * mid, axis=1, keepdims=True))
+                        d1 = -0.5 * Lv * mid * kv
+                        d2 = d2 + 0.25 * (Lv * Lv * mid * mid - Lv)
+                    q = (np.broadcast_to(kv, xc.shape), d1, d1, kv * d2)
+                else:
+                    raise NotImplementedError("a %s row has no derivative on this path" % KIND_NAMES.get(k, "kind-%d" % k))
+                quad = q if quad is None else (quad[0] * q[0], quad[1] * q[0] + quad[0] * q[1], quad[2] * q[0] + quad[0] * q[2],
+                                               quad[3] * q[0] + quad[1] * q[2] + quad[2] * q[1] + quad[0] * q[3])
+            out[rows] += quad[3]
+    return out
+
+
 # One evaluation asks every kernel of a composition for its term table several times (push to the device, then again at each level
 # of the chain rule -- AddKernel even asks only to learn T) while no parameter can change.  A model evaluation opens this cache.
 _TERMS_CACHE = None

@@ -10,7 +10,7 @@ from math import erf, sqrt
 
 from .config import config
 from .parameter import Parameter, ParameterHolder, Softplus, Sigmoid, _STRUCTURE_EPOCH
-from .kernel import Kernel, MulKernel, ChangePointsKernel, terms_cache, KIND_TIMES, KIND_MASK, KIND_DOT, KIND_GATE, KIND_WDOT, group_diag_grad, group_diag, group_slices
+from .kernel import Kernel, MulKernel, ChangePointsKernel, terms_cache, KIND_TIMES, KIND_MASK, KIND_DOT, KIND_GATE, KIND_WDOT, group_diag_grad, group_diag, group_slices, deriv_diag, KIND_WHITE, KIND_NAMES
 from .likelihood import Likelihood, GaussianLikelihood
 from .mean import Mean
 from .multioutput import MultiOutputSpectralMixtureKernel
@@ -833,6 +833,61 @@ class Exact(Model):
         named = self.parts()
         mu, var = self.predict_terms(X, np.stack([m for _, m in named]), full=full)
         return [n for n, _ in named], mu, var
+
+    # -- the posterior of df/dx (mogp_exact_predict_grad) ---------------------------------------------------------------
+    def _mean_slope(self, C):
+        """the slope (C, D) of the mean function, zero without one; a mean that is not affine is refused by name"""
+        if self.mean is None:
+            return np.zeros((C, self._D))
+        table = self._mean_affine()[0] if self._trainable_mean() else None
+        if table is None:
+            name = self.mean.name() if self._trainable_mean() else getattr(self.mean, "__name__", type(self.mean).__name__)
+            raise NotImplementedError("the derivative of the posterior needs the derivative of the mean function, and %s is not affine: only no "
+                                      "mean, ConstantMean, LinearMean and a MultiOutputMean of these have one on this path" % name)
+        return np.asarray(table, dtype=np.float64)[:, 1:1 + self._D]
+
+    def predict_df(self, X):
+        """The posterior of the derivative of the latent function at X: for every input dimension d
+            dmu_d(x*) = j_d(x*)^T Kj^-1 r + dm/dx_d,    dvar_d(x*) = kappa_d(x*) - |L^-1 j_d(x*)|^2,
+        with j_d(x*)_b = dK(x*, x_b)/dx*_d, kappa_d the prior variance of the derivative and Kj, r = y - mean(X) the model's -- one factorisation
+        and one substitution on the device for all dimensions.  -> (dmu, dvar), each (S, D).  No likelihood noise.  There is no covariance
+        between derivatives (it needs the mixed second-derivative Gram).  Refused by name: Matern 1/2 / exponential and white kernels (their
+        sample paths are not differentiable), change-point and FunctionKernel rows (not yet), a mean that is not affine, and the sharded
+        evaluation."""
+        comm = getattr(config, "comm", None)
+        if comm is not None and (comm.world > 1 or comm.force):      # before any device call
+            raise NotImplementedError("the posterior of the derivative is not carried through the sharded exact evaluation (use_distributed): "
+                                      "the row blocks share one factorisation on one device")
+        X = self._check_input(X)
+        with terms_cache():
+            Dd = self._D + sum(k._features() for k in self.kernel._feature_leaves())
+            kind = self.kernel._device_terms(Dd)[1]
+            for k in (2, KIND_WHITE, KIND_GATE, KIND_WDOT):
+                if np.any((kind & KIND_MASK) == k):
+                    raise NotImplementedError("the posterior of the derivative is not defined for a %s row: its sample paths are not differentiable"
+                                              % KIND_NAMES[k] if k in (2, KIND_WHITE) else
+                                              "the posterior of the derivative does not carry a %s row yet" % KIND_NAMES[k])
+            slope = self._mean_slope(kind.shape[0])
+            h, table, D = self._push_terms()
+            kind, shape = self.kernel._device_terms(D)[1:3]
+            Xk = self.kernel._kernel_format(X)
+            kappa = deriv_diag(table, kind, shape, Xk, D)
+        S = Xk.shape[0]
+        step = max(1, self.PART_ROWS // D)
+        dmus, dvars = [], []
+        with self._cholesky_guard():
+            for s0 in range(0, S, step):
+                run = lambda: h.predict_grad(self._noise_var(), self.jitter, np.ascontiguousarray(kappa[s0:s0 + step].T), Xk[s0:s0 + step],
+                                             data_var=self.data_variance)
+                dmu, dvar = run()
+                again = self._check_conditioning(h, run)
+                if again is not None:
+                    dmu, dvar = again
+                dmus.append(dmu.T)
+                dvars.append(dvar.T)
+        dmu = (dmus[0] if len(dmus) == 1 else np.concatenate(dmus, axis=0)) + slope[Xk[:, 0].astype(np.int64)]
+        dvar = dvars[0] if len(dvars) == 1 else np.concatenate(dvars, axis=0)
+        return dmu.astype(config.dtype, copy=False), dvar.astype(config.dtype, copy=False)
 
 
 # ---- inducing-point initialisation (reference gpr/model.py:11-69) ---------------------------------------------------

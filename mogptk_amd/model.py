@@ -868,6 +868,21 @@ class Model:
             upper.append([(m + s)[edges[j]:edges[j + 1]] for j in range(len(X))])
         return X, names, mu, lower, upper
 
+    def predict_derivative(self, X=None, sigma=2):
+        """The posterior of the derivative of the latent function with respect to its inputs: how fast each channel changes at X, and whether that
+        change is distinguishable from zero.  Returns (X, dmu, lower, upper), each a list per channel; dmu, lower and upper hold arrays of
+        shape (S_c, D), one column per input dimension, lower / upper = dmu -/+ sigma sqrt(dvar) without likelihood noise.  All values are in
+        the model's TRANSFORMED space and stay there, for the reason `predict_parts` gives: the derivative belongs to the latent function, and
+        `Y_transformer.backward` is neither linear nor applied to a slope; the inputs are the transformed inputs too.  Exact inference only."""
+        if not isinstance(self.gpr, gpr.Exact):
+            raise ValueError("predict_derivative() needs exact inference (mogptk_amd.Exact): %s has no posterior of the derivative" % self.gpr.name())
+        X = self.dataset.get_prediction_data() if X is None else self.dataset._format_X(X)
+        dmu, dvar = self.gpr.predict_df(self._to_kernel_format(X))
+        s = sigma * np.sqrt(dvar)
+        edges = np.cumsum([0] + [Xj.shape[0] for Xj in X])
+        cut = lambda a: [a[edges[j]:edges[j + 1]] for j in range(len(X))]
+        return X, cut(dmu), cut(dmu - s), cut(dmu + s)
+
     def sample(self, X=None, n=None, prior=False, transformed=False):
         """Draws of y at X (the behaviour of reference mogptk/model.py:692-734; the posterior's full covariance comes from the device).  As in
         the reference `prior` is accepted and unused, and the stacked draws are cut into channels along their FIRST axis whatever n is."""
