@@ -239,8 +239,7 @@ static int factorize_finish(mogp_model* m, const GramArgs& ga, double* lml, int6
     std::memcpy(&hinfo, m->h_pin + pl.info, sizeof(hinfo));
     int rc;
     if (hinfo == MOGP_INFO_CHAIN_TIMEOUT) return MOGP_RETRY_NO_CHAIN;      // the caller repeats the evaluation on the launch-per-step chain
-    static const bool fake = std::getenv("MOGP_FAKE_K") && std::atoi(std::getenv("MOGP_FAKE_K")) > 1;    // timing experiment: the numbers are wrong on purpose
-    if (hinfo != big && !fake) {
+    if (hinfo != big) {
         if (info) *info = (int64_t)hinfo;
         // distinguish NaN / Inf in the Gram from a plain indefinite matrix (reference prints which, gpr/model.py:249-252)
         int flag = 0;
@@ -289,10 +288,9 @@ static int factorize(mogp_model* m, const double* noise_var, const double* data_
     m->strip.attach(ga);
     // Dataflow schedule: the first chain kernel and the first panel read the first 512 columns only, so the Gram matrix is built in two
     // launches -- those columns on this stream, the rest on the bulk stream in front of the dataflow kernel, i.e. UNDERNEATH the first chain
-    // kernel (whose 240 us every workgroup of the dataflow kernel used to sit out after the whole Gram build).  MOGP_GRAM_SPLIT=0: one launch.
-    static const bool split_on = !(std::getenv("MOGP_GRAM_SPLIT") && std::atoi(std::getenv("MOGP_GRAM_SPLIT")) == 0);
+    // kernel (whose 240 us every workgroup of the dataflow kernel used to sit out after the whole Gram build).
     // (the prediction's dataflow schedule gains nothing from the split: 45.55 vs 45.59 ms at configs[3], it is throughput-bound)
-    const bool split = split_on && fuse_inverse && flow_enabled(m, m->k) && !m->tiles_head.empty() && !m->tiles_tail.empty() && m->st2;
+    const bool split = fuse_inverse && flow_enabled(m, m->k) && !m->tiles_head.empty() && !m->tiles_tail.empty() && m->st2;
     if (split) {
         GramArgs gh = ga, gt = ga;
         gh.tiles = m->d_tiles_head.p; m->strip_head.attach(gh); gh.ev1 = nullptr;
@@ -347,8 +345,7 @@ static int factorize(mogp_model* m, const double* noise_var, const double* data_
         // on the main stream (highest priority), the matrix solve goes to the all-CU stream of normal priority: the other way round a 4-workgroup leaf waits until the
         // large launch's queued workgroups have drained (titsias.hip found the same in configs[4]); (ii) Kj^-1 = W^T W with W = L^-1 from ONE substitution (every column a
         // backward-stable solve) and one LAUUM-mode product at the matrix cores' rate, instead of a second substitution L^-T W.  42.7 -> 25 ms (profiles/r6_exact_illcond.txt).
-        static const bool acc_aside = !(std::getenv("MOGP_ACC_ASIDE") && std::atoi(std::getenv("MOGP_ACC_ASIDE")) == 0);
-        hipStream_t ms = (plan.want_inverse && m->st2u && acc_aside) ? m->st2u : m->st;
+        hipStream_t ms = (plan.want_inverse && m->st2u) ? m->st2u : m->st;
         if (plan.want_inverse) {
             if (ms != m->st) {
                 while ((int)m->k.inv_ev.size() < 4) { hipEvent_t e; HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); m->k.inv_ev.push_back(e); }
@@ -403,7 +400,7 @@ static int factorize(mogp_model* m, const double* noise_var, const double* data_
     if ((rc = launch_pivot_range(m->k.invd.p, N, m->d_pivots.p, m->st))) return rc;
     HIP_TRY(hipMemcpyAsync(m->h_pin + pl.pivots, m->d_pivots.p, 2 * sizeof(double), hipMemcpyDeviceToHost, m->st));
     HIP_TRY(hipMemcpyAsync(m->h_pin + pl.logdet, m->k.logdet.p, m->nb * sizeof(double), hipMemcpyDeviceToHost, m->st));
-    static const int zz_piece = []() { const char* e = std::getenv("MOGP_D2H_CHUNK"); const int v = e ? std::atoi(e) : 2048; return v > 0 ? v : (1 << 30); }();
+    constexpr int zz_piece = 2048;
     for (int o = 0; o < nzz; o += zz_piece)               // in pieces of 16 KB: see mogp_ctx_create on larger device-to-host copies next to running co-operating kernels
         HIP_TRY(hipMemcpyAsync(m->h_pin + pl.zz + o, m->d_zz.p + o, std::min(zz_piece, nzz - o) * sizeof(double), hipMemcpyDeviceToHost, m->st));
     HIP_TRY(hipMemcpyAsync(m->h_pin + pl.info, m->d_info.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, m->st));
@@ -774,14 +771,11 @@ static int predict_core(mogp_model* m, const double* noise_var, const double* da
     // X L^T = [K_sf ; y^T]  by block columns of 512 (right-looking):  X[:, K] = T[:, K] W_KK^T,  T[:, > K] -= X[:, K] L[> K, K]^T.
     // W_KK = L_KK^-1 of the 512 x 512 diagonal blocks comes from the tile inverses the factorisation leaves behind (wkk.hip).
     if (!flowed) {
-        constexpr int OB = 4, KD = OB * MOGP_TILE;
+        // The factorisation behind this branch is spd_potrf's (factorize takes the dataflow form only with m->rhs_job set, i.e. as_flow, and
+        // spd_potri_flow sets flow_used wherever it succeeds): its outer blocks are these blocks and it has recorded sync_ev[2 kb] for every one.
+        constexpr int OB = MOGP_OUTER, KD = OB * MOGP_TILE;
         const int nouter = (nb + OB - 1) / OB, mt = (int)(Srow / MOGP_TILE);
         Spd& w = m->k;
-        const bool streamed = g_outer == OB && (int)w.sync_ev.size() >= 2 * nouter;     // spd_potrf's outer blocks are these blocks
-        if (!streamed) {                                       // other blocking (MOGP_OUTER override): after the whole factorisation
-            HIP_TRY(hipEventRecord(m->pred_ev[1], m->st));
-            HIP_TRY(hipStreamWaitEvent(sv, m->pred_ev[1], 0));
-        }
         if (w.Wd.n < (size_t)nouter * KD * KD) {             // tiles above the diagonal of a W_KK are never written and must be zero
             if ((rc = w.Wd.ensure((size_t)nouter * KD * KD))) return rc;
             HIP_TRY(hipMemsetAsync(w.Wd.p, 0, (size_t)nouter * KD * KD * sizeof(double), sv));
@@ -789,7 +783,7 @@ static int predict_core(mogp_model* m, const double* noise_var, const double* da
         for (int kb = 0; kb < nouter; ++kb) {
             const int k0 = kb * OB, nk = std::min(OB, nb - k0), k1 = k0 + nk, rem = nb - k1;
             const int64_t c0 = (int64_t)k0 * MOGP_TILE;
-            if (streamed) HIP_TRY(hipStreamWaitEvent(sv, w.sync_ev[2 * kb], 0));             // chain(kb): L[>= K, K] and the tile inverses of block K are final
+            HIP_TRY(hipStreamWaitEvent(sv, w.sync_ev[2 * kb], 0));            // chain(kb): L[>= K, K] and the tile inverses of block K are final
             double* Wk = w.Wd.p + (int64_t)kb * KD * KD;
             if ((rc = launch_wkk(w.A.p + c0 * (Npad + 1), Npad, w.invd.p + (int64_t)k0 * MOGP_TILE * MOGP_TILE, nk, Wk, KD, sv))) return rc;
             GemmArgs g{};

@@ -830,26 +830,7 @@ __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a, int ntiles) {
 // TC = terms a launch may carry (LDS is sized by it); raw rows of a block of 64 points: x | cos_t | sin_t.  Two workgroups per CU: the
 // arithmetic needs ~200 VGPRs, and three or four waves per SIMD bought with spills ran 1.3x / 2x slower.
 #define GS_TC_MAX 8
-// NC = columns per thread: 4 (256 threads, 4 x 4 entries each: ~200 VGPRs, two waves per SIMD) or 2 (512 threads, 4 x 2 entries: under 128 VGPRs,
-// FOUR waves per SIMD -- round 6: the kernel's waves were parked at s_waitcnt / s_barrier 36 % of their cycles with two)
-template <int TC, int NC = 4>
-struct StripLds {
-    static constexpr int NT = 64 * (MOGP_GT / NC) / 4;
-    static constexpr int RAW = 1 + 2 * TC, PF = (RAW * MOGP_GT + NT - 1) / NT;      // PF: prefetch registers per thread
-    // column-side arrays in two planes: a thread's four columns 4 cg .. 4 cg + 3 are two 16-byte reads, and with the points in order lane cg's reads sat
-    // 32 bytes apart -- every fourth lane on the same banks (SQ_LDS_BANK_CONFLICT: 54 % of the kernel's LDS cycles).  Columns 4 cg, 4 cg + 1 at
-    // [2 cg], columns 4 cg + 2, 4 cg + 3 at [CP + 2 cg]: each read is 16 contiguous lanes x 16 bytes.
-    // (NC = 2: a thread's two columns are ONE 16-byte read, 32 lanes x 16 bytes contiguous in the natural order)
-    static constexpr int CP = 36, CL = 72;
-    __device__ static __forceinline__ int cs(int pnt) { return NC == 2 ? pnt : ((pnt & 2) ? CP : 0) + ((pnt >> 2) << 1) + (pnt & 1); }
-    double rowraw[RAW][MOGP_GT];
-    double colraw[2][RAW][CL];
-    double cu[TC][MOGP_GT], su[TC][MOGP_GT], cw[TC][CL], sw[TC][CL];
-    double tab[TC][3];                            // A, V, Delta of the pair's terms
-    double V[TC], s[TC];
-    int deg[TC];
-};
-
+// one term into a thread's 4 x NC entries (NC = 4 is the only width left: the 4 x 2 form on 512 threads went with the two-barrier kernel)
 template <int N, int NC>
 __device__ __forceinline__ void strip_term(double (&acc)[4][NC], const double (&p)[4], const double (&q)[NC], double V, double s,
                                            const double (&cu)[4], const double (&su)[4], const double (&cw)[NC], const double (&sw)[NC]) {
@@ -873,172 +854,20 @@ __device__ __forceinline__ void strip_term(double (&acc)[4][NC], const double (&
     }
 }
 
-template <int TC, int NC>
-__global__ __launch_bounds__(64 * (MOGP_GT / NC) / 4, NC == 2 ? 4 : 2) void k_gram_strip(GramArgs a, const GSeg* __restrict__ segs) {
-    using SL = StripLds<TC, NC>;
-    constexpr int GS_TC = TC, GS_PF = SL::PF, NT = SL::NT, NCG = MOGP_GT / NC;
-    __shared__ SL L;
-    const int tid = threadIdx.x, cg = tid % NCG, rg = tid / NCG;
-    const GSeg sg = segs[blockIdx.x];
-    const int T = a.T, W = a.W;
-    const int ci = sg.pair / a.C, cj = sg.pair - ci * a.C;
-    const PhaseView v = phase_view(a.ph.ws, a.C, T, 1, a.ldxr, a.ldxc);
-    const double* __restrict__ tab = a.table + (size_t)sg.pair * T * W;
-    const int nraw = (1 + 2 * T) * MOGP_GT;
-    // raw row k of a block of points: 0 = input, 1 .. T = cos of term k - 1, T + 1 .. 2 T = sin of term k - 1 - T; LDS slot of row k
-    auto slot = [&](int k) { return k <= T ? k : k - T + GS_TC; };
-
-    for (int e = tid; e < nraw; e += NT) {               // the row block, once per run (rows take the table of the COLUMN channel)
-        const int k = e >> 6, pnt = e & 63;
-        const int64_t gp = sg.r0 + pnt;
-        double val;
-        if (k == 0) val = a.xr[gp];
-        else if (k <= T) val = v.rcs[((size_t)cj * T + (k - 1)) * a.ldxr + gp];
-        else val = v.rsn[((size_t)cj * T + (k - 1 - T)) * a.ldxr + gp];
-        L.rowraw[slot(k)][pnt] = val;
-    }
-    if (tid < 3 * T) { const int t = tid / 3, k = tid - 3 * t; L.tab[t][k] = tab[(size_t)t * W + (k == 0 ? 0 : 2 * k)]; }      // columns 0, 2, 4
-    const double cr = v.rcen[sg.r0], hr = v.rhalf[sg.r0];
-    double pf[GS_PF], cc_n, hc_n;
-    auto col_fetch = [&](int c0) {                        // columns take the table of the ROW channel
-#pragma unroll
-        for (int k5 = 0; k5 < GS_PF; ++k5) {
-            const int e = tid + NT * k5;
-            if (e < nraw) {
-                const int k = e >> 6, pnt = e & 63;
-                const int64_t gp = c0 + pnt;
-                if (k == 0) pf[k5] = a.xc[gp];
-                else if (k <= T) pf[k5] = v.ccs[((size_t)ci * T + (k - 1)) * a.ldxc + gp];
-                else pf[k5] = v.csn[((size_t)ci * T + (k - 1 - T)) * a.ldxc + gp];
-            }
-        }
-        cc_n = v.ccen[c0]; hc_n = v.chalf[c0];
-    };
-    // gfx9 counts loads and stores in ONE counter and the compiler, seeing both kinds pending, waits for all of them (vmcnt(0)): the next
-    // tile's columns go to LDS BEFORE the current tile is stored, so that wait never includes a store just issued.
-    auto col_commit = [&](int b) {
-#pragma unroll
-        for (int k5 = 0; k5 < GS_PF; ++k5) {
-            const int e = tid + NT * k5;
-            if (e < nraw) L.colraw[b][slot(e >> 6)][SL::cs(e & 63)] = pf[k5];
-        }
-    };
-    col_fetch(sg.c0);
-    col_commit(0);
-    double cc = cc_n, hc = hc_n;
-    __syncthreads();
-    if (sg.n > 1) col_fetch(sg.c0 + MOGP_GT);
-    double p[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) p[m] = L.rowraw[0][rg * 4 + m] - cr;
-
-    for (int u = 0; u < sg.n; ++u) {
-        const int b = u & 1, c0 = sg.c0 + u * MOGP_GT;
-        // ---- stage the tile-centred factors: (rows | columns) x term x point ----
-        for (int e = tid; e < 2 * T * MOGP_GT; e += NT) {
-            const int which = e >= T * MOGP_GT, rem = e - which * T * MOGP_GT, t = rem >> 6, pnt = rem & 63;
-            const double A = L.tab[t][0], V = L.tab[t][1], s = (cr - cc) + L.tab[t][2];
-            const double zmax = fabs(V) * hr * hc, es = V * s * s;
-            const double mu = fmax(0.0, fabs(s) - hr - hc), emin = V * mu * mu;
-            const double efac = fabs(V) * (hr * hr + hc * hc + 2.0 * (hr + hc) * fabs(s));
-            int deg;
-            if (A == 0.0 || 0.5 * emin > GT_SKIP_EXPONENT) deg = GT_SKIP;
-            else if (!(zmax <= 0.45) || !(0.5 * es < 600.0) || !(0.5 * efac < 600.0)) deg = GT_GENERAL;
-            else deg = GT_DEGREE(zmax);
-            if (pnt == 0 && which == 0) { L.deg[t] = deg; L.V[t] = V; L.s[t] = s; }
-            if (deg == GT_SKIP) continue;
-            double f = 1.0;
-            if (GRAM_DBG(a, 4)) { L.cu[t][pnt] = 1.0; L.su[t][pnt] = 0.5; L.cw[t][SL::cs(pnt)] = 0.25; L.sw[t][SL::cs(pnt)] = 2.0; continue; }
-            if (which == 0) {
-                if (deg != GT_GENERAL) {
-                    const double pp = L.rowraw[0][pnt] - cr;
-                    f = fast_exp(-0.5 * (V * (fma(pp, pp, s * s) + 2.0 * pp * s)));
-                }
-                f *= A;
-                L.cu[t][pnt] = f * L.rowraw[1 + t][pnt]; L.su[t][pnt] = f * L.rowraw[1 + GS_TC + t][pnt];
-            } else {
-                if (deg != GT_GENERAL) {
-                    const double qq = L.colraw[b][0][SL::cs(pnt)] - cc;
-                    f = fast_exp(-0.5 * (V * (qq * qq - 2.0 * qq * s)));
-                }
-                { const int cp = SL::cs(pnt); L.cw[t][cp] = f * L.colraw[b][1 + t][cp]; L.sw[t][cp] = f * L.colraw[b][1 + GS_TC + t][cp]; }
-            }
-        }
-        __syncthreads();
-        double q[NC], acc[4][NC];
-#pragma unroll
-        for (int n = 0; n < NC; ++n) q[n] = L.colraw[b][0][SL::cs(cg * NC + n)] - cc;
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int n = 0; n < NC; ++n) acc[m][n] = 0.0;
-        for (int t = 0; t < T; ++t) {
-            const int deg = __builtin_amdgcn_readfirstlane(L.deg[t]);
-            if (deg == GT_SKIP || GRAM_DBG(a, 2)) continue;
-            const double V = L.V[t], s = L.s[t];
-            double cu[4], su[4], cw[NC], sw[NC];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) { cu[m] = L.cu[t][rg * 4 + m]; su[m] = L.su[t][rg * 4 + m]; }
-#pragma unroll
-            for (int n = 0; n < NC; ++n) { cw[n] = L.cw[t][SL::cs(cg * NC + n)]; sw[n] = L.sw[t][SL::cs(cg * NC + n)]; }
-            switch (deg) {
-                #define GT_CASE(N) case N: strip_term<N, NC>(acc, p, q, V, s, cu, su, cw, sw); break;
-                GT_DEGREE_CASES(GT_CASE)
-#undef GT_CASE
-                default: strip_term<0, NC>(acc, p, q, V, s, cu, su, cw, sw); break;
-            }
-        }
-        if (u + 1 < sg.n) { col_commit(b ^ 1); cc = cc_n; hc = hc_n; }
-        if (sg.diag && u + 1 == sg.n) {
-            // the run's last tile sits on the matrix diagonal: the general kernel's epilogue for such a tile (gram_store) -- lower part only,
-            // noise + jitter (+ per-point variance) on the diagonal entries
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const int lr = rg * 4 + m;
-                const int64_t r = sg.r0 + lr;
-#pragma unroll
-                for (int n = 0; n < NC; ++n) {
-                    const int lc = cg * NC + n;
-                    if (lc > lr) continue;
-                    double val = acc[m][n];
-                    if (a.noise != nullptr && lc == lr) {
-                        val += a.noise[ci] + a.jitter_abs;
-                        if (a.dvar != nullptr) val += a.dvar[r];
-                    }
-                    a.out[r * a.ldo + c0 + lc] = val;
-                    if (a.out2) a.out2[r * a.ldo + c0 + lc] = val;
-                }
-            }
-        } else if (!(GRAM_DBG(a, 1) && acc[0][0] != 12345.678)) {
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const int64_t at = (int64_t)(sg.r0 + rg * 4 + m) * a.ldo + c0 + cg * NC;
-                double* o = a.out + at;
-#pragma unroll
-                for (int n = 0; n < NC; n += 2) *reinterpret_cast<d2_t*>(o + n) = (d2_t){acc[m][n], acc[m][n + 1]};
-                if (a.out2) {                              // the sparse models' working copy of K_uf (same leading dimension)
-                    double* o2 = a.out2 + at;
-#pragma unroll
-                    for (int n = 0; n < NC; n += 2) *reinterpret_cast<d2_t*>(o2 + n) = (d2_t){acc[m][n], acc[m][n + 1]};
-                }
-            }
-        }
-        __syncthreads();                                   // the next tile's columns are in LDS; this tile's factors are consumed
-        if (u + 2 < sg.n) col_fetch(c0 + 2 * MOGP_GT);
-    }
-}
-
-// ---- strip kernel, second form (round 6): ONE barrier per tile ---------------------------------------------------------------------
-// k_gram_strip above synchronises twice per tile (staged factors written -> read; read -> the buffers are restaged) and its waves were parked at
-// s_waitcnt / s_barrier 36 % of their cycles.  Here the tile-centred factors are double buffered and staged one tile AHEAD: iteration u stages tile
+// ---- the strip kernel (round 6): ONE barrier per tile -------------------------------------------------------------------------------
+// Its first form (k_gram_strip, round 5; removed) synchronised twice per tile (staged factors written -> read; read -> the buffers are restaged) and
+// its waves were parked at s_waitcnt / s_barrier 36 % of their cycles.  Here the tile-centred factors are double buffered and staged one tile AHEAD: iteration u stages tile
 // u + 1 into F[b ^ 1], computes tile u from F[b], commits the columns of tile u + 2 (prefetched an iteration earlier) and the scalars of tile u + 2
 // (degree, centre distance: computed ONCE per tile and term by wave 0, not by every staging item), stores tile u; one barrier; the columns of tile
 // u + 3 are requested behind it.  The 2 T 64 staging items of a tile do not divide over 256 threads for T = 3 (384): the half wave-pair that takes a
 // second item alternates with the tile's parity.  The addresses of the column prefetch and the LDS slots of its commit are per-thread constants,
-// worked out once per run.  Same arithmetic, entry by entry, as k_gram_strip (the same row / column factors, the same polynomial): same bits.
+// worked out once per run.  Same arithmetic, entry by entry, as the first form (the same row / column factors, the same polynomial): same bits.
 template <int TC>
 struct Strip2Lds {
-    static constexpr int RAW = 1 + 2 * TC, PF = (RAW * MOGP_GT + 255) / 256;
+    static constexpr int RAW = 1 + 2 * TC, PF = (RAW * MOGP_GT + 255) / 256;      // PF: prefetch registers per thread
+    // column-side arrays in two planes: a thread's four columns 4 cg .. 4 cg + 3 are two 16-byte reads, and with the points in order lane cg's reads sat
+    // 32 bytes apart -- every fourth lane on the same banks (SQ_LDS_BANK_CONFLICT: 54 % of the first form's LDS cycles).  Columns 4 cg, 4 cg + 1 at
+    // [2 cg], columns 4 cg + 2, 4 cg + 3 at [CP + 2 cg]: each read is 16 contiguous lanes x 16 bytes.
     static constexpr int CP = 36, CL = 72;
     __device__ static __forceinline__ int cs(int pnt) { return ((pnt & 2) ? CP : 0) + ((pnt >> 2) << 1) + (pnt & 1); }
     double rowraw[RAW][MOGP_GT];
@@ -1305,20 +1134,9 @@ int launch_gram(const GramArgs& a0, int ntiles, hipStream_t s, int rows) {
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    static const bool strip_on = !(std::getenv("MOGP_GRAM_STRIP") && std::atoi(std::getenv("MOGP_GRAM_STRIP")) == 0);
-    if (strip_on && a.segs && a.nsegs > 0 && a.D == 1 && a.W == 5 && a.T <= GS_TC_MAX && !a.mirror && (a.ldo & 1) == 0) {
-        static const int strip_nc = []() { const char* e = std::getenv("MOGP_GRAM_NC"); const int v = e ? std::atoi(e) : 4; return v == 2 ? 2 : 4; }();      // MOGP_GRAM_NC=2: 4 x 2 entries per thread on 512 threads (four waves per SIMD; round 6: 148 vs 159 us on one box, 154 vs 146 on another -- not kept as the default)
-        static const bool strip2 = !(std::getenv("MOGP_GRAM_STRIP2") && std::atoi(std::getenv("MOGP_GRAM_STRIP2")) == 0);      // the one-barrier form (k_gram_strip2)
-        if (strip2 && strip_nc == 4) {
-            if (a.T <= 4) hipLaunchKernelGGL((k_gram_strip2<4>), dim3(a.nsegs), dim3(256), 0, s, a, a.segs);
-            else hipLaunchKernelGGL((k_gram_strip2<8>), dim3(a.nsegs), dim3(256), 0, s, a, a.segs);
-        } else if (strip_nc == 2) {
-            if (a.T <= 4) hipLaunchKernelGGL((k_gram_strip<4, 2>), dim3(a.nsegs), dim3(512), 0, s, a, a.segs);
-            else hipLaunchKernelGGL((k_gram_strip<8, 2>), dim3(a.nsegs), dim3(512), 0, s, a, a.segs);
-        } else {
-            if (a.T <= 4) hipLaunchKernelGGL((k_gram_strip<4, 4>), dim3(a.nsegs), dim3(256), 0, s, a, a.segs);
-            else hipLaunchKernelGGL((k_gram_strip<8, 4>), dim3(a.nsegs), dim3(256), 0, s, a, a.segs);
-        }
+    if (a.segs && a.nsegs > 0 && a.D == 1 && a.W == 5 && a.T <= GS_TC_MAX && !a.mirror && (a.ldo & 1) == 0) {
+        if (a.T <= 4) hipLaunchKernelGGL((k_gram_strip2<4>), dim3(a.nsegs), dim3(256), 0, s, a, a.segs);
+        else hipLaunchKernelGGL((k_gram_strip2<8>), dim3(a.nsegs), dim3(256), 0, s, a, a.segs);
         if (a.nrest > 0) {
             a.tiles = a.rest;
             hipLaunchKernelGGL(k_gram<1>, dim3(std::min(a.nrest, 2 * ncu)), dim3(256), dyn, s, a, a.nrest);
@@ -2226,9 +2044,8 @@ int launch_moments(const MomentArgs& a0, hipStream_t s, int rows) {
     }
     if (a.G == nullptr) {
         if (a.ev0) HIP_TRY(hipEventRecord(a.ev0, s));
-        // D = 1 without an envelope, every row this rank's own: the persistent pipelined kernel (MOGP_MOM_X=0: the tile-per-workgroup one)
-        static const bool mx_on = !(std::getenv("MOGP_MOM_X") && std::atoi(std::getenv("MOGP_MOM_X")) == 0);
-        if (mx_on && !env && a.D == 1 && a.W == 5 && a.T <= 4 && a.row_mod <= 1 && a.xc == nullptr) {
+        // D = 1 without an envelope, every row this rank's own: the persistent pipelined kernel
+        if (!env && a.D == 1 && a.W == 5 && a.T <= 4 && a.row_mod <= 1 && a.xc == nullptr) {
             static const int ncu = []() { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256; return pr.multiProcessorCount; }();
             // (the reduction staging of eight terms does not fit in LDS; three terms -- every BASELINE config of the exact model -- get an instantiation of their
             // own: the moments now live in registers across tiles, and five fewer accumulators keep the kernel clear of spills)

@@ -556,12 +556,7 @@ static int launch_gemm_t(const GemmArgs& a, int grid, hipStream_t s) {
     return 0;
 }
 
-int launch_gemm(const GemmArgs& a0, hipStream_t s) {
-    GemmArgs a = a0;
-    // MOGP_FAKE_K=d (measurement only, WRONG results): the 128 x 128-tile launches contract 1/d of their k range -- is an evaluation bound
-    // by what the GEMM streams deliver (time falls with d) or by its dependency chain (it does not)?
-    static const int fake_k = std::getenv("MOGP_FAKE_K") ? std::atoi(std::getenv("MOGP_FAKE_K")) : 0;
-    if (fake_k > 1 && !a.small && a.mode != GM_TASKS && a.K >= 512) a.K = (a.K / fake_k) / GEMM_BK * GEMM_BK;
+int launch_gemm(const GemmArgs& a, hipStream_t s) {
     int grid;
     switch (a.mode) {
         case GM_LOWER: case GM_LAUUM: grid = a.mt * (a.mt + 1) / 2; break;
@@ -590,11 +585,10 @@ int launch_gemm(const GemmArgs& a0, hipStream_t s) {
     }
     // The 128 x 128 tile runs on EIGHT waves (4 x 2 MFMA tiles each, 512 threads, 128 VGPRs): two workgroups per CU as before, but four
     // waves per SIMD instead of two to pick MFMAs from while one waits for LDS, the barrier or its C tile.  Same arithmetic in the same
-    // order (results bit-identical to the four-wave kernel); measured round 3 on one box: rank-512 lower-triangle update 57.3 -> 58.4
-    // TFLOP/s (k-contiguous), 54.7 -> 58.9 (k-major); configs[1] 13.46 -> 12.96 ms, configs[2] 555 -> 546, configs[3] 48.8 -> 47.4.
-    // MOGP_GEMM8=0: the four-wave kernel (4 x 4 MFMA tiles a wave, 224 VGPRs).
-    static const bool eight = !(std::getenv("MOGP_GEMM8") && std::atoi(std::getenv("MOGP_GEMM8")) == 0);
-    if (a.sk_spans > 0 && eight && a.ksplit <= 1 && a.row_mod <= 1 && a.sk_ws && a.sk_flags &&
+    // order (results bit-identical to the four-wave kernel of 4 x 4 MFMA tiles a wave and 224 VGPRs, since removed); measured round 3 on
+    // one box: rank-512 lower-triangle update 57.3 -> 58.4 TFLOP/s (k-contiguous), 54.7 -> 58.9 (k-major); configs[1] 13.46 -> 12.96 ms,
+    // configs[2] 555 -> 546, configs[3] 48.8 -> 47.4.
+    if (a.sk_spans > 0 && a.ksplit <= 1 && a.row_mod <= 1 && a.sk_ws && a.sk_flags &&
         (a.mode == GM_RECT || a.mode == GM_RECT_LOWER || a.mode == GM_LOWER || a.mode == GM_KHI_J || a.mode == GM_KLO_J)) {
         switch (v) {
             case 0: return launch_gemm_sk_t<0, 0>(a, s);
@@ -604,19 +598,11 @@ int launch_gemm(const GemmArgs& a0, hipStream_t s) {
         }
     }
     // (Sixteen waves of 2 x 2 tiles -- eight per SIMD, 64 VGPRs -- spill and read LDS twice as often: 55-56 TFLOP/s, slower than either.)
-    if (eight) {
-        switch (v) {
-            case 0: return launch_gemm_t<0, 0, 4, 2, 4>(a, grid, s);
-            case 1: return launch_gemm_t<0, 1, 4, 2, 4>(a, grid, s);
-            case 2: return launch_gemm_t<1, 0, 4, 2, 4>(a, grid, s);
-            default: return launch_gemm_t<1, 1, 4, 2, 4>(a, grid, s);
-        }
-    }
     switch (v) {
-        case 0: return launch_gemm_t<0, 0, 4, 4>(a, grid, s);
-        case 1: return launch_gemm_t<0, 1, 4, 4>(a, grid, s);
-        case 2: return launch_gemm_t<1, 0, 4, 4>(a, grid, s);
-        default: return launch_gemm_t<1, 1, 4, 4>(a, grid, s);
+        case 0: return launch_gemm_t<0, 0, 4, 2, 4>(a, grid, s);
+        case 1: return launch_gemm_t<0, 1, 4, 2, 4>(a, grid, s);
+        case 2: return launch_gemm_t<1, 0, 4, 2, 4>(a, grid, s);
+        default: return launch_gemm_t<1, 1, 4, 2, 4>(a, grid, s);
     }
 }
 

@@ -112,15 +112,14 @@ void build_rect_tiles(const std::vector<int>& offr, const std::vector<int>& offc
 using namespace mogp;
 
 int StripTiles::build(const std::vector<GTile>& tiles) {
-    static const int maxrun = []() { const char* e = std::getenv("MOGP_STRIP_RUN"); const int v = e ? std::atoi(e) : 0; return v > 0 ? v : 8; }();      // (round 6, with the graded tail and the one-barrier kernel: 103 us at 8 against 105 at 4 and 108 at 6, configs[1])
+    constexpr int maxrun = 8;      // tiles per run (round 6, with the graded tail and the one-barrier kernel: 103 us at 8 against 105 at 4 and 108 at 6, configs[1])
     split_strip_tiles(tiles, maxrun, segs, rest);
     // The hardware hands out workgroups in index order as slots free up: the launch ends when its LAST runs end, so those should be short.  The runs
     // that would be dispatched last (the final `tail` tiles' worth) are cut into single tiles, the `tail` tiles before them into pairs; a list with
     // fewer runs than there are workgroup slots is cut into single tiles altogether (the head launch of the dataflow schedule: 8 column tiles a row).
-    static const int grade = []() { const char* e = std::getenv("MOGP_STRIP_GRADE"); return e ? std::atoi(e) : 1; }();
-    if (grade > 0 && maxrun > 1 && !segs.empty()) {
+    if (!segs.empty()) {
         static const int slots = []() { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 512; return 2 * pr.multiProcessorCount; }();
-        const long tail = (long)grade * slots;
+        const long tail = slots;
         long total = 0;
         for (const GSeg& g : segs) total += g.n;
         std::vector<GSeg> out;
@@ -146,9 +145,6 @@ int StripTiles::build(const std::vector<GTile>& tiles) {
     if (!rest.empty()) HIP_TRY(dev_upload(d_rest.p, rest.data(), rest.size() * sizeof(GTile)));
     return 0;
 }
-
-namespace mogp { int g_outer = 4; }    // outer Cholesky block in tiles (x128 columns); MOGP_OUTER env var overrides (tuning)
-#define MOGP_OUTER g_outer
 
 namespace mogp { int use_device(mogp_ctx* c) { HIP_TRY(hipSetDevice(c->device)); return 0; } }
 
@@ -258,15 +254,13 @@ namespace mogp { void build_trtri_levels(Spd& w) {
 // Measured inside the schedules (round 3, tools/r3_x2.sh): the wide triangular solves of the sparse models -- 782-tile updates that have the
 // chip to themselves -- gain (configs[4] 49.5 -> 47.9 ms); the fused factorisation + inversion and the prediction LOSE (configs[1] 12.9 ->
 // 13.9 ms, configs[3] 47.2 -> 50.4): next to other launches a partly filled round is filled by them anyway, and workgroups that hold their
-// slots four tiles long delay the critical stream's launches.  So: only where the caller asks (GemmArgs::sk_hint).
-// MOGP_SK (experiments): 0 = never; bit 0 = also launches of at least half the slots whose last round would be less than MOGP_SK_FILL
-// percent full; bit 1 = also launches of fewer tiles than a quarter of the slots on the critical stream; bit 2 = every eligible launch.
+// slots four tiles long delay the critical stream's launches.  So: only where the caller asks (GemmArgs::sk_hint), for launches of at least
+// half the slots whose last round would be less than sk_fill percent full.
 namespace mogp { static int stream_k_setup(mogp_model* m, GemmArgs& g, hipStream_t st) {
-    static const int sk_mode = std::getenv("MOGP_SK") ? std::atoi(std::getenv("MOGP_SK")) : 8;        // 8: hinted launches only
-    static const int sk_min = std::getenv("MOGP_SK_MIN") ? std::max(1, std::atoi(std::getenv("MOGP_SK_MIN"))) : 8;       // k blocks per span at least
-    static const int sk_fill = std::getenv("MOGP_SK_FILL") ? std::atoi(std::getenv("MOGP_SK_FILL")) : 60;
+    constexpr int sk_min = 8;        // k blocks per span at least
+    constexpr int sk_fill = 60;
     g.sk_spans = 0;
-    if (!sk_mode || m->no_chain || g.small || g.ksplit > 1 || g.row_mod > 1 || g.K % 16) return 0;
+    if (!g.sk_hint || m->no_chain || g.small || g.ksplit > 1 || g.row_mod > 1 || g.K % 16) return 0;
     if (!(g.mode == GM_RECT || g.mode == GM_RECT_LOWER || g.mode == GM_LOWER || g.mode == GM_KHI_J || g.mode == GM_KLO_J)) return 0;
     mogp_ctx* ctx = m->ctx;
     const int ncu = ctx->ncu > 0 ? ctx->ncu : 256;
@@ -281,13 +275,8 @@ namespace mogp { static int stream_k_setup(mogp_model* m, GemmArgs& g, hipStream
     if (g.mode == GM_KHI_J || g.mode == GM_KLO_J) { long long row = 0; for (int tj = 0; tj < g.nt; ++tj) row += (g.mode == GM_KHI_J ? std::min<long long>(g.K, (long long)(tj + 1) * MOGP_TILE) : g.K - (long long)tj * MOGP_TILE) / 16; tot = row * g.mt; }
     else tot = T * (g.K / 16);
     if (tot <= 0 || tot >= (1ll << 31) || (long long)slots * slots >= (1ll << 31)) return 0;
-    bool want = (sk_mode & 4) != 0;
-    if (((sk_mode & 1) || g.sk_hint) && 2 * T >= slots) {
-        const long long last = T % slots;                       // tiles of the last round
-        if (last != 0 && 100 * last < (long long)sk_fill * slots) want = true;
-    }
-    if ((sk_mode & 2) && st == ctx->st && 4 * T < slots) want = true;
-    if (!want) return 0;
+    const long long last = T % slots;                           // tiles of the last round
+    if (2 * T < slots || last == 0 || 100 * last >= (long long)sk_fill * slots) return 0;
     const long long spans = std::min<long long>(slots, tot / sk_min);
     if (spans < 2) return 0;
     mogp_ctx::SkWs& w = ctx->sk[st];
@@ -341,8 +330,7 @@ namespace mogp { int spd_potrf(mogp_model* m, Spd& w, long long info_base) {
     // Bulk stream: the one masked to everything but the reserved CUs while the serial chain matters -- the chain's small kernels (this
     // stream, all CUs) then find idle CUs instead of sharing one with GEMM waves: 15.9 vs 21.1 ms per evaluation at N = 8192, 74 vs 82 ms
     // for the N = 16384 prediction.  Once the work is flop-bound the 6 % of CUs matter more (sweep at N = 32768: 597 vs 638 ms): all CUs.
-    static const int bound_tiles = std::getenv("MOGP_CHAIN_BOUND") ? std::atoi(std::getenv("MOGP_CHAIN_BOUND")) : MOGP_CHAIN_BOUND_TILES;      // (experiment switch: tile rows up to which the bulk stream stays off the reserved CUs)
-    hipStream_t bulk_q = (w.nb > bound_tiles && m->st2u) ? m->st2u : m->st2;
+    hipStream_t bulk_q = (w.nb > MOGP_CHAIN_BOUND_TILES && m->st2u) ? m->st2u : m->st2;
     // ---- two-level blocked right-looking Cholesky with look-ahead.
     // Outer blocks of MOGP_OUTER tiles.  "chain(kb)" = for each 128-column of the block: leaf (factor + inverse) -> panel =
     // panel * inv(Lkk)^T for ALL rows below -> update of the block's remaining columns (64x64-tile GEMMs: latency-bound).
@@ -350,7 +338,6 @@ namespace mogp { int spd_potrf(mogp_model* m, Spd& w, long long info_base) {
     //   A(kb): the next block's columns, on the critical stream (chain(kb+1) needs them);
     //   B(kb): everything to the right, on the bulk stream, overlapping chain(kb+1).
     // A(kb) and B(kb-1) accumulate into the same tiles, so A(kb) waits for B(kb-1).
-    { const char* e = std::getenv("MOGP_OUTER"); if (e && std::atoi(e) > 0) g_outer = std::atoi(e); }
     const int nb = w.nb;
     const int nouter = (nb + MOGP_OUTER - 1) / MOGP_OUTER;
     while ((int)w.sync_ev.size() < 2 * nouter + 2) {

@@ -185,6 +185,7 @@ struct TrtriLevel {
 
 // dense SPD workspace: A (Npad x Npad, lower) -> L -> W = L^-1 in place; B = scratch, then W^T W
 #define MOGP_CHAIN_BOUND_TILES 160   // up to this many 128-row tiles (N <= 20480) the bulk work stays off the reserved CUs
+#define MOGP_OUTER 4        // outer Cholesky block of spd_potrf in tiles (x128 columns); the prediction's block columns (exact.hip) are these blocks
 #define MOGP_NPANEL 4       // the factorisation may run this many outer blocks ahead of the inverse stream
 struct Spd {
     int64_t Npad = 0;
@@ -278,7 +279,6 @@ struct TitsiasWork {
     SortedX pred_ss;                                    // the test inputs of the last sparse prediction (a = L^-1 Kus in Aus, b in Bus): what
     bool pred_valid = false;                            // mogp_sparse_predict_cov needs for the full covariance K_ss - a^T a + b^T b
     hipEvent_t side_ev[2] = {nullptr, nullptr};         // fork / join of the M x M adjoint chain on a side stream (side_fork / side_join)
-    hipEvent_t prod_ev[2] = {nullptr, nullptr};         // fork / join of the backward part's M x M x N product on the normal-priority stream (titsias.hip)
     DevBuf<int> blk_z, blk_x;                           // [first point, count] of the 64-point blocks of Z and of X (tile_blocks): the slots of
     std::vector<int> hblk_z, hblk_x;                    // the fixed-order reduction of d/dZ (gz_prepare / gz_attach)
     DevBuf<double> gzp;
@@ -296,7 +296,6 @@ struct TitsiasWork {
         Kus.release(); Aus.release(); Bus.release(); zero_col.release(); kslices.release(); nvec.release(); kd_point.release(); red.release();
         blk_z.release(); blk_x.release(); gzp.release(); hblk_z.clear(); hblk_x.clear();
         for (auto& e : side_ev) if (e) { hipError_t r = hipEventDestroy(e); (void)r; e = nullptr; }
-        for (auto& e : prod_ev) if (e) { hipError_t r = hipEventDestroy(e); (void)r; e = nullptr; }
     }
 };
 
@@ -491,10 +490,10 @@ int spd_info_verdict(mogp_model* m, const char* which, unsigned long long hinfo,
 int sparse_timeout_check(mogp_model* m);
 bool chain_enabled(const mogp_model* m);   // chain.hip
 int chain_fallback(mogp_model* m);     // exact.hip: after MOGP_INFO_CHAIN_TIMEOUT -- drain, switch the model to the launch-per-step chain; the caller repeats the evaluation
-// w.A (SPD, lower tiles) -> w.B = its inverse (lower tiles, full diagonal tiles) and *W = L^-1 (lower; in w.A, or in w.Wm on the fused path),
-// w.logdet per tile: POTRF, TRTRI, LAUUM.  MOGP_SPARSE_FUSED=1 takes the fused factorisation + inversion schedule of the exact path
-// (potri.hip) instead -- measured SLOWER for the 16-tile-row systems of configs[4] (52.0 vs 49.9 ms per evaluation: four outer blocks give
-// its streams nothing to overlap), kept as a switch.  A failed factorisation is reported through `info` / MOGP_ENOTPD naming `which`.
+// w.A (SPD, lower tiles) -> w.B = its inverse (lower tiles, full diagonal tiles) and *W = L^-1 (lower; in w.A),
+// w.logdet per tile: POTRF, TRTRI, LAUUM.  (The fused factorisation + inversion schedule of the exact path, potri.hip, was measured SLOWER
+// for the 16-tile-row systems of configs[4] -- 52.0 vs 49.9 ms per evaluation: four outer blocks give its streams nothing to overlap --
+// and is not offered here.)  A failed factorisation is reported through `info` / MOGP_ENOTPD naming `which`.
 int spd_invert(mogp_model* m, Spd& w, const char* which, int64_t* info, const double** W, bool defer_check = false);   // the pivot report of the last factorisation -> MOGP_ENOTPD naming `which`
 // out (Mpad x Mpad, lower tiles) = alpha A B^T over K (leading dimension ldk), K cut into slices so that the launch fills the chip
 int mm_lower_splitk(mogp_model* m, TitsiasWork& t, const double* A, const double* B, double* out, int mt, int64_t Mpad, int64_t ldk, int64_t K,
@@ -534,7 +533,6 @@ int sparse_predict_finish(mogp_model* m, TitsiasWork& t, const SortedX& ss, cons
                           const double* kss_diag, double* mu, double* var);   // sparse_point_stats with a, b = t.Aus, t.Bus
 // The scaffold of the exact path (exact.hip), shared with the sweep / sharded evaluation (shard.hip).
 #define MOGP_RETRY_NO_CHAIN 0x7e7e      // internal return code: a hand-off between workgroups timed out, nothing is wrong with the data (chain_fallback)
-extern int g_outer;                     // outer Cholesky block of spd_potrf in tiles (mogp_api.hip; MOGP_OUTER overrides)
 // An entry point's opening, behind its own argument check: dp/dr of an earlier gradient evaluation ends (its buffer may be overwritten or regrown: mogp_model_fetch 3), device, *info = 0, one_gpu_call
 int begin_call(mogp_model* m, int64_t* info, bool one_gpu);
 // The prologue of an evaluation: argument checks, ensure_system, counters reset, the absolute jitter (relative to the mean diagonal) into jabs, noise / per-point

@@ -149,8 +149,7 @@ int spd_potri_fused(mogp_model* m, Spd& w) {
     const int nouter = (nb + FZ_OB - 1) / FZ_OB;
     const auto t_host0 = std::chrono::steady_clock::now();
     hipStream_t crit = m->st, priv = m->st_priv ? m->st_priv : m->st, bulk = m->st2, inv = m->st3;
-    static const bool split_acc = !(std::getenv("MOGP_ACC_STREAM") && std::atoi(std::getenv("MOGP_ACC_STREAM")) == 0);
-    hipStream_t acc = (m->st4 && split_acc) ? m->st4 : m->st3;
+    hipStream_t acc = m->st4 ? m->st4 : m->st3;
 
     if (w.Wm.n < (size_t)ld * ld) {                      // nothing ever writes above the block diagonal of W: keep it finite
         RC(w.Wm.ensure((size_t)ld * ld));
@@ -212,7 +211,7 @@ int spd_potri_fused(mogp_model* m, Spd& w) {
     //   * device-side hand-offs instead of events on the block cycle (a one-thread kernel raising a flag behind the producer, a spinning
     //     one-wave kernel in front of the consumer): the kernel behind such a gate starts without the cache invalidation the runtime
     //     attaches to a cross-queue wait and reads stale panel rows (wrong pivots from N = 4096 on); and with the GEMM work taken out
-    //     (MOGP_FAKE_K=8, tools/fake_k.py) a block period is 475 us = chain 245 + mini-panel 140 + 90 for three hops and two tiny launches,
+    //     (a build that contracted an eighth of every k range) a block period is 475 us = chain 245 + mini-panel 140 + 90 for three hops and two tiny launches,
     //     so an event costs ~20 us, not the 45-55 us seen on a loaded chip -- those are slots that free in bursts.
     //   * the next block's columns and those of the block after it in ONE launch on the critical stream (high priority, one event fewer):
     //     13.25 vs 12.99 ms -- that launch has to wait for the whole remainder of the previous panel.

@@ -54,14 +54,6 @@ int side_join(mogp_model* m, TitsiasWork& t, hipStream_t side) {
 
 // defer_check: the caller reads the pivot word itself at its next synchronisation (a failed factorisation then runs on with garbage: bounded, harmless)
 int spd_invert(mogp_model* m, Spd& w, const char* which, int64_t* info, const double** W, bool defer_check) {
-    static const bool fused = std::getenv("MOGP_SPARSE_FUSED") && std::atoi(std::getenv("MOGP_SPARSE_FUSED")) != 0;
-    if (fused && w.nb <= 80) {
-        RC(spd_potri_fused(m, w));
-        RC(spd_potri_fused_finish(m, w));
-        if (!defer_check) RC(spd_check_info(m, which, info));
-        *W = w.Wm.p;
-        return 0;
-    }
     RC(spd_potrf(m, w));
     if (!defer_check) RC(spd_check_info(m, which, info));
     RC(spd_trtri(m, w));                                                        // w.A = L^-1
@@ -105,7 +97,7 @@ int spd_info_verdict(mogp_model* m, const char* which, unsigned long long hinfo,
     if (hinfo == MOGP_INFO_CHAIN_TIMEOUT) {
         m->no_chain = true;                                  // gates the chain kernel AND the stream-K launches (mogp_api.hip:stream_k_setup)
         return fail(MOGP_EHIP, "a hand-off between workgroups timed out (chain kernel, chain.hip, or a stream-K GEMM, linalg.hip:k_gemm_sk: the GPU is "
-                               "shared with another process?).  The model has switched both forms off, as MOGP_CHAIN=0 and MOGP_SK=0 do: repeat the call");
+                               "shared with another process?).  The model has switched both forms off (the chain kernel as MOGP_CHAIN=0 does): repeat the call");
     }
     if (hinfo != std::numeric_limits<unsigned long long>::max()) {
         if (info) *info = (int64_t)hinfo;
@@ -122,7 +114,7 @@ int sparse_timeout_check(mogp_model* m) {
     m->no_chain = true;
     return fail(MOGP_EHIP, "a hand-off between workgroups timed out during this evaluation (stream-K GEMM of a triangular solve, linalg.hip:k_gemm_sk, "
                            "or the chain kernel: the GPU is shared with another process?): its result is not valid.  The model has switched both forms "
-                           "off, as MOGP_SK=0 and MOGP_CHAIN=0 do: repeat the call");
+                           "off (the chain kernel as MOGP_CHAIN=0 does): repeat the call");
 }
 
 // mt (mt + 1) / 2 = 136 tiles at configs[4] would leave half the chip idle over K = N: K is cut into ks slices, each slice into a block of
@@ -133,7 +125,6 @@ int mm_lower_splitk(mogp_model* m, TitsiasWork& t, const double* A, const double
     GemmArgs g = make_gemm(A, ldk, 0, B, ldk, 0, out, Mpad, alpha, GM_LOWER, mt, mt, K);
     const int tiles_q = mt * (mt + 1) / 2;
     int ks = 1;
-    static const int ks_env = []() { const char* e = std::getenv("MOGP_SYRK_KS"); return e ? atoi(e) : 0; }();      // > 0: that many slices, slice-major; < 0: |.| slices, one XCD each
     if (tiles_q < 512 && K >= 4096) {
         double best = 1e30;
         for (int c = 1; c <= 16; ++c) {
@@ -143,9 +134,7 @@ int mm_lower_splitk(mogp_model* m, TitsiasWork& t, const double* A, const double
         }
         // (round 4: eight or sixteen slices, each on ONE XCD -- k_gemm: ksplit_xcd, the workgroups that share an L2 then share a k window as well --
         // measured no faster than fifteen slice-major ones, 45.4 vs 45.3 ms at configs[4], although those fetch 12.4 GB for 1.6 GB of v: the product is
-        // not bound by that traffic; kept as a switch)
-        if (ks_env > 0) ks = ks_env;
-        if (ks_env < 0) { ks = -ks_env; g.ksplit_xcd = (ks % 8 == 0); }
+        // not bound by that traffic; no caller sets GemmArgs::ksplit_xcd any more)
     }
     if (ks > 1) {
         if (t.kslices.n < (size_t)ks * Mpad * Mpad) {         // the upper tiles are never written: keep them finite
@@ -242,7 +231,7 @@ int sparse_kuu(mogp_model* m, int64_t M, const double* Z, double jitter, bool wa
     RC(launch_gram(ga, (int)t.n_tuu, m->st));
     RC(launch_pad_identity(t.a.A.p, Mpad, M, Mpad, m->st));
     t.a.keep_L = true;                                                          // the solves need L itself, diagonal tiles included
-    t.a.refine_panels = !(std::getenv("MOGP_REFINE_PANELS") && std::atoi(std::getenv("MOGP_REFINE_PANELS")) == 0);   // K_uu + jitter is ill-conditioned: mogp_api.hip:spd_potrf
+    t.a.refine_panels = true;                                                   // K_uu + jitter is ill-conditioned: mogp_api.hip:spd_potrf
     return 0;
 }
 

@@ -65,8 +65,7 @@ int sweep_block(mogp_model* m, Spd& w, int kb, hipEvent_t* prof, hipEvent_t pane
     const bool ow = m->sh_owned;                                 // owned-rows form (head of this file)
     auto owned = [&](int i) { return rm == 0 || i % rm == rr; };
     // bulk stream: see spd_potrf; a rank of a sharded evaluation updates 1 / sh_n of the rows, so its chain matters at every size
-    static const int force_masked = std::getenv("MOGP_SWEEP_MASKED") ? std::atoi(std::getenv("MOGP_SWEEP_MASKED")) : 0;    // measurement switch
-    hipStream_t q1 = m->st, q2 = (rm == 0 && !force_masked && w.nb > MOGP_CHAIN_BOUND_TILES && m->st2u) ? m->st2u : m->st2;
+    hipStream_t q1 = m->st, q2 = (rm == 0 && w.nb > MOGP_CHAIN_BOUND_TILES && m->st2u) ? m->st2u : m->st2;
     double* A = w.A.p;
     const int k0 = kb * SW_OB, k1 = std::min(k0 + SW_OB, nb), nk = k1 - k0;
     const int64_t Kd = (int64_t)nk * MOGP_TILE;

@@ -152,54 +152,32 @@ static int titsias_eval_impl(mogp_model* m, int64_t M, const double* Z, double s
     double* btb = t.vec.p + 8 * Mpad;             // [Npad]
     double* r = btb + Npad;                       // [Npad]
     // GA = 1/2 L^-T E L^-1 (symmetric), E = 2I - Pq - Qs: T1 = L^-T E in place, then L^-T T1^T, then the lower triangle of the symmetrised half.
-    // M x M only, underneath the M x N work below.  Round 6 (experiment, see prod_aside): the adjoint chain (~70 launches of 4 .. 200 workgroups) stays on the MAIN stream (highest priority) and the
-    // M x M x N product goes to the all-CU stream of normal priority instead -- on a lower-priority side stream (rounds 3 - 5) a 4-workgroup leaf that arrived while the
-    // product's 12 000 workgroups were queued was not dispatched until the product had drained: 12.8 ms for a 67 us kernel in EVERY configs[4] evaluation
-    // (profiles/r5_cfg5_bench_kernel_stats.csv: max 12.9 ms, median 67 us), i.e. the chain ran BEHIND the product, not under it.  MOGP_SIDE_URGENT=1 switches this on.
-    static const bool prod_aside = std::getenv("MOGP_SIDE_URGENT") && std::atoi(std::getenv("MOGP_SIDE_URGENT")) != 0;      // measured: 42.8 vs 40.0 ms -- the chain is hidden, the product and the memory-bound passes behind the chain slow each other by more.  OFF by default
-    // MOGP_SIDE_URGENT=2 (round 6, second session): the two on DISJOINT CUs -- the product on the bulk stream (masked off the reserved CUs), the chain on the private
-    // stream (the reserved CUs only): neither priority nor slots are shared.  Same tiles, same bits.
-    static const int urgent_mode = std::getenv("MOGP_SIDE_URGENT") ? std::atoi(std::getenv("MOGP_SIDE_URGENT")) : 0;
-    const bool disjoint = urgent_mode == 2 && m->st_priv && m->st2;
-    const bool aside = (prod_aside && m->st2u != nullptr) || disjoint;
-    hipStream_t prod_q = disjoint ? m->st2 : m->st2u;
-    hipStream_t side = m->st;
-    if (disjoint) {
-        for (auto& e : t.side_ev) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(t.side_ev[0], m->st));
-        HIP_TRY(hipStreamWaitEvent(m->st_priv, t.side_ev[0], 0));
-        side = m->st_priv;
-    } else if (!aside) RC(side_fork(m, t, &side));
-    // GB = L^-T (R v) / s2, and beta = L^-T t1 riding along: when N is not a multiple of 128 the right-hand side has zero padding columns,
-    // and t1 travels through the blocked solve in the first of them (a vector solve of its own is 2 nb dependent, almost empty launches).
-    // The large product is ENQUEUED before the side chain's ~70 launches, so that a slow host does not hold it back.
+    // M x M only, on the side stream underneath the M x N work below.  Round 6, measured and removed: the adjoint chain (~70 launches of 4 .. 200
+    // workgroups) on the MAIN stream (highest priority) and the M x M x N product on the all-CU stream of normal priority -- on the lower-priority side
+    // stream a 4-workgroup leaf that arrives while the product's 12 000 workgroups are queued is not dispatched until the product has drained, 12.8 ms for
+    // a 67 us kernel in every configs[4] evaluation (profiles/r5_cfg5_bench_kernel_stats.csv), i.e. the chain runs BEHIND the product, not under it: 42.8 vs
+    // 40.0 ms -- the chain is hidden, the product and the memory-bound passes behind the chain slow each other by more.  And the two on DISJOINT CUs (the
+    // product masked off the reserved CUs, the chain on them alone; same tiles, same bits): 40.6 vs 40.4 ms, no gain.
+    hipStream_t side;
+    RC(side_fork(m, t, &side));
+    // GB = L^-T (R v) / s2.  The large product is ENQUEUED before the side chain's ~70 launches, so that a slow host does not hold it back.
     RC(launch_combine(t.R.p, t.q.B.p, nullptr, Mpad, Mpad, 1.0, 1.0, 0.0, m->st));           // R = I - Pq
     // Round 4: GB = (L^-T R) v / s2 -- the M x M solve FIRST (16 block rows of a 2048-column right-hand side), then ONE M x M x N product, instead of
-    // the product followed by the M x N solve (8.6 of configs[4]'s 45 ms).  This is not the explicit-inverse product that cost round 1 its dELBO/dZ:
+    // the product followed by the M x N solve (8.6 of configs[4]'s 45 ms; removed).  This is not the explicit-inverse product that cost round 1 its dELBO/dZ:
     // L^-T R comes from a backward-stable substitution, v is the accurately solved L^-1 B, and the product is the LAST step before the contraction
     // with the kernel derivatives -- no solve behind it amplifies its rounding.  Against the 80-bit truth dELBO/dZ is 2.17e-3 of the tensor off
-    // (M x N solve: 2.37e-3, the reference's fp64: 2.40e-3); kernel gradients 9.6e-9 (9.2e-9).  MOGP_TITSIAS_GB=0: the M x N solve.
-    static const bool gb_first = !(std::getenv("MOGP_TITSIAS_GB") && atoi(std::getenv("MOGP_TITSIAS_GB")) == 0);
-    if (gb_first) RC(trsm_lower(m, t.a.A.p, Mpad, mt, t.R.p, Mpad, Mpad, true));
+    // (M x N solve: 2.37e-3, the reference's fp64: 2.40e-3); kernel gradients 9.6e-9 (9.2e-9).
+    RC(trsm_lower(m, t.a.A.p, Mpad, mt, t.R.p, Mpad, Mpad, true));
     GemmArgs g = make_gemm(t.R.p, Mpad, 0, t.v.p, Npad, 1, t.GB.p, Npad, 1.0 / s2, GM_RECT, mt, nt, Mpad);
     // tiles down the columns: the 64 workgroups an XCD holds are then 64 / mt column blocks of v against all of R (M x M: cache-resident), and v comes
     // in from memory once -- row by row it came in mt times (27 GB fetched at configs[4] for a 1.6 GB panel)
-    static const bool rv_cols = !(std::getenv("MOGP_RV_COLS") && atoi(std::getenv("MOGP_RV_COLS")) == 0);
-    g.col_major = rv_cols ? 1 : 0;
-    if (aside) {
-        for (auto& e : t.prod_ev) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(t.prod_ev[0], m->st));
-        HIP_TRY(hipStreamWaitEvent(prod_q, t.prod_ev[0], 0));
-        RC(gemm_call(m, g, gemm_flops(g, nullptr), prod_q));
-        HIP_TRY(hipEventRecord(t.prod_ev[1], prod_q));        // (the main stream waits for it right in front of the (Z, X) moment pass, its first reader)
-    } else
+    g.col_major = 1;
     RC(gemm_call(m, g, gemm_flops(g, nullptr)));
     RC(launch_combine(t.E.p, t.q.B.p, t.Qs.p, Mpad, Mpad, 2.0, 1.0, 1.0, side));
     RC(adjoint_GA(m, t, 0.5, side));                                            // its diagonal -> dga
-    RC(solve_with_rider(m, t, gb_first ? nullptr : t.GB.p, t1, beta));          // gb_first: GB is finished above, beta alone is solved for
+    RC(solve_with_rider(m, t, nullptr, t1, beta));                              // GB is finished above, beta alone is solved for
     RC(launch_gemv_cols(t.B.p, Npad, Mpad, Npad, beta, btb, t.scratch.p, m->st));                           // B^T beta
     RC(launch_axpby(Npad, 1.0 / (s2 * s2), m->d_y.p, -1.0 / (s2 * s2 * s2), btb, r, m->st));
-    if (aside) HIP_TRY(hipStreamWaitEvent(m->st, t.prod_ev[1], 0));       // GB is there
     const MomentSpec uf{t.GB.p, Npad, beta, r, 1.0, true}, uu{t.GA.p, Mpad, beta, beta, -0.5 / (s2 * s2), true};
     RC(sparse_moments(m, t, sz, &uf, uu, sharded, side));
 

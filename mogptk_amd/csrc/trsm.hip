@@ -298,10 +298,9 @@ static int launch_leaf_t(const double* Lt, int64_t ldl, double* B, int64_t ldb, 
 // are one round of 196 workgroups instead of two rounds of 391) for wide right-hand sides, one wave per workgroup for narrow ones (more CUs)
 template <bool TRANS>
 static int launch_leaf(const double* Lt, int64_t ldl, double* B, int64_t ldb, int64_t ncols, hipStream_t s) {
-    // MOGP_TRSM_LEAF: 0 the LDS-tile kernel of round 3; 7 the matrix-core kernel for wide right-hand sides only; 8 (default) for all of them.
-    // Same bits either way (tools/r4_leaf.sh: the checksum of a configs[4] gradient); configs[4]: 48.3 -> 46.3 ms on one box.
-    static const int form = []() { const char* e = std::getenv("MOGP_TRSM_LEAF"); return e ? atoi(e) : 8; }();
-    if (form >= 7 && ldb * 8 * TS_T < (int64_t)1 << 32 && (ncols >= 65536 || form >= 8)) return launch_leaf_r<TRANS, 4>(Lt, ldl, B, ldb, ncols, s);
+    // The matrix-core kernel for every right-hand side its 32-bit offsets reach, the LDS-tile kernel of round 3 for the rest.  Same bits either
+    // way (the checksum of a configs[4] gradient); configs[4]: 48.3 -> 46.3 ms on one box.
+    if (ldb * 8 * TS_T < (int64_t)1 << 32) return launch_leaf_r<TRANS, 4>(Lt, ldl, B, ldb, ncols, s);
     if (ncols >= 65536) return launch_leaf_t<TRANS, 512>(Lt, ldl, B, ldb, ncols, s);
     return launch_leaf_t<TRANS, 64>(Lt, ldl, B, ldb, ncols, s);
 }

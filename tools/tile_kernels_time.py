@@ -1,6 +1,6 @@
-"""The two tile kernels of the exact path by themselves: Gram build (k_gram_strip) and gradient-moment pass (k_moments_x), HIP events around the kernel inside
+"""The two tile kernels of the exact path by themselves: Gram build (k_gram_strip2) and gradient-moment pass (k_moments_x), HIP events around the kernel inside
 evaluations on the phases schedule (one Gram launch, one moment launch per evaluation), median of `reps`; bytes = the lower triangle 4 N (N + 1).
-usage: python tools/tile_kernels_time.py [N] [C] [Q] [reps]   (environment switches of the kernels apply: MOGP_STRIP_RUN, MOGP_GRAM_NC, ...)"""
+usage: python tools/tile_kernels_time.py [N] [C] [Q] [reps]"""
 import json, os, sys
 import numpy as np
 os.environ.setdefault("MOGP_GRAD_PATH", "phases")
