@@ -272,6 +272,25 @@ int  mogp_exact_predict_parts(mogp_model* m, const double* noise_var, const doub
 int  mogp_exact_predict_grad(mogp_model* m, const double* noise_var, const double* data_var, double jitter,
                              const double* dkss_diag, int64_t S, const double* Xs, double* dmu, double* dvar, int64_t* info);
 
+/* The JOINT posterior covariance of the derivative over all test points and input dimensions: with x*_a, x*_b test points and d, e dimensions
+ *   dcov[a,d,b,e] = Cov(df/dx_d(x*_a), df/dx_e(x*_b) | y) = H_de[a][b] - (L^-1 j_d(x*_a))^T (L^-1 j_e(x*_b)),
+ *   H_de[a][b]    = d^2 K(x_a, x_b)/dx_a,d dx_b,e  on (Xs, Xs), cross-channel pairs included,
+ * j_d, L, Kj, the jitter and dmu exactly those of mogp_exact_predict_grad; no noise.  dcov[a,d,a,d] is that call's dvar -- here from the device's own
+ * H at coincident inputs: this entry takes no dkss_diag.  Per table row, with chi = -2 dpsi/ds beside phi and psi:
+ *   kinds 0, 1, 3, 4, 6   H_de = A [ (delta_de V_d psi - chi V_d u_d V_e u_e + 4 pi^2 M_d M_e phi) cos theta - 2 pi psi (V_d u_d M_e + V_e u_e M_d) sin theta ]
+ *                         (Gaussian rows: phi = psi = chi = E; chi u_d u_e = 0 at r = 0)
+ *   ... with an envelope  -g h_de + 1/2 g_e h_d - 1/2 g_d h_e + 1/4 g_de h,  g the envelope on the midpoint, h the Gaussian row, subscripts u- and m-derivatives
+ *   kind 5 (periodic)     A V_0 (2 pi M)^2 exp(V_0 (cos theta - 1)) (cos theta - V_0 sin^2 theta)
+ *   kind 7 (dot product)  n (n-1) b^(n-2) A^2 x_b,d x_a,e + n b^(n-1) A delta_de        (only H_de[a][b] = H_ed[b][a] holds)
+ *   a product group       sum_h H_h prod_{g != h} k_g + sum_{h != g} (d_a,d k_h)(d_b,e k_g) prod_{f != h, g} k_f
+ * dmu: D x S as mogp_exact_predict_grad returns it.  dcov: (S D) x (S D) in the caller's row order, index ((a D + d) S + b) D + e; symmetric up to rounding.
+ * ONE factorisation and ONE substitution as there, then one launch of the second-derivative Gram over the symmetric tile list of Xs, one product V V^T over
+ * all D S stacked rows and one copy back.  D S <= MOGP_GRAD_COV_ROWS: beyond it MOGP_EINVAL stating the limit.  Refused by name as
+ * mogp_exact_predict_grad refuses: kinds 2, 8, 9 and 10, and a sharded context. */
+#define MOGP_GRAD_COV_ROWS 8192
+int  mogp_exact_predict_grad_cov(mogp_model* m, const double* noise_var, const double* data_var, double jitter,
+                                 int64_t S, const double* Xs, double* dmu, double* dcov, int64_t* info);
+
 /* ---- Titsias sparse variational bound (BASELINE.json configs[4]) ------------------------------------------------ */
 /* replaces Titsias.elbo (gpr/model.py:700-724) and, with MOGP_EVAL_GRAD, the autograd backward of gpr.Model.loss():
  *   Z: M x (1+D) inducing inputs (channel id in column 0), sigma: SCALAR noise scale (gpr/model.py:686-689),

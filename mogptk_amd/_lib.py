@@ -65,6 +65,7 @@ SIGNATURES = {
     "mogp_exact_predict_parts": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.c_double, ctypes.c_int, c_dp, c_dp, ctypes.c_int64, c_dp,
                                                 ctypes.c_int, c_dp, c_dp, c_i64p]),
     "mogp_exact_predict_grad": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.c_double, c_dp, ctypes.c_int64, c_dp, c_dp, c_dp, c_i64p]),
+    "mogp_exact_predict_grad_cov": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.c_double, ctypes.c_int64, c_dp, c_dp, c_dp, c_i64p]),
     "mogp_titsias_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_dp, ctypes.c_double, ctypes.c_double, c_dp, ctypes.c_int,
                                          c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_i64p]),
     "mogp_titsias_fetch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_dp]),
@@ -555,15 +556,27 @@ class ExactHandle:
         check(code, info.value)
         return mu.reshape(P, S, 1), (var if full else var.reshape(P, S, 1))
 
-    def predict_grad(self, noise_var, jitter, dkss_diag, Xs, data_var=None):
+    def predict_grad(self, noise_var, jitter, dkss_diag, Xs, data_var=None, full=False):
         """the posterior of df/dx_d at the test points behind one factorisation (mogp_exact_predict_grad): dkss_diag (D, S) the prior variance
         kappa_d of the derivative per input dimension and test point -> dmu (D, S), dvar (D, S); no noise, no mean.  Never sharded, and no row
-        of kind 2, 8, 9 or 10 (gpr.Exact refuses before it gets here; the library refuses again)"""
+        of kind 2, 8, 9 or 10 (gpr.Exact refuses before it gets here; the library refuses again).
+        full (mogp_exact_predict_grad_cov): the joint covariance of all derivatives -> dmu (D, S), dcov (S, D, S, D); dkss_diag is None (the
+        diagonal is the device's own second-derivative Gram), D * S <= GRAD_COV_ROWS"""
         noise_var = _f64(noise_var)
         data_var = _f64(data_var)
-        dkss_diag = _f64(dkss_diag)
         Xs = _f64(Xs)
         S = Xs.shape[0]
+        if full:
+            if dkss_diag is not None:
+                raise ValueError("the joint covariance takes no dkss_diag: its diagonal comes from the device")
+            dmu = np.empty((self.D, S))
+            dcov = np.empty((S, self.D, S, self.D))
+            info = ctypes.c_int64(0)
+            code = lib().mogp_exact_predict_grad_cov(self._h, _dp(noise_var), _dp(data_var), float(jitter), S, _dp(Xs), _dp(dmu), _dp(dcov),
+                                                     ctypes.byref(info))
+            check(code, info.value)
+            return dmu, dcov
+        dkss_diag = _f64(dkss_diag)
         if dkss_diag.shape != (self.D, S):
             raise ValueError("dkss_diag must be (D, S): one row per input dimension, one value per test point")
         dmu = np.empty((self.D, S))

@@ -691,7 +691,9 @@ int mogp_model_loo_bytes(mogp_model* m, int64_t* bytes) {
 // substitution; kss_diag, mu and var then hold R rows.  psi_same[p] (p >= 1): table p has the Psi column of table p - 1, so its launch keeps the phase tables.
 // The row blocks of a call are one of two descriptions.  tables != null: block p is the Gram from table p (above).  jacobian (mogp_exact_predict_grad):
 // block d is the Jacobian dK(Xs, X)/dx*_d of the model's OWN table in input dimension d, R = D, all blocks written by ONE launch (gram.hip:k_gram_dx); kss_diag
-// then holds one value per block and test point whatever the table (D x S, caller order), and there is no full covariance.
+// then holds one value per block and test point whatever the table (D x S, caller order).  `full` with Jacobian blocks (mogp_exact_predict_grad_cov):
+// `var` is the joint covariance of all D S derivatives, H - V V^T over the D Spad stacked rows, index ((a D + d) S + b) D + e; kss_diag is then not read
+// by the result (the diagonal comes from the device's own H).
 struct RowBlocks { int R; const double* tables; const char* psi_same; bool jacobian; };
 static int predict_core(mogp_model* m, const double* noise_var, const double* data_var, double jitter,
                         const double* kss_diag, int64_t S, const double* Xs, int full,
@@ -701,7 +703,7 @@ static int predict_core(mogp_model* m, const double* noise_var, const double* da
     const int R = blocks ? blocks->R : 1;
     const bool jac = blocks && blocks->jacobian;
     const RowBlocks* parts = blocks && blocks->tables ? blocks : nullptr;      // blocks that bring tables of their own
-    if (jac && (full || mean_w)) return fail(MOGP_EINVAL, "predict_core: Jacobian row blocks have no full covariance and no mean weights");
+    if (jac && mean_w) return fail(MOGP_EINVAL, "predict_core: Jacobian row blocks have no mean weights");
     const size_t tab_n = (size_t)m->C * m->C * m->T * m->Wt;
     // Cholesky factor only: the predictive equations need V = L^-1 K_fs and z = L^-1 y, never L^-1 itself (reference gpr/model.py:470-472 solves).
     // Round 1 / 2a formed W = L^-1 (N^3/3 flop) and multiplied; here [V | z] comes from ONE blocked forward substitution, N^2 (S+1) flop,
@@ -833,6 +835,38 @@ static int predict_core(mogp_model* m, const double* noise_var, const double* da
     std::vector<GTile> st_tiles;
     std::vector<int> ps;
     build_sym_tiles(ss.off, C, st_tiles, ps);
+    if (jac) {
+        // the joint covariance of the derivative: H (every (d, e) block from ONE launch of k_gram_dxdx) less ONE product V V^T over all D Spad rows
+        const size_t HH = (size_t)Sall * Sall;
+        if ((rc = m->d_Kss.ensure(HH))) return rc;
+        if ((rc = m->d_ptiles.ensure(st_tiles.size()))) return rc;
+        HIP_TRY(hipMemsetAsync(m->d_Kss.p, 0, HH * sizeof(double), m->st));
+        HIP_TRY(hipMemcpyAsync(m->d_ptiles.p, st_tiles.data(), st_tiles.size() * sizeof(GTile), hipMemcpyHostToDevice, m->st));
+        ga.tiles = m->d_ptiles.p; ga.xc = m->d_xs.p; ga.ldxc = Spad; ga.ncols = S; ga.out = m->d_Kss.p; ga.ldo = Sall; ga.mirror = 0;
+        if ((rc = m->ph_ss.prepare(ss.off, ss.off, C, m->T, Spad, Spad, m->st, ga.ph))) return rc;
+        if ((rc = launch_gram_dxdx(ga, (int)st_tiles.size(), Spad, m->st))) return rc;
+        GemmArgs c{};
+        c.A = m->d_Vt.p; c.lda = Npad; c.a_kmajor = 0; c.B = c.A; c.ldb = Npad; c.b_kmajor = 0;
+        c.C = m->d_Kss.p; c.ldc = Sall; c.alpha = -1.0; c.beta = 1.0;
+        c.mode = GM_RECT; c.mt = c.nt = (int)(Sall / MOGP_TILE); c.K = (int)Npad; c.tasks = nullptr; c.ntasks = 0;
+        if ((rc = gemm_call(m, c, gemm_flops(c, nullptr)))) return rc;
+        std::vector<double> hc(HH);
+        HIP_TRY(hipMemcpyAsync(hc.data(), m->d_Kss.p, HH * sizeof(double), hipMemcpyDeviceToHost, m->st));
+        if ((rc = mark(m, 5))) return rc;
+        HIP_TRY(hipStreamSynchronize(m->st));
+        if ((rc = factorize_finish(m, gaK, nullptr, info))) return retry_on_streams(m, rc, again);
+        collect_timing(m, 5);
+        for (int d = 0; d < R; ++d) {
+            scatter_by_perm(ss, hmu.data() + d * Spad, mu + d * S);
+            for (int64_t a = 0; a < S; ++a)
+                for (int e = 0; e < R; ++e) {
+                    const double* row = hc.data() + ((size_t)d * Spad + a) * Sall + (size_t)e * Spad;
+                    double* out = var + ((size_t)ss.perm[a] * R + d) * S * R + e;
+                    for (int64_t b = 0; b < S; ++b) out[(size_t)ss.perm[b] * R] = row[b];
+                }
+        }
+        return MOGP_OK;
+    }
     const size_t SS = (size_t)Spad * Spad;
     if ((rc = m->d_Kss.ensure(R * SS))) return rc;
     if ((rc = m->d_ptiles.ensure(st_tiles.size()))) return rc;
@@ -922,6 +956,30 @@ int mogp_exact_predict_grad(mogp_model* m, const double* noise_var, const double
         }
     const RowBlocks blocks{m->D, nullptr, nullptr, true};
     return predict_core(m, noise_var, data_var, jitter, dkss_diag, S, Xs, 0, dmu, dvar, info, nullptr, &blocks);
+}
+
+// The joint posterior covariance of df/dx over all test points and dimensions: mogp_exact_predict_grad's row blocks, factorisation and substitution,
+// then H = d^2 K(Xs, Xs)/dx dx' from one launch of k_gram_dxdx less one product V V^T.  No dkss_diag: the diagonal is the device's own H at coincident inputs.
+int mogp_exact_predict_grad_cov(mogp_model* m, const double* noise_var, const double* data_var, double jitter,
+                                int64_t S, const double* Xs, double* dmu, double* dcov, int64_t* info) {
+    if (!m || !Xs || !dmu || !dcov || S <= 0) return fail(MOGP_EINVAL, "mogp_exact_predict_grad_cov: bad argument (null pointer or S <= 0)");
+    if (m->T <= 0) return fail(MOGP_EINVAL, "mogp_model_set_terms must be called before an evaluation");
+    if (m->ctx->comm.kind != MOGP_COMM_NONE && m->ctx->comm.n > 1) return fail(MOGP_EINVAL, "mogp_exact_predict_grad_cov: not sharded (the handle's context has a communicator of more than one rank)");
+    if ((int64_t)m->D * S > MOGP_GRAD_COV_ROWS)
+        return fail(MOGP_EINVAL, "mogp_exact_predict_grad_cov: D * S = " + std::to_string((int64_t)m->D * S) + " stacked rows, and the joint covariance is limited to " +
+                                 std::to_string(MOGP_GRAD_COV_ROWS) + " (half a gigabyte on the device and again on the host)");
+    if (m->radial)                                                     // the refusals of mogp_exact_predict_grad, row by row
+        for (size_t k = 0; k < (size_t)m->C * m->C * m->T; ++k) {
+            const int kd = m->hkind[k] & MOGP_KIND_MASK;
+            const std::string row = "row " + std::to_string(k % m->T) + " of pair (" + std::to_string(k / m->T / m->C) + ", " + std::to_string(k / m->T % m->C) + ") is ";
+            if (kd == MOGP_KIND_MATERN12) return fail(MOGP_EINVAL, "mogp_exact_predict_grad_cov: " + row + "a Matern 1/2 (exponential) row (kind 2): its sample paths are not differentiable");
+            if (kd == MOGP_KIND_WHITE) return fail(MOGP_EINVAL, "mogp_exact_predict_grad_cov: " + row + "a white row (kind 10): its sample paths are not differentiable");
+            if (kd == MOGP_KIND_GATE) return fail(MOGP_EINVAL, "mogp_exact_predict_grad_cov: " + row + "a gate row (kind 8): its input derivative is not yet carried on the device");
+            if (kd == MOGP_KIND_WDOT) return fail(MOGP_EINVAL, "mogp_exact_predict_grad_cov: " + row + "a weighted-dot row (kind 9): its input derivative is not yet carried on the device");
+        }
+    const std::vector<double> kappa((size_t)m->D * S, 0.0);            // (test_side uploads a prior diagonal per block; the full covariance does not read it)
+    const RowBlocks blocks{m->D, nullptr, nullptr, true};
+    return predict_core(m, noise_var, data_var, jitter, kappa.data(), S, Xs, 1, dmu, dcov, info, nullptr, &blocks);
 }
 
 // OpperArchambeau.predict_f (reference gpr/model.py:640-668):  mu = K_sf nu,  var = K_ss - K_sf (K + diag(1 / lambda^2))^-1 K_fs, no jitter

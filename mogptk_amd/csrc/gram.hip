@@ -1398,6 +1398,352 @@ int launch_gram_dx(const GramArgs& a0, int ntiles, int64_t dstride, hipStream_t 
     return 0;
 }
 
+// ---- the mixed second derivative of a symmetric Gram -----------------------------------------------------------------------
+// H_de[a][b] = d^2 K(x_a, x_b) / dx_a,d dx_b,e over (Xs, Xs): the prior covariance of df/dx_d(x_a) and df/dx_e(x_b), from which the joint
+// posterior covariance of the derivative subtracts one product (exact.hip: mogp_exact_predict_grad_cov).  With u = x_a - x_b + Delta,
+// theta = 2 pi (M u + Psi), s = sum V u^2 and the three profile functions phi, psi = -2 dphi/ds, chi = -2 dpsi/ds (radial_profile3):
+//   profile rows (0, 1, 3, 4, 6)  k = A phi cos:  k_d  = dk/du_d = A [ -psi V_d u_d cos - 2 pi M_d phi sin ]
+//                                 k_de = A [ (chi V_d u_d V_e u_e - delta_de V_d psi - 4 pi^2 M_d M_e phi) cos + 2 pi psi (V_d u_d M_e + V_e u_e M_d) sin ]
+//                                 d/dx_a,d = k_d,  d/dx_b,e = -k_e,  H_de = -k_de      (Gaussian rows: phi = psi = chi = exp(-s/2))
+//   periodic rows (D = 1)         k = A exp(V (cos - 1)):  k_u = -A V 2 pi M sin E,  H = A V (2 pi M)^2 E (cos - V sin^2)
+//   dot-product rows              k = b^n:  d/dx_a,d = n b^(n-1) A x_b,d,  d/dx_b,e = n b^(n-1) A x_a,e,
+//                                 H_de = n (n-1) b^(n-2) A^2 x_b,d x_a,e + n b^(n-1) A delta_de
+//   enveloped rows                k = g(m) h(u), m the midpoint less the centre, g = exp(-1/2 sum L m^2): d/dx_a = d_u + 1/2 d_m, d/dx_b = -d_u + 1/2 d_m,
+//                                 H_de = -g h_de + 1/2 g_e h_d - 1/2 g_d h_e + 1/4 g_de h,  g_d = -L_d m_d g,  g_de = (L_d m_d L_e m_e - delta_de L_d) g
+//   a product group               the product rule carried FORWARD over the group's rows: with (P, Pa, Pb, Pab) the product so far, its two first
+//                                 derivatives and its mixed one, a row (k, ka, kb, kab) makes Pab <- Pab k + Pa kb + Pb ka + P kab, Pa <- Pa k + P ka,
+//                                 Pb <- Pb k + P kb, P <- P k -- sum_h H_h prod k_g + sum_{h != g} (d_a k_h)(d_b k_g) prod k_f term by term, every row
+//                                 evaluated once and nothing ever divided out.  A row on its own is a group of one.
+// One 64 x 64 tile of the SYMMETRIC tile list per workgroup (lower tiles only), 4 x 4 entries per thread, staged by tile_context / stage_chunk
+// without the tile-centred split, ONE (d, e) pair per pass: D^2 passes over the terms.  The output is ONE (D Spad) x (D Spad) matrix, block
+// (d, e) at row offset d * bstride and column offset e * bstride.  A tile of the matrix diagonal (GT_DIAG) holds both triangles of its 64 x 64
+// entries and is stored once; any other tile is stored twice, as H_de[a][b] and -- by H_de[a][b] = H_ed[b][a] -- transposed into block (e, d)
+// at [b][a].  Every element of the matrix is written exactly once: a plain launch, no flags, no atomics.  A group is walked row of entries
+// by row of entries (m outermost), so the recurrence keeps 16 values for four entries, not 64 for sixteen.
+
+// phi, psi = -2 dphi/ds and chi = -2 dpsi/ds of the kinds the derivative carries (Matern 1/2 never gets here).  The only singular one is
+// Matern 3/2 at s = 0 (chi = 9 exp(-r) / r): there chi is RETURNED as 0, the limit of the only product it enters (chi u_d u_e = O(r)).
+__device__ __forceinline__ void radial_profile3(int kind, double shape, double s, double& phi, double& psi, double& chi) {
+    s = fmax(s, 0.0);
+    switch (kind) {
+        case MOGP_KIND_RQ: {
+            const double b = fma(s, 0.5 / shape, 1.0), ib = 1.0 / b;
+            phi = exp(-shape * log(b));
+            psi = phi * ib;
+            chi = ((shape + 1.0) / shape) * psi * ib;
+        } break;
+        case MOGP_KIND_MATERN32: {
+            const double r = sqrt(3.0 * s), e = exp(-r);
+            phi = fma(r, e, e);
+            psi = 3.0 * e;
+            chi = r > 0.0 ? 9.0 * e / r : 0.0;
+        } break;
+        case MOGP_KIND_MATERN52: {
+            const double r = sqrt(5.0 * s), e = exp(-r);
+            phi = fma(r, r, 3.0 * (1.0 + r)) * (e * (1.0 / 3.0));
+            psi = (5.0 / 3.0) * fma(r, e, e);
+            chi = (25.0 / 3.0) * e;
+        } break;
+        case MOGP_KIND_SINC: {
+            // chi = (3 psi - pi^2 phi) / s = 2 pi^4 sum_j (-x)^j (j + 1)(2j + 4) / (2j + 5)!,  x = pi^2 s  (chi(0) = pi^4 / 15).  The series below
+            // x = 1 (first neglected term 10 * 22 x^9 / 23! < 1e-20 beside 1 / 30); above it the closed forms, where 3 psi - pi^2 phi has lost at
+            // most log2(15 / x) < 4 bits more than psi.  phi and psi exactly as radial_profile<true> has them.
+            const double x = 9.869604401089358 * s;
+            if (x <= 1.0) {
+                double a = 2.8114572543455206e-15;                       // 1 / 17!
+                a = fma(-x, a, 7.6471637318198164e-13);                 // 1 / 15!
+                a = fma(-x, a, 1.6059043836821613e-10);                 // 1 / 13!
+                a = fma(-x, a, 2.505210838544172e-08);                  // 1 / 11!
+                a = fma(-x, a, 2.7557319223985893e-06);                 // 1 / 9!
+                a = fma(-x, a, 1.984126984126984e-04);                  // 1 / 7!
+                a = fma(-x, a, 8.333333333333333e-03);                  // 1 / 5!
+                a = fma(-x, a, 1.6666666666666666e-01);                 // 1 / 3!
+                phi = fma(-x, a, 1.0);
+                double b = 4.4983316069528329e-14;                       // 16 / 17!
+                b = fma(-x, b, 1.0706029224547743e-11);                 // 14 / 15!
+                b = fma(-x, b, 1.9270852604185937e-09);                 // 12 / 13!
+                b = fma(-x, b, 2.505210838544172e-07);                  // 10 / 11!
+                b = fma(-x, b, 2.2045855379188714e-05);                 // 8 / 9!
+                b = fma(-x, b, 1.1904761904761906e-03);                 // 6 / 7!
+                b = fma(-x, b, 3.3333333333333333e-02);                 // 4 / 5!
+                b = fma(-x, b, 3.3333333333333331e-01);                 // 2 / 3!
+                psi = 9.869604401089358 * b;
+                double c = 3.5231792294250488e-18;                       // 9 * 20 / 21!
+                c = fma(-x, c, 1.1837882210868172e-15);                 // 8 * 18 / 19!
+                c = fma(-x, c, 3.1487144778081596e-13);                 // 7 * 16 / 17!
+                c = fma(-x, c, 6.4236175347286462e-11);                 // 6 * 14 / 15!
+                c = fma(-x, c, 9.6354263020929683e-09);                 // 5 * 12 / 13!
+                c = fma(-x, c, 1.0020843354176688e-06);                 // 4 * 10 / 11!
+                c = fma(-x, c, 6.6137566137566142e-05);                 // 3 * 8 / 9!
+                c = fma(-x, c, 2.3809523809523812e-03);                 // 2 * 6 / 7!
+                c = fma(-x, c, 3.3333333333333333e-02);                 // 1 * 4 / 5!
+                chi = 2.0 * 97.409091034002437 * c;                      // 2 pi^4
+            } else {
+                const double r = sqrt(s);
+                double sn, cs;
+                sincospi(r, &sn, &cs);
+                phi = sn / (3.14159265358979323846 * r);
+                psi = (phi - cs) / s;
+                chi = fma(3.0, psi, -9.869604401089358 * phi) / s;
+            }
+        } break;
+        default:
+            phi = exp(-0.5 * s);
+            psi = phi;
+            chi = phi;
+            break;
+    }
+}
+
+// x[d] for a d the compiler does not know: a blend over the (few) registers of a specialised instantiation -- an index would send the thread's
+// inputs to scratch --, a plain index in the generic one, whose inputs live there anyway
+template <int DM>
+__device__ __forceinline__ double pick(const double (&x)[DM], int d) {
+    if constexpr (DM <= 3) {
+        double r = 0.0;                                     // (a blend by 0 / 1 weights, exact: a chain of selects is turned back into an index)
+#pragma unroll
+        for (int j = 0; j < DM; ++j) r = fma(x[j], d == j ? 1.0 : 0.0, r);
+        return r;
+    } else {
+        return x[d];
+    }
+}
+
+// (k, d/dx_a,d, d/dx_b,e, d^2/dx_a,d dx_b,e) of the radial row t at the four entries of one thread row: p = the row point, q the four column points
+template <int DM>
+__device__ __forceinline__ void dxdx_row_radial(double (&k)[4], double (&ka)[4], double (&kb)[4], double (&kab)[4], const double (&p)[DM],
+                                                const double (&q)[4][DM], const TileLds<DM>& L, int t, int D, int d, int e, int kind, double shape,
+                                                int lr, int cg) {
+    constexpr double TWO_PI = 6.283185307179586476925286766559;
+    const double* V = L.V[t];
+    const double* s = L.s[t];
+    const double A = L.A[t];
+    if (kind == MOGP_KIND_DOT) {                            // x_a = p + the row centre (L.Kp), x_b = q + the column centre (L.L): dot_row_inner
+        const int n = dot_row_degree(shape);
+        const double c = L.e[t][0], xae = pick<DM>(p, e) + L.Kp[t][e];
+#pragma unroll
+        for (int nn = 0; nn < 4; ++nn) {
+            double ip = 0.0;                                // (dot_row_inner, its loop unrolled by name: an index the compiler keeps sends q to scratch)
+#pragma unroll
+            for (int j = 0; j < DM; ++j)
+                if (j < D) ip = fma(p[j] + L.Kp[t][j], q[nn][j] + L.L[t][j], ip);
+            const double b = fma(A, ip, c), xbd = pick<DM>(q[nn], d) + L.L[t][d];
+            const double b1 = n > 1 ? dot_row_power(b, n - 1) : 1.0, b2 = n > 2 ? dot_row_power(b, n - 2) : 1.0;
+            const double g = (double)n * A * b1;
+            k[nn] = b1 * b;
+            ka[nn] = g * xbd;
+            kb[nn] = g * xae;
+            kab[nn] = (n > 1 ? (double)(n * (n - 1)) * A * A * b2 * xbd * xae : 0.0) + (d == e ? g : 0.0);
+        }
+        return;
+    }
+    const bool per = kind == MOGP_KIND_PERIODIC;
+    const double cu = L.cu[t][lr], su = L.su[t][lr];        // (times the amplitude, but for the periodic row: stage_item_compute)
+    const double md = TWO_PI * L.M[t][d], me = TWO_PI * L.M[t][e], pd = pick<DM>(p, d), pe = pick<DM>(p, e);
+#pragma unroll
+    for (int nn = 0; nn < 4; ++nn) {
+        if ((nn & 1) == 0) __builtin_amdgcn_sched_barrier(0);      // two entries' profiles at a time (see dx_term_radial)
+        const double cw = L.cw[t][cg * 4 + nn], sw = L.sw[t][cg * 4 + nn];
+        const double cc = fma(cu, cw, su * sw), sn = fma(su, cw, -cu * sw);
+        double phi, psi, chi;
+        if (per) {                                          // D = 1: k_u = -A V 2 pi M sin E and k_uu = A V (2 pi M)^2 E (V sin^2 - cos)
+            radial_profile<false>(MOGP_KIND_GAUSS, shape, periodic_s(V[0], cc), phi, psi);
+            const double E = A * phi, ku = -E * V[0] * md * sn;
+            k[nn] = E;
+            ka[nn] = ku;
+            kb[nn] = -ku;
+            kab[nn] = E * V[0] * md * md * (cc - V[0] * sn * sn);
+            continue;
+        }
+        double arg = 0.0;                                   // (radial_s, unrolled by name)
+#pragma unroll
+        for (int j = 0; j < DM; ++j)
+            if (j < D) { const double u = (p[j] - q[nn][j]) + s[j]; arg = fma(V[j] * u, u, arg); }
+        radial_profile3(kind, shape, arg, phi, psi, chi);
+        const double wd = V[d] * ((pd - pick<DM>(q[nn], d)) + s[d]), we = V[e] * ((pe - pick<DM>(q[nn], e)) + s[e]);
+        k[nn] = phi * cc;
+        ka[nn] = -fma(psi * wd, cc, md * phi * sn);
+        kb[nn] = fma(psi * we, cc, me * phi * sn);
+        double h = fma(chi * wd, we, -md * me * phi);
+        if (d == e) h -= V[d] * psi;
+        kab[nn] = -fma(h, cc, psi * fma(wd, me, we * md) * sn);
+    }
+}
+
+// one Gaussian or enveloped term of a table without kinds: acc += H_de at the thread's sixteen entries
+template <int DM, bool ENV>
+__device__ __forceinline__ void dxdx_term(double (&acc)[4][4], const double (&p)[4][DM], const double (&q)[4][DM], const TileLds<DM>& L, int t,
+                                          int D, int d, int e, const double (&cu)[4], const double (&su)[4], const double (&cw)[4], const double (&sw)[4]) {
+    constexpr double TWO_PI = 6.283185307179586476925286766559;
+    const double* V = L.V[t];
+    const double* s = L.s[t];
+    const double md = TWO_PI * L.M[t][d], me = TWO_PI * L.M[t][e];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        __builtin_amdgcn_sched_barrier(0);                  // one row of four library exps at a time (see gram_term_radial)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            const double E = gauss_general<DM>(p[m], q[n], V, s, L.L[t], L.e[t], D);      // (the envelope's g included)
+            const double cc = E * fma(cu[m], cw[n], su[m] * sw[n]), sn = E * fma(su[m], cw[n], -cu[m] * sw[n]);
+            const double wd = V[d] * ((p[m][d] - q[n][d]) + s[d]), we = V[e] * ((p[m][e] - q[n][e]) + s[e]);
+            double h = fma(wd, we, -md * me);
+            if (d == e) h -= V[d];
+            double H = -fma(h, cc, fma(wd, me, we * md) * sn);                            // -g h_de
+            if (ENV) {
+                const double gd = -L.L[t][d] * (0.5 * (p[m][d] + q[n][d]) + L.e[t][d]), ge = -L.L[t][e] * (0.5 * (p[m][e] + q[n][e]) + L.e[t][e]);
+                const double hd = -fma(wd, cc, md * sn), he = -fma(we, cc, me * sn);      // g h_d, g h_e
+                H = fma(0.5 * ge, hd, H);
+                H = fma(-0.5 * gd, he, H);
+                H = fma(0.25 * (gd * ge - (d == e ? L.L[t][d] : 0.0)), cc, H);
+            }
+            acc[m][n] += H;
+        }
+    }
+}
+
+template <int DT, bool ENV, bool RAD>
+__global__ __launch_bounds__(256) void k_gram_dxdx(GramArgs a, int ntiles, int64_t bstride) {
+    static_assert(!(ENV && RAD), "radial rows carry no envelope");
+    constexpr int DM = DT > 0 ? DT : MOGP_MAXD;
+    const int D = DT > 0 ? DT : a.D;
+    const int W = a.W;
+    const int tid = threadIdx.x;
+    const int cg = tid & 15, rg = tid >> 4;
+    if ((int)blockIdx.x >= ntiles) return;
+    const GTile tl = a.tiles[blockIdx.x];
+    const double* tab = a.table + (size_t)tl.pair * a.T * W;
+    const int* kinds = RAD ? a.kind + (size_t)tl.pair * a.T : nullptr;
+    __shared__ TileLds<DM> L;
+    const PhaseView v = phase_view(a.ph.ws, a.C, a.T, D, a.ldxr, a.ldxc);
+    TileCtx<DM> X;
+    double p[4][DM], q[4][DM];
+    tile_context<DM>(X, p, q, tl, D, v, a.xr, a.ldxr, a.xc, a.ldxc, rg, cg);
+    const bool mirror = !(tl.flags & GT_DIAG);
+
+    for (int de = 0; de < D * D; ++de) {
+        const int d = de / D, e = de - d * D;
+        double acc[4][4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int n = 0; n < 4; ++n) acc[m][n] = 0.0;
+        for (int t0 = 0, nt; t0 < a.T; t0 += nt) {
+            if constexpr (RAD) nt = radial_chunk(a.kind, a.T, t0); else nt = min(MOGP_TC, a.T - t0);
+            if (t0 > 0 || de > 0) __syncthreads();           // the chunk before this one has been consumed
+            stage_chunk<DM, true, false, RAD, 0, false>(L, X, tl, tab, W, D, a.C, a.T, t0, nt, v, a.xr, a.ldxr, a.xc, a.ldxc, tid, kinds);
+            __syncthreads();
+            if constexpr (RAD) {
+                const int* kd = kinds + t0;
+                const double* sh = a.shape + (size_t)tl.pair * a.T + t0;
+                for (int t = 0, te; t < nt; t = te + 1) {    // group by group, as k_gram_dx walks them
+                    bool skip = false;
+                    for (te = t;; ++te) {
+                        skip |= L.deg[te] == GT_SKIP;
+                        if (te == nt - 1 || !(__builtin_amdgcn_readfirstlane(kd[te]) & MOGP_KIND_TIMES)) break;
+                    }
+                    if (skip) continue;                      // a row of zero amplitude: the group and every term of its derivatives are zero
+#pragma unroll 1
+                    for (int m = 0; m < 4; ++m) {            // a LOOP over the thread's rows: the row's inputs by an exact 0 / 1 blend, one copy of the group's code
+                        double pm[DM], P[4], Pa[4], Pb[4], Pab[4];
+#pragma unroll
+                        for (int j = 0; j < DM; ++j) {
+                            pm[j] = 0.0;
+#pragma unroll
+                            for (int mm = 0; mm < 4; ++mm) pm[j] = fma(p[mm][j], mm == m ? 1.0 : 0.0, pm[j]);
+                        }
+                        dxdx_row_radial<DM>(P, Pa, Pb, Pab, pm, q, L, t, D, d, e, __builtin_amdgcn_readfirstlane(kd[t]) & MOGP_KIND_MASK, sh[t], rg * 4 + m, cg);
+                        for (int h = t + 1; h <= te; ++h) {
+                            double k[4], ka[4], kb[4], kab[4];
+                            dxdx_row_radial<DM>(k, ka, kb, kab, pm, q, L, h, D, d, e, __builtin_amdgcn_readfirstlane(kd[h]) & MOGP_KIND_MASK, sh[h], rg * 4 + m, cg);
+#pragma unroll
+                            for (int n = 0; n < 4; ++n) {
+                                Pab[n] = fma(Pab[n], k[n], fma(Pa[n], kb[n], fma(Pb[n], ka[n], P[n] * kab[n])));
+                                Pa[n] = fma(Pa[n], k[n], P[n] * ka[n]);
+                                Pb[n] = fma(Pb[n], k[n], P[n] * kb[n]);
+                                P[n] *= k[n];
+                            }
+                        }
+#pragma unroll
+                        for (int mm = 0; mm < 4; ++mm)
+#pragma unroll
+                            for (int n = 0; n < 4; ++n) acc[mm][n] += mm == m ? Pab[n] : 0.0;
+                    }
+                }
+            } else {
+                for (int t = 0; t < nt; ++t) {
+                    if (L.deg[t] == GT_SKIP) continue;
+                    double cu[4], su[4], cw[4], sw[4];
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) {
+                        cu[m] = L.cu[t][rg * 4 + m]; su[m] = L.su[t][rg * 4 + m];
+                        cw[m] = L.cw[t][cg * 4 + m]; sw[m] = L.sw[t][cg * 4 + m];
+                    }
+                    dxdx_term<DM, ENV>(acc, p, q, L, t, D, d, e, cu, su, cw, sw);
+                }
+            }
+        }
+        // block (d, e) at [a][b], and for a tile off the matrix diagonal block (e, d) at [b][a]; rows and columns past the tile's points are not stored
+        double* out = a.out + ((int64_t)d * bstride) * a.ldo + (int64_t)e * bstride;
+        double* outT = a.out + ((int64_t)e * bstride) * a.ldo + (int64_t)d * bstride;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const int lr = rg * 4 + m;
+            if (lr >= tl.nr) continue;
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                const int lc = cg * 4 + n;
+                if (lc >= tl.nc) continue;
+                out[(int64_t)(tl.r0 + lr) * a.ldo + tl.c0 + lc] = acc[m][n];
+                if (mirror) outT[(int64_t)(tl.c0 + lc) * a.ldo + tl.r0 + lr] = acc[m][n];
+            }
+        }
+    }
+}
+
+// H over the symmetric tile list of (xr, xr) (build_sym_tiles; a.xc = a.xr) into the (D bstride)^2 matrix a.out of leading dimension a.ldo.
+// Tables and kinds as launch_gram_dx takes them; noise, dvar, mirror, out2 and the strip lists are not read.
+int launch_gram_dxdx(const GramArgs& a0, int ntiles, int64_t bstride, hipStream_t s) {
+    if (ntiles <= 0) return 0;
+    GramArgs a = a0;
+    if (a.W <= 0) a.W = 2 + 3 * a.D;
+    a.dbg = 0; a.tab_lds = 0;
+    if (a.D < 1 || a.D > MOGP_MAXD) { set_error("launch_gram_dxdx: input dimension out of range"); return -1; }
+    const bool env = a.W > 2 + 3 * a.D;
+    if (a.kind && (!a.shape || env)) { set_error("launch_gram_dxdx: kinds without shapes, or with enveloped term rows"); return -1; }
+    if (a.W != 2 + 3 * a.D && a.W != 2 + 5 * a.D) { set_error("launch_gram_dxdx: table rows of an unknown width"); return -1; }
+    if (a.xc != a.xr || a.ldxc != a.ldxr || a.ldo < a.D * bstride) { set_error("launch_gram_dxdx: not a symmetric launch, or the output is too narrow for D blocks"); return -1; }
+    int rc = a.phases_ready ? 0 : launch_phase_tables(a.ph, a.xr, a.ldxr, a.nrows, a.xc, a.ldxc, a.ncols, a.table, a.T, a.D, a.C, a.W, s);
+    if (rc) return rc;
+    if (a.ev0) HIP_TRY(hipEventRecord(a.ev0, s));
+#define DXDX_LAUNCH(DT, ENV, RAD) hipLaunchKernelGGL((k_gram_dxdx<DT, ENV, RAD>), dim3(ntiles), dim3(256), 0, s, a, ntiles, bstride)
+    if (a.kind) {
+        switch (a.D) {
+            case 1: DXDX_LAUNCH(1, false, true); break;
+            case 2: DXDX_LAUNCH(2, false, true); break;
+            case 3: DXDX_LAUNCH(3, false, true); break;
+            default: DXDX_LAUNCH(0, false, true); break;
+        }
+    } else if (env) {
+        switch (a.D) {
+            case 1: DXDX_LAUNCH(1, true, false); break;
+            case 2: DXDX_LAUNCH(2, true, false); break;
+            case 3: DXDX_LAUNCH(3, true, false); break;
+            default: DXDX_LAUNCH(0, true, false); break;
+        }
+    } else {
+        switch (a.D) {
+            case 1: DXDX_LAUNCH(1, false, false); break;
+            case 2: DXDX_LAUNCH(2, false, false); break;
+            case 3: DXDX_LAUNCH(3, false, false); break;
+            default: DXDX_LAUNCH(0, false, false); break;
+        }
+    }
+#undef DXDX_LAUNCH
+    if (a.ev1) HIP_TRY(hipEventRecord(a.ev1, s));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // ---- gradient moments ---------------------------------------------------------------------------------
 // partial[tile][t][w], w = [ m0 = sum g E cos, m4 = sum g E sin, m1_d = sum g u_d^2 E cos, m2_d = sum g u_d E cos,
 //                           m3_d = sum g u_d E sin ].

@@ -181,6 +181,11 @@ int launch_gram(const GramArgs& a, int ntiles, hipStream_t s, int rows = 0);
 // dK(xr, xc)/dxr_d at a.out + d * dstride, over the tile list of a rectangular launch (no GT_DIAG / GT_MIRROR tiles; noise, dvar, mirror, out2 and
 // the strip lists are not read).  Gaussian and enveloped tables, and kinds 0, 1, 3 - 7 with product groups; the caller refuses every other kind.
 int launch_gram_dx(const GramArgs& a, int ntiles, int64_t dstride, hipStream_t s);
+// The mixed second derivative of a symmetric Gram (gram.hip:k_gram_dxdx): H_de[a][b] = d^2 K(x_a, x_b)/dx_a,d dx_b,e over the tile list of a
+// symmetric launch (build_sym_tiles; a.xc = a.xr), every (d, e) block of ONE (D bstride) x (D bstride) matrix in one launch: block (d, e) at row
+// offset d * bstride, column offset e * bstride of a.out (leading dimension a.ldo >= D bstride).  Lower tiles are computed and mirrored with the
+// (d, e) <-> (e, d) transposition, so both triangles are written.  Tables and kinds as for launch_gram_dx.
+int launch_gram_dxdx(const GramArgs& a, int ntiles, int64_t bstride, hipStream_t s);
 // split a tile list into runs of at most `maxrun` full interior tiles (same pair and row block, consecutive columns) and the rest
 void split_strip_tiles(const std::vector<GTile>& tiles, int maxrun, std::vector<GSeg>& segs, std::vector<GTile>& rest);
 int launch_moments(const MomentArgs& a, hipStream_t s, int rows = 0);

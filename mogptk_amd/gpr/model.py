@@ -850,8 +850,8 @@ class Exact(Model):
         """The posterior of the derivative of the latent function at X: for every input dimension d
             dmu_d(x*) = j_d(x*)^T Kj^-1 r + dm/dx_d,    dvar_d(x*) = kappa_d(x*) - |L^-1 j_d(x*)|^2,
         with j_d(x*)_b = dK(x*, x_b)/dx*_d, kappa_d the prior variance of the derivative and Kj, r = y - mean(X) the model's -- one factorisation
-        and one substitution on the device for all dimensions.  -> (dmu, dvar), each (S, D).  No likelihood noise.  There is no covariance
-        between derivatives (it needs the mixed second-derivative Gram).  Refused by name: Matern 1/2 / exponential and white kernels (their
+        and one substitution on the device for all dimensions.  -> (dmu, dvar), each (S, D).  No likelihood noise.  Their joint covariance is
+        `predict_df_cov`'s.  Refused by name: Matern 1/2 / exponential and white kernels (their
         sample paths are not differentiable), change-point and FunctionKernel rows (not yet), a mean that is not affine, and the sharded
         evaluation."""
         comm = getattr(config, "comm", None)
@@ -888,6 +888,59 @@ class Exact(Model):
         dmu = (dmus[0] if len(dmus) == 1 else np.concatenate(dmus, axis=0)) + slope[Xk[:, 0].astype(np.int64)]
         dvar = dvars[0] if len(dvars) == 1 else np.concatenate(dvars, axis=0)
         return dmu.astype(config.dtype, copy=False), dvar.astype(config.dtype, copy=False)
+
+    # -- the joint covariance of df/dx (mogp_exact_predict_grad_cov) -------------------------------------------------------
+    GRAD_COV_ROWS = 8192       # stacked rows D * S of one joint covariance (MOGP_GRAD_COV_ROWS: half a gigabyte on the device and again on the host)
+
+    def predict_df_cov(self, X):
+        """The posterior of the derivative of the latent function at X with the JOINT covariance of all its components:
+            dcov[a, d, b, e] = Cov(df/dx_d(x*_a), df/dx_e(x*_b) | y) = d^2 K(x*_a, x*_b)/dx_d dx'_e - (L^-1 j_d(x*_a))^T (L^-1 j_e(x*_b)),
+        j_d, L and the mean as `predict_df` has them.  -> (dmu (S, D), dcov (S, D, S, D)), dcov symmetrised on the host; its diagonal is
+        `predict_df`'s dvar.  No likelihood noise.  One device call without chunks: D * S <= GRAD_COV_ROWS.  `predict_df` keeps its one
+        argument -- its callers and its tests rely on there being no other -- so the covariance is a call of its own.  Refused by name as
+        `predict_df` refuses."""
+        comm = getattr(config, "comm", None)
+        if comm is not None and (comm.world > 1 or comm.force):      # before any device call
+            raise NotImplementedError("the posterior of the derivative is not carried through the sharded exact evaluation (use_distributed): "
+                                      "the row blocks share one factorisation on one device")
+        X = self._check_input(X)
+        if self._D * X.shape[0] > self.GRAD_COV_ROWS:                # before any device call
+            raise ValueError("the joint covariance of the derivative is limited to D * S <= %d stacked rows, and D * S = %d * %d = %d"
+                             % (self.GRAD_COV_ROWS, self._D, X.shape[0], self._D * X.shape[0]))
+        with terms_cache():
+            Dd = self._D + sum(k._features() for k in self.kernel._feature_leaves())
+            kind = self.kernel._device_terms(Dd)[1]
+            for k in (2, KIND_WHITE, KIND_GATE, KIND_WDOT):
+                if np.any((kind & KIND_MASK) == k):
+                    raise NotImplementedError("the posterior of the derivative is not defined for a %s row: its sample paths are not differentiable"
+                                              % KIND_NAMES[k] if k in (2, KIND_WHITE) else
+                                              "the posterior of the derivative does not carry a %s row yet" % KIND_NAMES[k])
+            slope = self._mean_slope(kind.shape[0])
+            h, table, D = self._push_terms()
+            Xk = self.kernel._kernel_format(X)
+        with self._cholesky_guard():
+            run = lambda: h.predict_grad(self._noise_var(), self.jitter, None, Xk, data_var=self.data_variance, full=True)
+            dmu, dcov = run()
+            again = self._check_conditioning(h, run)
+            if again is not None:
+                dmu, dcov = again
+        dmu = dmu.T + slope[Xk[:, 0].astype(np.int64)]
+        dcov = 0.5 * (dcov + dcov.transpose(2, 3, 0, 1))
+        return dmu.astype(config.dtype, copy=False), dcov.astype(config.dtype, copy=False)
+
+    def sample_df(self, X, n=None):
+        """Joint draws of the derivative of the latent function at X, built as `sample_f` builds draws of f: torch's MultivariateNormal on
+        `predict_df_cov(X)` -- mean dmu.reshape(-1), covariance dcov.reshape(S D, S D) + jitter * mean(diag) * I -- from torch's global
+        generator.  -> (n, S, D), or (S, D) without n."""
+        from .likelihood import _torch
+        torch = _torch()
+        dmu, dcov = self.predict_df_cov(X)
+        S, D = dmu.shape
+        cov = np.array(dcov, dtype=np.float64).reshape(S * D, S * D)
+        cov += self.jitter * np.mean(np.diagonal(cov)) * np.eye(S * D)
+        dist = torch.distributions.multivariate_normal.MultivariateNormal(torch.tensor(np.reshape(dmu, -1), dtype=torch.float64), torch.tensor(cov))
+        samples = dist.sample([1 if n is None else n]).numpy().reshape(-1, S, D)
+        return samples[0] if n is None else samples
 
 
 # ---- inducing-point initialisation (reference gpr/model.py:11-69) ---------------------------------------------------

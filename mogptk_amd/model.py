@@ -883,6 +883,17 @@ class Model:
         cut = lambda a: [a[edges[j]:edges[j + 1]] for j in range(len(X))]
         return X, cut(dmu), cut(dmu - s), cut(dmu + s)
 
+    def sample_derivative(self, X=None, n=None):
+        """Joint draws of the derivative of the latent function with respect to its inputs (`gpr.Exact.sample_df`: the draws of all channels,
+        points and dimensions share one covariance).  Returns (X, draws), each a list per channel; draws hold arrays of shape (n, S_c, D), or
+        (S_c, D) without n.  In the model's TRANSFORMED space, as `predict_derivative` is.  Exact inference only."""
+        if not isinstance(self.gpr, gpr.Exact):
+            raise ValueError("sample_derivative() needs exact inference (mogptk_amd.Exact): %s has no posterior of the derivative" % self.gpr.name())
+        X = self.dataset.get_prediction_data() if X is None else self.dataset._format_X(X)
+        draws = self.gpr.sample_df(self._to_kernel_format(X), n=n)
+        edges = np.cumsum([0] + [Xj.shape[0] for Xj in X])
+        return X, [draws[..., edges[j]:edges[j + 1], :] for j in range(len(X))]
+
     def sample(self, X=None, n=None, prior=False, transformed=False):
         """Draws of y at X (the behaviour of reference mogptk/model.py:692-734; the posterior's full covariance comes from the device).  As in
         the reference `prior` is accepted and unused, and the stacked draws are cut into channels along their FIRST axis whatever n is."""
