@@ -226,6 +226,31 @@ int  mogp_exact_cv(mogp_model* m, const double* noise_var, const double* data_va
 /* bytes of device memory the handle holds for mogp_exact_loo and mogp_exact_cv alone: 0 until the first call of either (no reference seam) */
 int  mogp_model_loo_bytes(mogp_model* m, int64_t* bytes);
 
+/* The rolling-origin forecast of the exact model: every training point predicted from the points that precede it in an order the caller gives
+ * (time, across all channels), for up to MOGP_FORECAST_MAXH cuts per point in one call, behind ONE factorisation.  No reference seam: mogptk has
+ * no such score -- the formulas are the chain rule of the joint Gaussian density, checked against conditional Gaussians formed directly from Kj
+ * (tests/golden/gen_forecast.py).  order[p]: the caller's row at time position p, a permutation of 0 .. N - 1.  With Kj, r and the targets y as
+ * in mogp_exact_loo, Kj = L L^T factored IN THAT ORDER and z = L^-1 r, every leading block of L is the factor of the leading block of Kj, so for
+ * the cut c = cut[h N + p] in {0 .. p} the predictive of the point at position p given the points at positions 0 .. c - 1 is
+ *   mu  = m_p + sum_{k < c}       L[p, k] z[k]        (m_p = y_p - r_p: the mean table's value, 0 without one),
+ *   var =       sum_{c <= k <= p} L[p, k]^2           (noise and jitter included: a sum of squares, nothing cancels),
+ *   score[h] = sum over the points with cut >= 0 of log N(y_p; mu, var), added up on the host side of the library in time order.
+ * c = 0 is the prior predictive; cut = -1 skips the point (mu, var NaN, no term in the score).  With c = p at every point the scores are the
+ * terms of the chain rule and score[h] is the log marginal likelihood of mogp_exact_eval.  jitter * mean(diag) is that of the WHOLE matrix: these
+ * are conditionals of the one joint Gaussian the LML is the density of, not refits on shorter series.  mu, var: H x N, row h in the CALLER's row
+ * order.  Cost: one Gram build, its symmetric permutation into time order (csrc/forecast.hip; mogp_model_create sorts the storage by channel),
+ * the refined factorisation of mogp_model_set_accurate's form (N^3 / 3), one substitution on a 128-column block and one pass over the rows of
+ * L for all H cuts (N^2 / 2 doubles read once): no inverse.  Repeated calls give identical bits, and H cuts in one call the bits of H calls.
+ * Afterwards the handle is as a prediction leaves it: mogp_model_pivot_range is valid (the pivots of the time-ordered factor),
+ * mogp_model_fetch(0), (1) and (2) have nothing to return; the N x N scratch of the inverse is used for the permutation.  The first call
+ * allocates (3 MOGP_FORECAST_MAXH + 1) N words; they go with the handle.
+ * MOGP_EINVAL by name: H outside 1 .. MOGP_FORECAST_MAXH, an order that is not a permutation (the entry), a cut outside -1 .. p (h and p), a
+ * communicator of more than one rank.  jitter_abs may be NULL.  On MOGP_ENOTPD *info is the 1-based failing pivot IN TIME ORDER. */
+#define MOGP_FORECAST_MAXH 8
+int  mogp_exact_forecast(mogp_model* m, const double* noise_var, const double* data_var, double jitter,
+                         const int64_t* order, int H, const int64_t* cut,
+                         double* score, double* mu, double* var, double* jitter_abs, int64_t* info);
+
 /* replaces Exact.predict_f (gpr/model.py:455-483): mu = Kfs^T Kj^-1 y, var = Kss_diag - colsum((L^-1 Kfs)^2)
  * (full != 0: var is S x S = Kss - v^T v).  Xs: S x (1+D).  mu: S, var: S or S*S.  No noise added to var.
  * kss_diag[C]: the kernel's K_diag value per channel as the reference returns it (gpr/kernel.py:483-495; for SM

@@ -60,6 +60,8 @@ SIGNATURES = {
     "mogp_exact_cv": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.c_double, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64,
                                      c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_i64p]),
     "mogp_model_loo_bytes": (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
+    "mogp_exact_forecast": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.c_double, c_i64p, ctypes.c_int, c_i64p,
+                                           c_dp, c_dp, c_dp, c_dp, c_i64p]),
     "mogp_exact_predict": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.c_double, c_dp, ctypes.c_int64, c_dp,
                                           ctypes.c_int, c_dp, c_dp, c_i64p]),
     "mogp_exact_predict_parts": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.c_double, ctypes.c_int, c_dp, c_dp, ctypes.c_int64, c_dp,
@@ -495,6 +497,24 @@ class ExactHandle:
         if fold.shape != (self.N,):
             raise ValueError("fold must hold one label per training point")
         return self._held_out("cv", lib().mogp_exact_cv, noise_var, jitter, grad, data_var, fold.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(nfolds))
+
+    def forecast(self, noise_var, jitter, order, cut, data_var=None):
+        """the rolling-origin forecast (mogp_exact_forecast): order (N,) the model's row at every time position, cut (H, N) per horizon and time
+        position the number of leading points the prediction may use (-1: skipped) -> dict(score[H], mu[H, N], var[H, N], jitter_abs), mu and
+        var in the model's row order and NaN where skipped; never sharded (gpr.Exact refuses before it gets here)"""
+        noise_var = _f64(noise_var)
+        data_var = _f64(data_var)
+        order = np.ascontiguousarray(order, dtype=np.int64)
+        cut = np.ascontiguousarray(cut, dtype=np.int64)
+        if order.shape != (self.N,) or cut.ndim != 2 or cut.shape[1] != self.N:
+            raise ValueError("order must hold one row per time position and cut one row of N cuts per horizon")
+        H = cut.shape[0]
+        score, mu, var = np.empty(H), np.empty((H, self.N)), np.empty((H, self.N))
+        jit, info = ctypes.c_double(), ctypes.c_int64(0)
+        code = lib().mogp_exact_forecast(self._h, _dp(noise_var), _dp(data_var), float(jitter), order.ctypes.data_as(c_i64p), H,
+                                         cut.ctypes.data_as(c_i64p), _dp(score), _dp(mu), _dp(var), ctypes.byref(jit), ctypes.byref(info))
+        check(code, info.value)
+        return dict(score=score, mu=mu, var=var, jitter_abs=jit.value)
 
     def loo_bytes(self):
         """device memory held for `loo` and `cv` alone (mogp_model_loo_bytes): 0 on a handle that never called either"""

@@ -269,6 +269,7 @@ struct FactorPlan {
     bool defer = false;             // enqueue only -- the scalars travel to the pinned block asynchronously; factorize_finish() (after the caller's ONE stream sync) makes the LML / the failure report of them
     bool want_inverse = true;       // the accurate form: Kj^-1 too (an LML-only evaluation needs L, z and the log-determinant: not the N^2 fill and the N^3 solve nothing would read)
     bool refine = false;            // the factorisation keeps L's diagonal tiles and refines every panel against L_kk (Spd::keep_L, refine_panels); the accurate form implies it
+    const int* gather = nullptr;    // the forecast (forecast.hip): device map [Npad], time position -> storage position -- Kj is factored in THAT order (FactorOnly, refine, no rhs_job; k.B is the scratch of the permutation)
 };
 
 // Gram + factorisation + inverse factor + alpha.  On return d_A holds W = L^-1, d_alpha = Kj^-1 y.
@@ -309,6 +310,12 @@ static int factorize(mogp_model* m, const double* noise_var, const double* data_
     } else {
         if ((rc = launch_gram(ga, (int)m->tiles.size(), m->st, m->radial ? m->gate_kinds : 0))) return rc;
         if ((rc = launch_pad_identity(m->k.A.p, Npad, N, Npad, m->st))) return rc;
+        if (plan.gather) {              // Kj into time order: A -> B through the map, the lower block triangle back into A; spd_potrf then runs as it stands
+            if (!factor_only || !plan.refine || m->rhs_job) return fail(MOGP_EINVAL, "factorize: a gathered factorisation is the refined factor alone, on streams");
+            if ((rc = launch_sym_gather(m->k.A.p, m->k.B.p, Npad, m->nb, N, plan.gather, m->st))) return rc;
+            if ((rc = launch_sym_gather(m->k.B.p, m->k.A.p, Npad, m->nb, N, nullptr, m->st))) return rc;
+            if ((rc = launch_pad_identity(m->k.A.p, Npad, N, Npad, m->st))) return rc;
+        }
     }
     ga.ev0 = ga.ev1 = nullptr;
     if ((rc = mark(m, 1))) return rc;
@@ -319,7 +326,7 @@ static int factorize(mogp_model* m, const double* noise_var, const double* data_
     const PinLayout pl(m);
     if ((rc = pin_ensure(m, pl.total))) return rc;
     if ((rc = m->d_pivots.ensure(2))) return rc;
-    if (m->accurate && (rc = m->acc_rhs.ensure((size_t)Npad * MOGP_TILE))) return rc;
+    if ((m->accurate || plan.gather) && (rc = m->acc_rhs.ensure((size_t)Npad * MOGP_TILE))) return rc;
     m->k.flow_used = false;                           // (mogp_model_schedule reports the LAST evaluation: set again by spd_potri_flow)
     m->flow_ran = false;                              // ... and chain_fallback decides from THIS evaluation which schedule to drop, not from an earlier one
     m->k.want_vec = fuse_inverse;                     // the dataflow schedule (flow.hip) also forms z = W y and alpha = W^T z
@@ -681,6 +688,83 @@ int mogp_exact_cv(mogp_model* m, const double* noise_var, const double* data_var
 int mogp_model_loo_bytes(mogp_model* m, int64_t* bytes) {
     if (!m || !bytes) return fail(MOGP_EINVAL, "mogp_model_loo_bytes: bad argument");
     *bytes = (int64_t)((m->loo.G.n + m->loo.vec.n) * sizeof(double) + cv_bytes(m));
+    return MOGP_OK;
+}
+
+// The rolling-origin forecast: Kj gathered into time order and factored once in the refined form (FactorPlan::gather), r gathered the same way,
+// z = L^-1 r by substitution on a 128-column block as the accurate form has it, ONE pass over the rows of L for every cut (forecast.hip) and the 2 H N sums home
+// through the pinned block behind the call's one wait.  The scores are added up here, in time order.
+int mogp_exact_forecast(mogp_model* m, const double* noise_var, const double* data_var, double jitter, const int64_t* order, int H, const int64_t* cut,
+                        double* score, double* mu, double* var, double* jitter_abs, int64_t* info) {
+    if (!m) return fail(MOGP_EINVAL, "mogp_exact_forecast: model is null");
+    if (!order || !cut || !score || !mu || !var) return fail(MOGP_EINVAL, "mogp_exact_forecast: order, cut, score, mu or var is null");
+    if (H < 1 || H > MOGP_FORECAST_MAXH) return fail(MOGP_EINVAL, "mogp_exact_forecast: H = " + std::to_string(H) + " cuts per point, and a call takes 1 .. " + std::to_string(MOGP_FORECAST_MAXH));
+    if (m->ctx->comm.kind != MOGP_COMM_NONE && m->ctx->comm.n > 1) return fail(MOGP_EINVAL, "mogp_exact_forecast: not sharded (the handle's context has a communicator of more than one rank)");
+    const int64_t N = m->N, Npad = m->Npad;
+    std::vector<int> storage(N, -1), map(Npad, -1);             // caller's row -> storage position; time position -> storage position
+    for (int64_t pos = 0; pos < N; ++pos) storage[m->sx.perm[pos]] = (int)pos;
+    std::vector<char> seen(N, 0);
+    for (int64_t p = 0; p < N; ++p) {
+        if (order[p] < 0 || order[p] >= N || seen[order[p]])
+            return fail(MOGP_EINVAL, "mogp_exact_forecast: order is not a permutation of 0 .. N - 1: order[" + std::to_string(p) + "] = " + std::to_string(order[p]) +
+                                     (order[p] < 0 || order[p] >= N ? " is out of range" : " appears twice"));
+        seen[order[p]] = 1;
+        map[p] = storage[order[p]];
+    }
+    std::vector<int> hcut((size_t)H * N);
+    for (int h = 0; h < H; ++h)
+        for (int64_t p = 0; p < N; ++p) {
+            const int64_t c = cut[(size_t)h * N + p];
+            if (c < -1 || c > p)
+                return fail(MOGP_EINVAL, "mogp_exact_forecast: cut[h = " + std::to_string(h) + ", p = " + std::to_string(p) + "] = " + std::to_string(c) + ", and a cut is -1 (skipped) or 0 .. p");
+            hcut[(size_t)h * N + p] = (int)c;
+        }
+    int rc;
+    if ((rc = begin_call(m, info, true))) return rc;
+    auto again = [&]() { return mogp_exact_forecast(m, noise_var, data_var, jitter, order, H, cut, score, mu, var, jitter_abs, info); };
+    // every allocation and upload before the factorisation is enqueued (see factorize); the sums travel behind the evaluation's own scalars in the pinned block
+    if ((rc = ensure_system(m))) return rc;
+    const PinLayout pl(m);
+    const size_t HN = (size_t)H * N;
+    if ((rc = pin_ensure(m, pl.total + 2 * HN))) return rc;
+    ForecastWork& f = m->fc;
+    if ((rc = f.map.ensure(Npad))) return rc;
+    if ((rc = f.cut.ensure((size_t)MOGP_FORECAST_MAXH * N))) return rc;
+    if ((rc = f.sums.ensure((size_t)2 * MOGP_FORECAST_MAXH * N))) return rc;
+    HIP_TRY(hipMemcpyAsync(f.map.p, map.data(), Npad * sizeof(int), hipMemcpyHostToDevice, m->st));          // (pageable sources: staged before the call returns)
+    HIP_TRY(hipMemcpyAsync(f.cut.p, hcut.data(), HN * sizeof(int), hipMemcpyHostToDevice, m->st));
+    GramArgs ga{};
+    FactorPlan plan;
+    plan.schedule = FactorPlan::FactorOnly; plan.defer = true; plan.refine = true; plan.gather = f.map.p;
+    if ((rc = factorize(m, noise_var, data_var, jitter, plan, nullptr, jitter_abs, info, &ga))) return rc;
+    // z = L^-1 r with L itself, r in time order
+    HIP_TRY(hipMemsetAsync(m->acc_rhs.p, 0, (size_t)Npad * MOGP_TILE * sizeof(double), m->st));
+    if ((rc = launch_gather_vec(m->d_y.p, m->d_z.p, N, Npad, f.map.p, m->st))) return rc;
+    if ((rc = launch_copy2d(m->acc_rhs.p, MOGP_TILE, m->d_z.p, 1, Npad, 1, 1.0, m->st))) return rc;
+    if ((rc = trsm_lower(m, m->k.A.p, Npad, m->nb, m->acc_rhs.p, MOGP_TILE, MOGP_TILE, false))) return rc;
+    if ((rc = launch_copy2d(m->d_z.p, 1, m->acc_rhs.p, MOGP_TILE, Npad, 1, 1.0, m->st))) return rc;
+    if ((rc = launch_forecast_rows(m->k.A.p, Npad, N, m->d_z.p, f.cut.p, H, f.sums.p, f.sums.p + HN, m->st))) return rc;
+    double* hs = m->h_pin + pl.total;
+    HIP_TRY(hipMemcpyAsync(hs, f.sums.p, 2 * HN * sizeof(double), hipMemcpyDeviceToHost, m->st));
+    if ((rc = mark(m, 5))) return rc;
+    if ((rc = wait_stream(m->st))) return rc;
+    if ((rc = factorize_finish(m, ga, nullptr, info))) return retry_on_streams(m, rc, again);      // the pivot report: in time order
+    collect_timing(m, 5);
+    // y as the caller gave it: under a mean table hy0 holds it and hy the residual, so m_p = hy0 - hy
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int h = 0; h < H; ++h) {
+        double sum = 0.0;
+        for (int64_t p = 0; p < N; ++p) {
+            const size_t i = (size_t)h * N + p, o = (size_t)h * N + order[p];
+            if (hcut[i] < 0) { mu[o] = var[o] = nan; continue; }
+            const int s = map[p];
+            const double r = m->hy[s], e = r - hs[i], v = hs[HN + i];
+            mu[o] = (m->mean_on ? m->hy0[s] - r : 0.0) + hs[i];
+            var[o] = v;
+            sum += -0.5 * std::log(2.0 * M_PI * v) - 0.5 * e * e / v;
+        }
+        score[h] = sum;
+    }
     return MOGP_OK;
 }
 

@@ -771,6 +771,7 @@ int mogp_model_destroy(mogp_model* m) {
     m->oa.release();
     m->loo.release();
     m->cv.release();
+    m->fc.release();
     m->d_x.release(); m->d_y.release(); m->d_table.release(); m->d_kind.release(); m->d_shape.release();
     m->d_noise.release(); m->d_dvar.release(); m->d_z.release(); m->d_alpha.release(); m->d_zz.release();
     m->d_partial.release(); m->d_moments.release(); m->d_diagG.release(); m->d_tiles.release(); m->d_pair_start.release(); m->strip.release(); m->strip_own.release();

@@ -332,6 +332,14 @@ struct CvWork {
     }
 };
 
+// workspace of the rolling-origin forecast (forecast.hip): the time-order map, the cuts and the two sums per cut and point.  Allocated by the first
+// mogp_exact_forecast of a handle and released with it
+struct ForecastWork {
+    mogp::DevBuf<int> map, cut;         // [Npad] storage position of time position p; [MOGP_FORECAST_MAXH][N] cuts in time order
+    mogp::DevBuf<double> sums;          // [2][MOGP_FORECAST_MAXH][N]: s1, s2
+    void release() { map.release(); cut.release(); sums.release(); }
+};
+
 // right-hand sides of the prediction's dataflow schedule: X L^T = T, `nt` tile rows (row-major, the leading dimension of the N x N matrices), `ready`: T is in place
 struct FlowRhs { double* T; double* X; int nt; hipEvent_t ready; };
 struct mogp_model {
@@ -442,6 +450,7 @@ struct mogp_model {
     OaWork oa;
     LooWork loo;
     CvWork cv;
+    ForecastWork fc;
 
     // trainable mean (mean.hip, mogp_model_set_mean): with a table set, d_y / hy hold the residual y0 - m(X) and d_y0 / hy0 the raw targets
     bool mean_on = false, mean_g_valid = false, mean_g_pending = false;
@@ -562,6 +571,11 @@ int cv_workspace(mogp_model* m, const int32_t* fold, int64_t nfolds, bool grad);
 int cv_folds(mogp_model* m, const double* kinv, const double* y, bool grad);   // vec zeroed, then per fold: mu, diag Sigma, b, the term of L, with grad the factor F_B (events 0, 1 around the kernel)
 int cv_fill_S(mogp_model* m, const double* kinv, double* scratch);    // S = 0, then S[:, B] = Kj^-1[:, B] F_B fold by fold (events 2, 3 around both)
 size_t cv_bytes(const mogp_model* m);                               // device memory of CvWork
+// forecast.hip -- the rolling-origin forecast's kernels.  map[p]: the position in channel-sorted storage of the point at time position p < N
+int launch_sym_gather(const double* src, double* dst, int64_t ld, int nb, int64_t N, const int* map, hipStream_t s);   // dst[p, q] = src[max, min of (map[p], map[q])] over the lower block triangle (diagonal tiles whole), identity on the padding; map null: the plain copy of those tiles
+int launch_gather_vec(const double* src, double* dst, int64_t N, int64_t Npad, const int* map, hipStream_t s);         // dst[p] = src[map[p]], zeros on the padding
+// s1[h N + p] = sum_{k < cut[h N + p]} L[p, k] z[k],  s2[h N + p] = sum_{cut[h N + p] <= k <= p} L[p, k]^2 for H <= MOGP_FORECAST_MAXH cuts in one pass over row p; NaN where cut = -1
+int launch_forecast_rows(const double* L, int64_t ld, int64_t N, const double* z, const int* cut, int H, double* s1, double* s2, hipStream_t s);
 int eval_sweep(mogp_model* m, const double* noise_var, const double* data_var, double jitter, double* lml, double* jitter_abs, int64_t* info);   // shard.hip
 void one_gpu_call(mogp_model* m);   // ownership state of a previous sharded evaluation off (every one-GPU entry point calls this first)
 int ensure_system(mogp_model* m);     // the N x N system of the exact / OA paths and the tile lists over (X, X), on first use (mogp_api.hip)

@@ -735,6 +735,57 @@ class Exact(Model):
         with terms_cache():
             return self._loss_impl(score="cv", folds=folds)
 
+    # -- rolling-origin forecast from one factorisation (csrc/forecast.hip) ---------------------------------------------
+    FORECAST_MAXH = 8          # cuts per point of one device call (MOGP_FORECAST_MAXH)
+
+    def _forecast_args(self, order, cut):
+        """`order` (N,): the model's row at every time position; `cut` (N,) or (H, N): per time position p the number of leading points the
+        prediction of that point may use, 0 .. p, or -1 to skip it -> (order int64, cut int64 (H, N), cut was 1-D); what the device would
+        refuse is refused here, by name, before any device call"""
+        N = self.X.shape[0]
+        order, cut = np.asarray(order), np.asarray(cut)
+        if order.shape != (N,) or order.dtype.kind not in "iu":
+            raise ValueError("order must hold one integer row index per training point: shape %s for %d points" % (order.shape, N))
+        order = order.astype(np.int64)
+        if not np.array_equal(np.sort(order), np.arange(N)):
+            raise ValueError("order is not a permutation of 0 .. %d" % (N - 1))
+        flat = cut.ndim == 1
+        if cut.ndim not in (1, 2) or cut.shape[-1] != N or cut.dtype.kind not in "iu":
+            raise ValueError("cut must hold one integer per training point, (N,) or (H, N): shape %s for %d points" % (cut.shape, N))
+        cut = cut.astype(np.int64).reshape(-1, N)
+        if not 1 <= cut.shape[0] <= self.FORECAST_MAXH:
+            raise ValueError("cut holds %d horizons: one call takes 1 .. %d" % (cut.shape[0], self.FORECAST_MAXH))
+        bad = np.argwhere((cut < -1) | (cut > np.arange(N)))
+        if bad.size:
+            h, p = bad[0]
+            raise ValueError("cut[%d, %d] = %d: a cut is -1 (skipped) or 0 .. p, the number of points in front of time position p that are used" % (h, p, cut[h, p]))
+        return order, cut, flat
+
+    def _forecast(self, order, cut):
+        self._refuse_sharded_loo("the rolling-origin forecast")      # before any device call
+        order, cut, flat = self._forecast_args(order, cut)
+        h, table, D = self._push_terms()
+        with self._cholesky_guard():             # (no conditioning switch: this factorisation is the refined one, with substitution by L itself)
+            res = h.forecast(self._noise_var(), self.jitter, order, cut, data_var=self.data_variance)
+        return res, flat
+
+    def forecast(self, order, cut):
+        """-> (mu, var), each (H, N) in the model's row order ((N,) for a 1-D cut): mean and variance (noise included) of the prediction of every
+        training target from the `cut` points in front of it in the order `order`; NaN where cut is -1.  One factorisation for all of them"""
+        res, flat = self._forecast(order, cut)
+        mu = res["mu"]
+        if self.mean is not None and not (self._trainable_mean() and self._mean_affine()[0] is not None):
+            mu = mu + np.asarray(self.mean(self.X)).reshape(1, -1)      # the device holds y - m(X) as its targets (as _held_out)
+        mu, var = mu.astype(config.dtype, copy=False), res["var"].astype(config.dtype, copy=False)
+        return (mu[0], var[0]) if flat else (mu, var)
+
+    def forecast_log_likelihood(self, order, cut):
+        """-> (H,) (a scalar for a 1-D cut): sum over the points with cut >= 0 of log p(y_p | the cut points in front of it).  With cut[p] = p
+        the sum is the log marginal likelihood, whatever the order"""
+        res, flat = self._forecast(order, cut)
+        score = res["score"].astype(config.dtype, copy=False)
+        return score[0] if flat else score
+
     def predict_f(self, X, full=False):
         """reference gpr/model.py:455-483"""
         X = self._check_input(X)

@@ -650,6 +650,92 @@ class Model:
             first += -(-rows.size // size)
         return labels
 
+    # ---- rolling-origin forecasts: every training point from the points up to `horizon` before it, all from one factorisation --------
+    def _forecast_only(self, what):
+        if not isinstance(self.gpr, gpr.Exact):
+            raise ValueError("%s needs exact inference (mogptk_amd.Exact): %s has no rolling-origin forecast" % (what, self.gpr.name()))
+
+    def forecast_origins(self, horizons, min_train=1):
+        """The time order of the training points and, per horizon, what every point may be predicted from -> (order, cut).  `order` (N,) is the
+        stable argsort of the inputs over the model's row order (channels stacked), so points of different channels interleave in time;
+        `cut[h, p]` is the number of points with x <= x_p - horizons[h] + tol, tol = 1e-9 (x_max - x_min), for the point at time position
+        p: the points known `horizons[h]` before it, on every channel.  A point with fewer than `min_train` such points gets -1 and is not
+        scored.  Horizons are in the units of the (transformed) input and must exceed tol; one input dimension only."""
+        if self.dataset.get_input_dims()[0] != 1:
+            raise ValueError("forecast_origins orders the points by their input: one input dimension only")
+        horizons = np.atleast_1d(np.asarray(horizons, dtype=np.float64))
+        if horizons.ndim != 1 or horizons.size == 0:
+            raise ValueError("horizons must be a number or a sequence of numbers")
+        x = np.asarray(self.gpr.X, dtype=np.float64)[:, -1]
+        tol = 1e-9 * (x.max() - x.min())
+        if not np.all(horizons > tol):
+            raise ValueError("every horizon must exceed %g (1e-9 of the inputs' range): a point is never predicted from itself" % tol)
+        if int(min_train) < 0:
+            raise ValueError("min_train must not be negative")
+        order = np.argsort(x, kind="stable")
+        xs = x[order]
+        cut = np.stack([np.searchsorted(xs, xs - hz + tol, side="right") for hz in horizons]).astype(np.int64)
+        cut[cut < int(min_train)] = -1
+        return order, cut
+
+    def _forecast(self, horizons, min_train):
+        """(order, cut, mu, var) in transformed space, the horizons in chunks of what one device call takes"""
+        order, cut = self.forecast_origins(horizons, min_train)
+        step = gpr.Exact.FORECAST_MAXH
+        parts = [self.gpr.forecast(order, cut[a:a + step]) for a in range(0, cut.shape[0], step)]
+        return order, cut, np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+
+    def _channel_rows(self):
+        ends = np.cumsum([0] + [len(x) for x in self.dataset.get_train_data()[0]])
+        return [slice(ends[j], ends[j + 1]) for j in range(len(self.dataset))]
+
+    def forecast_log_likelihood(self, horizons, min_train=1, per_channel=False):
+        """Rolling-origin forecast log-likelihood in transformed space -> (H,), or (H, channels) with `per_channel`: the sum over the training
+        points of log p(y_p | every point of every channel up to horizons[h] before x_p).  It asks what removing the end of a series and
+        extrapolating asks, at every origin at once, from one factorisation; the points with fewer than `min_train` earlier points are not
+        scored.  Exact inference only."""
+        self._forecast_only("forecast_log_likelihood()")
+        _, _, mu, var = self._forecast(horizons, min_train)
+        y = np.asarray(self.gpr.y, dtype=np.float64).reshape(1, -1)
+        terms = -0.5 * np.log(2.0 * np.pi * var) - 0.5 * np.square(y - mu) / var
+        if per_channel:
+            return np.stack([np.nansum(terms[:, rows], axis=1) for rows in self._channel_rows()], axis=1)
+        return np.nansum(terms, axis=1)
+
+    def backtest(self, horizons, sigma=2, min_train=1, transformed=False):
+        """Rolling-origin forecasts of the training data -> (X, mu, lower, upper), each a list per channel (bare arrays for a single channel):
+        mu, lower and upper are (H, N_c), row h the prediction of every point of the channel from the data up to horizons[h] before it,
+        lower / upper = mu -/+ sigma sqrt(var) with the likelihood's noise, NaN where fewer than `min_train` points precede.  Back through
+        every channel's Y transformer unless `transformed`, as `predict`.  Exact inference only."""
+        self._forecast_only("backtest()")
+        _, _, mu, var = self._forecast(horizons, min_train)
+        s = sigma * np.sqrt(var)
+        X = self.dataset.get_train_data()[0]
+        out = []
+        for j, rows in enumerate(self._channel_rows()):
+            undo = (lambda v: v) if transformed else (lambda v, j=j: self.dataset[j].Y_transformer.backward(v, X[j]))
+            out.append([np.stack([undo(v[h, rows]) for h in range(mu.shape[0])]) for v in (mu, mu - s, mu + s)])
+        if len(self.dataset) == 1:
+            return (X[0],) + tuple(out[0])
+        return (X,) + tuple([c[k] for c in out] for k in range(3))
+
+    def forecast_error(self, horizons, method="MAE", min_train=1):
+        """Error of the rolling-origin forecasts against the training targets, in the data's own units -> (H,): `method` (MAE, MAPE, sMAPE,
+        MSE, RMSE, or a function (y_true, y_pred)) over the points that have a forecast at that horizon.  Exact inference only."""
+        self._forecast_only("forecast_error()")
+        measure = method if callable(method) else self._ERROR_MEASURES.get(str(method).lower())
+        if measure is None:
+            raise ValueError("valid error calculation methods are MAE, MAPE, sMAPE, MSE, and RMSE")
+        _, _, mu, _ = self._forecast(horizons, min_train)
+        X, Y = self.dataset.get_train_data()
+        truth = np.concatenate(Y)
+        out = np.empty(mu.shape[0])
+        for h in range(mu.shape[0]):
+            pred = np.concatenate([np.reshape(self.dataset[j].Y_transformer.backward(mu[h, rows], X[j]), -1) for j, rows in enumerate(self._channel_rows())])
+            scored = ~np.isnan(mu[h])
+            out[h] = measure(truth[scored], pred[scored]) if np.any(scored) else np.nan
+        return out
+
     _ERROR_MEASURES = {"mae": mean_absolute_error, "mape": mean_absolute_percentage_error,
                        "smape": symmetric_mean_absolute_percentage_error, "mse": mean_squared_error,
                        "rmse": root_mean_squared_error}
