@@ -92,7 +92,9 @@ int  mogp_model_set_point_diag(mogp_model* m, const double* kdiag);
 /* replaces MultiOutputKernel.K (gpr/kernel.py:446-481); stateless, needs only a context and a term table
  * (C x C x T x MOGP_TERM_WIDTH(D)).  X1 is M1 x (1+D).  X2 == NULL: symmetric Gram K(X1), K_out is M1 x M1
  * (lower channel pairs + mirror, :458-467).  Otherwise X2 is M2 x (1+D) and K_out is M1 x M2
- * (all C*C pairs, no symmetry, :468-479).  Rows may be in any order. */
+ * (all C*C pairs, no symmetry, :468-479).  Rows may be in any order.
+ * The phase of a term is formed per point from the ABSOLUTE inputs, so an entry's error grows with 2 pi (sum_d |M_d| max|x_d + Delta_d| + |Psi|)
+ * ulps -- inputs far from the origin (years) with high frequencies lose that much of the 1e-12; centring them is the caller's business. */
 int  mogp_gram(mogp_ctx* ctx, int C, int D, int T, const double* table,
                int64_t M1, const double* X1, int64_t M2, const double* X2, double* K_out);
 /* the same with rows of `width` = 2 + 3 D or 2 + 5 D (envelope, see mogp_model_set_terms_ex) */
@@ -469,6 +471,24 @@ int  mogp_model_schedule(mogp_model* m, int* flags);
  * the previous evaluation's: use the mode for measurement only.  Requires a completed gradient evaluation on this model.  on = 0: back to normal. */
 int  mogp_model_flow_replay(mogp_model* m, int on);
 
+/* Measurement / test entry in the manner of mogp_model_flow_replay (no counterpart in the reference): the CU count the Gram and moment launches of
+ * this context PLAN with -- the cutting of the strip kernel's runs (2 ncu workgroup slots), the persistent grid of the general Gram kernel
+ * (min(tiles, 2 ncu)) and that of the pipelined moment kernel (min(tiles, ncu)) -- and nothing else.  ncu = 0 restores the device's own count,
+ * a negative value is EINVAL.  A small count makes small problems take the cross-tile paths that otherwise need N of several thousand
+ * (tests/test_spectral_sweep_gpu.py); results do not depend on it beyond the summation order of the moment kernel's chunks.  Every model of the
+ * context cuts its strip lists again with the next call that needs them. */
+int  mogp_ctx_plan_cus(mogp_ctx* ctx, int ncu);
+/* The strip plan of a symmetric training Gram as numbers -- no device work, callable without a GPU, like mogp_flow_plan: the lower tile list of
+ * C channels of sizes[c] points, split into the strip kernel's runs and the general kernel's rest as a launch planned on ncu CUs cuts them.
+ * *count = rows; out (cap >= 8 * count, or NULL to ask for the count) gets 8 numbers per row, the runs first, both in launch order:
+ *   [1, r0, c0, n tiles, pair, diag (the LAST tile is the diagonal one), 64, 64]      a run of n full tiles at columns c0, c0 + 64, ...
+ *   [0, r0, c0, 1, pair, diag, rows, columns]                                          a tile of the rest */
+int  mogp_strip_plan(int C, const int64_t* sizes, int ncu, int64_t* out, int64_t cap, int64_t* count);
+/* What a live handle's strip lists hold at the moment -- the same kind of test entry, no device work: which 0 the training Gram's list, 1 / 2 its
+ * head / tail lists of the dataflow schedule, 3 the owned list of a sharded evaluation, 4 the (Z, X) list of the sparse models.
+ * out4 = [the CU count the runs were cut for (-1: the list was never built), runs, rest tiles, tiles of the longest run]. */
+int  mogp_model_strip_runs(mogp_model* m, int which, int64_t* out4);
+
 /* Diagnostic counters of the dataflow schedule, summed over every evaluation of this model so far (no counterpart in the reference).  A workgroup
  * (or a chain kernel / private-stream hook) that has waited for a few ms re-reads what it waits for with RETURNING read-modify-writes -- a "deep"
  * look -- next to the sc1 loads every look uses, and counts the answers that differ.  out[0] deep looks of the dataflow kernel, out[1] of them with a
@@ -511,6 +531,11 @@ int  mogp_flow_trace(mogp_model* m, int64_t* out, int64_t cap, int64_t* count);
  *        4 = measurement only (tools/cv_time.py): out[0], out[1] = ms of the per-fold kernel and of the zero fill + column kernel of the last
  *        mogp_exact_cv(MOGP_EVAL_GRAD) that ran with profiling on. */
 int  mogp_model_fetch(mogp_model* m, int which, double* out);
+/* Kj = K + noise + data_var + jitter as the exact path writes it before it factors it (the strip kernel's runs, the general kernel's rest), in the
+ * device's CHANNEL-SORTED order, N x N, lower triangle (zeros above) -- numerics diagnostics (tests/test_spectral_sweep_gpu.py), no reference
+ * seam.  Arguments as mogp_exact_eval's; factorises nothing, and like every evaluation it ends what the last one left on the handle
+ * (mogp_model_fetch: EINVAL until the next evaluation). */
+int  mogp_model_gram(mogp_model* m, const double* noise_var, const double* data_var, double jitter, double* K_out);
 
 /* The pseudo-input sparse GP of Snelson & Ghahramani (FITC) on the model's data: reference gpr/model.py:516-541
  * (Snelson.log_marginal_likelihood) + the autograd backward through it, and :543-576 (Snelson.predict_f).

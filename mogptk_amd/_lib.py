@@ -103,6 +103,10 @@ SIGNATURES = {
     "mogp_model_fetch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_dp]),
     "mogp_model_schedule": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
     "mogp_model_flow_replay": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "mogp_ctx_plan_cus": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "mogp_strip_plan": (ctypes.c_int, [ctypes.c_int, c_i64p, ctypes.c_int, c_i64p, ctypes.c_int64, c_i64p]),
+    "mogp_model_strip_runs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i64p]),
+    "mogp_model_gram": (ctypes.c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.c_double, c_dp]),
     "mogp_model_flow_diag": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint)]),
     "mogp_flow_plan": (ctypes.c_int, [ctypes.c_int, c_i64p, ctypes.c_int64, c_i64p]),
     "mogp_flow_plan_rhs": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i64p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
@@ -203,6 +207,23 @@ def device_name(device=0):
 
 def _ip(a):
     return None if a is None else a.ctypes.data_as(c_ip)
+
+
+def plan_cus(ncu, device=0):
+    """measurement / test switch (mogp_ctx_plan_cus): the CU count the Gram and moment launches of the device's context plan their strip runs and
+    persistent grids with; 0 restores the device's own count"""
+    check(lib().mogp_ctx_plan_cus(context(device), int(ncu)))
+
+
+def strip_plan(sizes, ncu):
+    """-> int64 array [rows, 8] of the strip plan of a symmetric training Gram over channels of `sizes` points on `ncu` CUs (mogp_strip_plan, host
+    only): runs [1, r0, c0, n, pair, diag, 64, 64] first, then the rest tiles [0, r0, c0, 1, pair, diag, rows, columns]"""
+    sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+    cnt = ctypes.c_int64(0)
+    check(lib().mogp_strip_plan(int(sizes.size), sizes.ctypes.data_as(c_i64p), int(ncu), None, 0, ctypes.byref(cnt)))
+    out = np.zeros((cnt.value, 8), dtype=np.int64)
+    check(lib().mogp_strip_plan(int(sizes.size), sizes.ctypes.data_as(c_i64p), int(ncu), out.ctypes.data_as(c_i64p), out.size, ctypes.byref(cnt)))
+    return out
 
 
 def gram(device, C, D, table, X1, X2=None, kind=None, shape=None):
@@ -847,6 +868,19 @@ class ExactHandle:
         f = np.zeros(1)
         check(lib().mogp_model_inverse_fraction(self._h, _dp(f)))
         return float(f[0])
+
+    def strip_runs(self, which=0):
+        """-> dict(ncu, runs, rest, longest) of one of the handle's strip lists as it stands (mogp_model_strip_runs): which 0 the training Gram's,
+        1 / 2 its head / tail lists, 3 the owned list, 4 the sparse models' (Z, X) list; ncu -1: never built"""
+        out = np.zeros(4, dtype=np.int64)
+        check(lib().mogp_model_strip_runs(self._h, int(which), out.ctypes.data_as(c_i64p)))
+        return dict(ncu=int(out[0]), runs=int(out[1]), rest=int(out[2]), longest=int(out[3]))
+
+    def gram_probe(self, noise_var, jitter, data_var=None):
+        """Kj as the exact path writes it before factoring it (mogp_model_gram): N x N in channel-sorted order, lower triangle, zeros above"""
+        out = np.empty((self.N, self.N))
+        check(lib().mogp_model_gram(self._h, _dp(_f64(noise_var)), _dp(_f64(data_var)), float(jitter), _dp(out)))
+        return out
 
     def fetch(self, which):
         out = np.empty(2 if which == 4 else self.N if which in (2, 3) else (self.N, self.N))

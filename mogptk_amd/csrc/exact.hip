@@ -244,7 +244,7 @@ static int factorize_finish(mogp_model* m, const GramArgs& ga, double* lml, int6
         // distinguish NaN / Inf in the Gram from a plain indefinite matrix (reference prints which, gpr/model.py:249-252)
         int flag = 0;
         HIP_TRY(hipMemsetAsync(m->d_flag.p, 0, sizeof(int), m->st));
-        if ((rc = launch_gram(ga, (int)m->tiles.size(), m->st, m->radial ? m->gate_kinds : 0))) return rc;
+        if ((rc = launch_gram(plan_cus(m->ctx), ga, (int)m->tiles.size(), m->st, m->radial ? m->gate_kinds : 0))) return rc;
         if ((rc = launch_nonfinite_scan(m->k.A.p, Npad, N, m->d_flag.p, m->st))) return rc;
         HIP_TRY(hipMemcpyAsync(&flag, m->d_flag.p, sizeof(int), hipMemcpyDeviceToHost, m->st));
         HIP_TRY(hipStreamSynchronize(m->st));
@@ -296,19 +296,19 @@ static int factorize(mogp_model* m, const double* noise_var, const double* data_
         GramArgs gh = ga, gt = ga;
         gh.tiles = m->d_tiles_head.p; m->strip_head.attach(gh); gh.ev1 = nullptr;
         gt.tiles = m->d_tiles_tail.p; m->strip_tail.attach(gt); gt.ev0 = nullptr; gt.phases_ready = 1;
-        if ((rc = launch_gram(gh, (int)m->tiles_head.size(), m->st, m->radial ? m->gate_kinds : 0))) return rc;
+        if ((rc = launch_gram(plan_cus(m->ctx), gh, (int)m->tiles_head.size(), m->st, m->radial ? m->gate_kinds : 0))) return rc;
         if ((rc = launch_pad_identity(m->k.A.p, Npad, N, Npad, m->st))) return rc;
         if (!m->gram_ev) HIP_TRY(hipEventCreateWithFlags(&m->gram_ev, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(m->gram_ev, m->st));
         HIP_TRY(hipStreamWaitEvent(m->st2, m->gram_ev, 0));
-        if ((rc = launch_gram(gt, (int)m->tiles_tail.size(), m->st2, m->radial ? m->gate_kinds : 0))) return rc;       // spd_potri_flow enqueues the dataflow kernel behind it
+        if ((rc = launch_gram(plan_cus(m->ctx), gt, (int)m->tiles_tail.size(), m->st2, m->radial ? m->gate_kinds : 0))) return rc;       // spd_potri_flow enqueues the dataflow kernel behind it
         // ... and makes the private stream wait for this event before the first launch that reads beyond the first 512 columns (round 4: with
         // four processes on one GPU the next-diagonal update of block 0 ran BEFORE this launch had written its block: "not positive definite")
         if (!m->gram_tail_ev) HIP_TRY(hipEventCreateWithFlags(&m->gram_tail_ev, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(m->gram_tail_ev, m->st2));
         m->k.tail_ready = m->gram_tail_ev;
     } else {
-        if ((rc = launch_gram(ga, (int)m->tiles.size(), m->st, m->radial ? m->gate_kinds : 0))) return rc;
+        if ((rc = launch_gram(plan_cus(m->ctx), ga, (int)m->tiles.size(), m->st, m->radial ? m->gate_kinds : 0))) return rc;
         if ((rc = launch_pad_identity(m->k.A.p, Npad, N, Npad, m->st))) return rc;
         if (plan.gather) {              // Kj into time order: A -> B through the map, the lower block triangle back into A; spd_potrf then runs as it stands
             if (!factor_only || !plan.refine || m->rhs_job) return fail(MOGP_EINVAL, "factorize: a gathered factorisation is the refined factor alone, on streams");
@@ -454,7 +454,7 @@ int moment_pass_device(mogp_model* m, const double* kinv, double ksign) {
     ma.partial = m->d_partial.p;
     ma.phases_ready = 1;                       // ph_xx was filled by this evaluation's Gram launch: same inputs, same table
     ma.ev0 = prof_event(m, 9); ma.ev1 = prof_event(m, 10);
-    if ((rc = launch_moments(ma, m->st, m->radial ? m->gate_kinds : 0))) return rc;
+    if ((rc = launch_moments(plan_cus(m->ctx), ma, m->st, m->radial ? m->gate_kinds : 0))) return rc;
     if ((rc = launch_moment_reduce(m->d_partial.p, own ? m->d_pair_start_own.p : m->d_pair_start.p, P, T, W, D, m->d_moments.p, m->st))) return rc;
     if ((rc = launch_diagG(kinv, Npad, m->d_alpha.p, m->d_chan_off.p, C, m->d_diagG.p, m->st, ksign, rm, m->sh_rank))) return rc;
     if ((rc = mean_grad_enqueue(m, m->d_alpha.p, -1.0))) return rc;            // dp/dr = -alpha (nothing is launched without a mean table)
@@ -669,6 +669,27 @@ int mogp_exact_eval(mogp_model* m, const double* noise_var, const double* data_v
     return MOGP_OK;
 }
 
+// Kj as factorize() builds it in its unsplit branch -- the strip runs of m->strip on k_gram_strip2, the rest on k_gram<1>, the padding's identity --
+// read back before anything factors it: numerics diagnostics (tests/test_spectral_sweep_gpu.py), no reference seam
+int mogp_model_gram(mogp_model* m, const double* noise_var, const double* data_var, double jitter, double* K_out) {
+    if (!m || !K_out) return fail(MOGP_EINVAL, "mogp_model_gram: null argument");
+    int rc;
+    if ((rc = begin_call(m, nullptr, true))) return rc;
+    const int64_t N = m->N, Npad = m->Npad;
+    GramArgs ga{};
+    double jabs = 0.0;
+    if ((rc = exact_begin(m, noise_var, data_var, jitter, ga, jabs))) return rc;
+    m->strip.attach(ga);
+    if ((rc = launch_gram(plan_cus(m->ctx), ga, (int)m->tiles.size(), m->st, m->radial ? m->gate_kinds : 0))) return rc;
+    if ((rc = launch_pad_identity(m->k.A.p, Npad, N, Npad, m->st))) return rc;
+    std::vector<double> h((size_t)Npad * Npad);
+    HIP_TRY(hipMemcpyAsync(h.data(), m->k.A.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, m->st));
+    HIP_TRY(hipStreamSynchronize(m->st));
+    for (int64_t a = 0; a < N; ++a)
+        for (int64_t b = 0; b < N; ++b) K_out[a * N + b] = b <= a ? h[(size_t)a * Npad + b] : 0.0;
+    return MOGP_OK;
+}
+
 int mogp_exact_loo(mogp_model* m, const double* noise_var, const double* data_var, double jitter, int flags,
                    double* loo, double* mu, double* var, double* moments, double* diagG, double* trG, double* jitter_abs, int64_t* info) {
     if (!m) return fail(MOGP_EINVAL, "mogp_exact_loo: model is null");
@@ -815,7 +836,7 @@ static int predict_core(mogp_model* m, const double* noise_var, const double* da
     for (int p = 0; p < R; ++p) {                                    // block p: K_p(Xs, X) from table p into its Spad rows
         GramArgs gp = ga;
         if (parts) { gp.table = m->d_parts.p + p * tab_n; gp.out = m->d_Ksf.p + (int64_t)p * Spad * Npad; gp.phases_ready = p > 0 && parts->psi_same[p]; }
-        if ((rc = launch_gram(gp, ts.ntiles, sv, m->radial ? m->gate_kinds : 0))) return rc;
+        if ((rc = launch_gram(plan_cus(m->ctx), gp, ts.ntiles, sv, m->radial ? m->gate_kinds : 0))) return rc;
     }
     if (mean_w) {                                                    // mu = K_sf w, before the substitution consumes K_sf
         std::vector<double> hw(Npad, 0.0);
@@ -961,7 +982,7 @@ static int predict_core(mogp_model* m, const double* noise_var, const double* da
     for (int p = 0; p < R; ++p) {
         GramArgs gp = ga;
         if (parts) { gp.table = m->d_parts.p + p * tab_n; gp.out = m->d_Kss.p + p * SS; gp.phases_ready = p > 0 && parts->psi_same[p]; }
-        if ((rc = launch_gram(gp, (int)st_tiles.size(), m->st, m->radial ? m->gate_kinds : 0))) return rc;
+        if ((rc = launch_gram(plan_cus(m->ctx), gp, (int)st_tiles.size(), m->st, m->radial ? m->gate_kinds : 0))) return rc;
         GemmArgs c{};
         c.A = m->d_Vt.p + (int64_t)p * Spad * Npad; c.lda = Npad; c.a_kmajor = 0; c.B = c.A; c.ldb = Npad; c.b_kmajor = 0;
         c.C = m->d_Kss.p + p * SS; c.ldc = Spad; c.alpha = -1.0; c.beta = 1.0;

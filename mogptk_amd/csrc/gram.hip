@@ -1091,7 +1091,7 @@ void split_strip_tiles(const std::vector<GTile>& tiles, int maxrun, std::vector<
     }
 }
 
-int launch_gram(const GramArgs& a0, int ntiles, hipStream_t s, int rows) {
+int launch_gram(int ncu, const GramArgs& a0, int ntiles, hipStream_t s, int rows) {
     if (ntiles <= 0) return 0;
     GramArgs a = a0;
     if (a.W <= 0) a.W = 2 + 3 * a.D;
@@ -1103,7 +1103,6 @@ int launch_gram(const GramArgs& a0, int ntiles, hipStream_t s, int rows) {
 #endif
     int rc = a.phases_ready ? 0 : launch_phase_tables(a.ph, a.xr, a.ldxr, a.nrows, a.xc, a.ldxc, a.ncols, a.table, a.T, a.D, a.C, a.W, s);
     if (rc) return rc;
-    static const int ncu = []() { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256; return pr.multiProcessorCount; }();
     const int grid = std::min(ntiles, 2 * ncu);              // persistent: two workgroups per CU (__launch_bounds__(256, 2))
     const size_t tab_bytes = (size_t)a.C * a.C * a.T * a.W * sizeof(double);
     a.tab_lds = tab_bytes <= 24 * 1024;                      // the term table rides in LDS when small (it is read by every staging item)
@@ -2368,7 +2367,7 @@ static void launch_moments_radial(const MomentArgs& a, hipStream_t s, int rows) 
     }
 }
 
-int launch_moments(const MomentArgs& a0, hipStream_t s, int rows) {
+int launch_moments(int ncu, const MomentArgs& a0, hipStream_t s, int rows) {
     if (a0.ntiles <= 0) return 0;
     MomentArgs a = a0;
     if (a.W <= 0) a.W = 2 + 3 * a.D;
@@ -2392,7 +2391,6 @@ int launch_moments(const MomentArgs& a0, hipStream_t s, int rows) {
         if (a.ev0) HIP_TRY(hipEventRecord(a.ev0, s));
         // D = 1 without an envelope, every row this rank's own: the persistent pipelined kernel
         if (!env && a.D == 1 && a.W == 5 && a.T <= 4 && a.row_mod <= 1 && a.xc == nullptr) {
-            static const int ncu = []() { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256; return pr.multiProcessorCount; }();
             // (the reduction staging of eight terms does not fit in LDS; three terms -- every BASELINE config of the exact model -- get an instantiation of their
             // own: the moments now live in registers across tiles, and five fewer accumulators keep the kernel clear of spills)
             if (a.T <= 3) hipLaunchKernelGGL(k_moments_x<3>, dim3(std::min(a.ntiles, ncu)), dim3(512), 0, s, a);

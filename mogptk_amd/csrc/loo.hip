@@ -130,7 +130,7 @@ int loo_moment_pass(mogp_model* m) {
     if (m->radial) { ma.kind = m->d_kind.p; ma.shape = m->d_shape.p; }
     ma.partial = m->d_partial.p;
     ma.phases_ready = 1;                       // ph_xx was filled by this evaluation's Gram launch: same inputs, same table
-    RC(launch_moments(ma, m->st, m->radial ? m->gate_kinds : 0));
+    RC(launch_moments(plan_cus(m->ctx), ma, m->st, m->radial ? m->gate_kinds : 0));
     RC(launch_moment_reduce(m->d_partial.p, m->d_pair_start.p, P, T, W, D, m->d_moments.p, m->st, 1));
     hipLaunchKernelGGL(k_loo_diag, dim3(C), dim3(256), 0, m->st, m->loo.G.p, Npad, m->d_chan_off.p, m->d_diagG.p);
     HIP_TRY(hipGetLastError());

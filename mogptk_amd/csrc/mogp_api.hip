@@ -109,35 +109,47 @@ void build_rect_tiles(const std::vector<int>& offr, const std::vector<int>& offc
 
 }  // namespace mogp
 
-using namespace mogp;
+namespace mogp {
+int plan_cus(const mogp_ctx* ctx) {
+    if (ctx && ctx->plan_ncu > 0) return ctx->plan_ncu;
+    static const int ncu = []() { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256; return pr.multiProcessorCount; }();
+    return ncu;
+}
 
-int StripTiles::build(const std::vector<GTile>& tiles) {
-    constexpr int maxrun = 8;      // tiles per run (round 6, with the graded tail and the one-barrier kernel: 103 us at 8 against 105 at 4 and 108 at 6, configs[1])
+void plan_strip_tiles(const std::vector<GTile>& tiles, int maxrun, int slots, std::vector<GSeg>& segs, std::vector<GTile>& rest) {
     split_strip_tiles(tiles, maxrun, segs, rest);
     // The hardware hands out workgroups in index order as slots free up: the launch ends when its LAST runs end, so those should be short.  The runs
     // that would be dispatched last (the final `tail` tiles' worth) are cut into single tiles, the `tail` tiles before them into pairs; a list with
     // fewer runs than there are workgroup slots is cut into single tiles altogether (the head launch of the dataflow schedule: 8 column tiles a row).
-    if (!segs.empty()) {
-        static const int slots = []() { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 512; return 2 * pr.multiProcessorCount; }();
-        const long tail = slots;
-        long total = 0;
-        for (const GSeg& g : segs) total += g.n;
-        std::vector<GSeg> out;
-        out.reserve(segs.size() * 2);
-        long seen = 0;
-        const bool all_single = (long)segs.size() < 2L * slots;
-        for (const GSeg& g : segs) {
-            const long left = total - seen;                      // tiles from this run to the end of the list
-            const int cut = (all_single || left <= tail) ? 1 : (left <= 2 * tail ? 2 : maxrun);
-            for (int o = 0; o < g.n; o += cut) {
-                GSeg h = g;
-                h.c0 = g.c0 + o * MOGP_GT; h.n = std::min(cut, g.n - o); h.diag = (o + cut >= g.n) ? g.diag : 0;
-                out.push_back(h);
-            }
-            seen += g.n;
+    if (segs.empty()) return;
+    const long tail = slots;
+    long total = 0;
+    for (const GSeg& g : segs) total += g.n;
+    std::vector<GSeg> out;
+    out.reserve(segs.size() * 2);
+    long seen = 0;
+    const bool all_single = (long)segs.size() < 2L * slots;
+    for (const GSeg& g : segs) {
+        const long left = total - seen;                      // tiles from this run to the end of the list
+        const int cut = (all_single || left <= tail) ? 1 : (left <= 2 * tail ? 2 : maxrun);
+        for (int o = 0; o < g.n; o += cut) {
+            GSeg h = g;
+            h.c0 = g.c0 + o * MOGP_GT; h.n = std::min(cut, g.n - o); h.diag = (o + cut >= g.n) ? g.diag : 0;
+            out.push_back(h);
         }
-        segs.swap(out);
+        seen += g.n;
     }
+    segs.swap(out);
+}
+}  // namespace mogp
+
+using namespace mogp;
+
+constexpr int kStripMaxRun = 8;    // tiles per run (round 6, with the graded tail and the one-barrier kernel: 103 us at 8 against 105 at 4 and 108 at 6, configs[1])
+
+int StripTiles::build(const std::vector<GTile>& tiles, int ncu_) {
+    plan_strip_tiles(tiles, kStripMaxRun, 2 * ncu_, segs, rest);
+    ncu = ncu_;
     int rc;
     if ((rc = d_segs.ensure(std::max<size_t>(segs.size(), 1)))) return rc;
     if ((rc = d_rest.ensure(std::max<size_t>(rest.size(), 1)))) return rc;
@@ -643,20 +655,30 @@ namespace mogp { void one_gpu_call(mogp_model* m) { m->sh_n = 1; m->sh_rank = 0;
 
 namespace mogp { int ensure_system(mogp_model* m) {
     int rc;
+    const int ncu = plan_cus(m->ctx);
+    if (!m->tiles.empty() && m->strip.ncu != ncu) {
+        // mogp_ctx_plan_cus changed the count since the runs were cut: cut them again (a measurement / test path -- the kernels of an earlier
+        // evaluation may still read the old lists, so every stream that takes a Gram launch is drained first)
+        for (hipStream_t q : {m->st, m->st2}) if (q) HIP_TRY(hipStreamSynchronize(q));
+        if ((rc = m->strip.build(m->tiles, ncu))) return rc;
+        if (m->strip_head.ncu >= 0 && (rc = m->strip_head.build(m->tiles_head, ncu))) return rc;
+        if (m->strip_tail.ncu >= 0 && (rc = m->strip_tail.build(m->tiles_tail, ncu))) return rc;
+        if (m->strip_own.ncu >= 0 && (rc = m->strip_own.build(m->tiles_own, ncu))) return rc;
+    }
     if (m->tiles.empty()) {
         build_sym_tiles(m->sx.off, m->C, m->tiles, m->pair_start);
         if ((rc = m->d_tiles.ensure(m->tiles.size()))) return rc;
         if ((rc = m->d_pair_start.ensure(m->pair_start.size()))) return rc;
         HIP_TRY(dev_upload(m->d_tiles.p, m->tiles.data(), m->tiles.size() * sizeof(GTile)));
-        if ((rc = m->strip.build(m->tiles))) return rc;
+        if ((rc = m->strip.build(m->tiles, ncu))) return rc;
         for (const GTile& t : m->tiles) (t.c0 < 4 * MOGP_TILE ? m->tiles_head : m->tiles_tail).push_back(t);
         if (!m->tiles_head.empty() && !m->tiles_tail.empty()) {
             if ((rc = m->d_tiles_head.ensure(m->tiles_head.size()))) return rc;
             if ((rc = m->d_tiles_tail.ensure(m->tiles_tail.size()))) return rc;
             HIP_TRY(dev_upload(m->d_tiles_head.p, m->tiles_head.data(), m->tiles_head.size() * sizeof(GTile)));
             HIP_TRY(dev_upload(m->d_tiles_tail.p, m->tiles_tail.data(), m->tiles_tail.size() * sizeof(GTile)));
-            if ((rc = m->strip_head.build(m->tiles_head))) return rc;
-            if ((rc = m->strip_tail.build(m->tiles_tail))) return rc;
+            if ((rc = m->strip_head.build(m->tiles_head, ncu))) return rc;
+            if ((rc = m->strip_tail.build(m->tiles_tail, ncu))) return rc;
         }
         HIP_TRY(dev_upload(m->d_pair_start.p, m->pair_start.data(), m->pair_start.size() * sizeof(int)));
     }
@@ -928,7 +950,7 @@ int mogp_gram_kinds(mogp_ctx* ctx, int C, int D, int T, int width, const double*
         G_HIP(dev_upload(dshape.p, shape, (size_t)C * C * T * sizeof(double)));
         ga.kind = dkind.p; ga.shape = dshape.p;
     }
-    G_TRY(launch_gram(ga, (int)tiles.size(), nullptr, radial ? extra_rows(kind, (size_t)C * C * T) : 0));
+    G_TRY(launch_gram(plan_cus(ctx), ga, (int)tiles.size(), nullptr, radial ? extra_rows(kind, (size_t)C * C * T) : 0));
     G_HIP(hipDeviceSynchronize());
     if (s1.identity && sc.identity) {
         G_HIP(hipMemcpy(K_out, dout.p, (size_t)R * Cc * sizeof(double), hipMemcpyDeviceToHost));
@@ -982,6 +1004,45 @@ int mogp_model_flow_replay(mogp_model* m, int on) {
     if (!m) return fail(MOGP_EINVAL, "mogp_model_flow_replay: null model");
     if (on && !(m->k.Wm.p && m->have_Kinv)) return fail(MOGP_EINVAL, "mogp_model_flow_replay: needs a completed gradient evaluation on this model first (its W_KK blocks are the replay's input)");
     m->replay_flow = on != 0;
+    return MOGP_OK;
+}
+
+int mogp_ctx_plan_cus(mogp_ctx* ctx, int ncu) {
+    if (!ctx || ncu < 0) return fail(MOGP_EINVAL, "mogp_ctx_plan_cus: need a context and ncu >= 0 (0: the device's count)");
+    ctx->plan_ncu = ncu;                        // the models' strip lists follow with their next evaluation (ensure_system, sparse_tiles)
+    return MOGP_OK;
+}
+
+int mogp_model_strip_runs(mogp_model* m, int which, int64_t* out4) {
+    if (!m || !out4 || which < 0 || which > 4) return fail(MOGP_EINVAL, "mogp_model_strip_runs: bad argument");
+    const StripTiles* lists[5] = {&m->strip, &m->strip_head, &m->strip_tail, &m->strip_own, m->tw ? &m->tw->strip_uf : nullptr};
+    const StripTiles* s = lists[which];
+    out4[0] = s ? s->ncu : -1; out4[1] = out4[2] = out4[3] = 0;
+    if (!s || s->ncu < 0) return MOGP_OK;                  // never built (or released)
+    out4[1] = (int64_t)s->segs.size(); out4[2] = (int64_t)s->rest.size();
+    for (const GSeg& g : s->segs) out4[3] = std::max<int64_t>(out4[3], g.n);
+    return MOGP_OK;
+}
+
+int mogp_strip_plan(int C, const int64_t* sizes, int ncu, int64_t* out, int64_t cap, int64_t* count) {
+    if (C <= 0 || !sizes || ncu <= 0 || ncu > (1 << 20) || !count) return fail(MOGP_EINVAL, "mogp_strip_plan: bad argument");
+    std::vector<int> off(C + 1, 0);
+    for (int c = 0; c < C; ++c) {
+        if (sizes[c] < 0 || sizes[c] > (1 << 24) || (int64_t)off[c] + sizes[c] > (1 << 24)) return fail(MOGP_EINVAL, "mogp_strip_plan: channel sizes out of range");
+        off[c + 1] = off[c] + (int)sizes[c];
+    }
+    std::vector<GTile> tiles, rest;
+    std::vector<int> ps;
+    std::vector<GSeg> segs;
+    build_sym_tiles(off, C, tiles, ps);
+    plan_strip_tiles(tiles, kStripMaxRun, 2 * ncu, segs, rest);
+    const int64_t W = 8, rows = (int64_t)segs.size() + (int64_t)rest.size();
+    *count = rows;
+    if (!out) return MOGP_OK;
+    if (cap < rows * W) return fail(MOGP_EINVAL, "mogp_strip_plan: the output holds fewer than 8 * count numbers");
+    int64_t* o = out;
+    for (const GSeg& g : segs) { const int64_t r[8] = {1, g.r0, g.c0, g.n, g.pair, g.diag, MOGP_GT, MOGP_GT}; std::copy(r, r + W, o); o += W; }
+    for (const GTile& t : rest) { const int64_t r[8] = {0, t.r0, t.c0, 1, t.pair, (t.flags & GT_DIAG) ? 1 : 0, t.nr, t.nc}; std::copy(r, r + W, o); o += W; }
     return MOGP_OK;
 }
 

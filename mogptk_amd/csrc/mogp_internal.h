@@ -176,7 +176,8 @@ struct MomentArgs {
 // The launchers cannot see the device-side kinds: a caller whose `kind` may hold an 8, 9 or 10 MUST pass `rows` (mogp_model::gate_kinds, which
 // mogp_model_set_kinds keeps beside `radial`), or the row is staged as phase factors without an error.  The flag is an argument and not a
 // member of GramArgs / MomentArgs because those are the kernels' arguments: a member would move every kernel's argument layout.
-int launch_gram(const GramArgs& a, int ntiles, hipStream_t s, int rows = 0);
+// ncu: the CU count the launch plans its persistent grid with (mogp::plan_cus of the caller's context)
+int launch_gram(int ncu, const GramArgs& a, int ntiles, hipStream_t s, int rows = 0);
 // The Jacobian of a rectangular Gram with respect to its row inputs (gram.hip:k_gram_dx): D row blocks in one launch, block d =
 // dK(xr, xc)/dxr_d at a.out + d * dstride, over the tile list of a rectangular launch (no GT_DIAG / GT_MIRROR tiles; noise, dvar, mirror, out2 and
 // the strip lists are not read).  Gaussian and enveloped tables, and kinds 0, 1, 3 - 7 with product groups; the caller refuses every other kind.
@@ -188,7 +189,9 @@ int launch_gram_dx(const GramArgs& a, int ntiles, int64_t dstride, hipStream_t s
 int launch_gram_dxdx(const GramArgs& a, int ntiles, int64_t bstride, hipStream_t s);
 // split a tile list into runs of at most `maxrun` full interior tiles (same pair and row block, consecutive columns) and the rest
 void split_strip_tiles(const std::vector<GTile>& tiles, int maxrun, std::vector<GSeg>& segs, std::vector<GTile>& rest);
-int launch_moments(const MomentArgs& a, hipStream_t s, int rows = 0);
+// ... and cut the runs for a launch on `slots` workgroup slots (mogp_api.hip; pure host code: mogp_strip_plan returns what it makes)
+void plan_strip_tiles(const std::vector<GTile>& tiles, int maxrun, int slots, std::vector<GSeg>& segs, std::vector<GTile>& rest);
+int launch_moments(int ncu, const MomentArgs& a, hipStream_t s, int rows = 0);
 inline int extra_rows(const int* kind, size_t n) {
     int rows = 0;
     for (size_t i = 0; i < n; ++i) {

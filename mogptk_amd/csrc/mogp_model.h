@@ -175,7 +175,13 @@ struct mogp_ctx {
     struct SkWs { DevBuf<double> ws; DevBuf<unsigned> flags; unsigned epoch = 0; };
     std::map<hipStream_t, SkWs> sk;
     int ncu = 0, ncu_reserved = 0;      // CUs of the device, and how many of them the private stream owns
+    int plan_ncu = 0;                   // mogp_ctx_plan_cus: the CU count the Gram and moment launches plan with instead of the device's (0: the device's)
 };
+namespace mogp {
+// the CU count behind the run cutting of the strip lists (2 slots per CU) and the persistent grids of k_gram (2 per CU) and k_moments_x (1 per CU):
+// the context's override (mogp_ctx_plan_cus) when set, the device's count otherwise.  Nothing else reads it.
+int plan_cus(const mogp_ctx* ctx);
+}
 
 struct TrtriLevel {
     std::vector<GemmTask> h1, h2;
@@ -254,9 +260,10 @@ struct StripTiles {
     std::vector<mogp::GTile> rest;
     mogp::DevBuf<mogp::GSeg> d_segs;
     mogp::DevBuf<mogp::GTile> d_rest;
-    int build(const std::vector<mogp::GTile>& tiles);      // host split + upload
+    int ncu = -1;                                          // the plan_cus value the runs were cut for (-1: never built)
+    int build(const std::vector<mogp::GTile>& tiles, int ncu);      // host split (plan_strip_tiles, 2 ncu slots) + upload
     void attach(mogp::GramArgs& ga) const { ga.segs = d_segs.p; ga.nsegs = (int)segs.size(); ga.rest = d_rest.p; ga.nrest = (int)rest.size(); }
-    void release() { d_segs.release(); d_rest.release(); }
+    void release() { d_segs.release(); d_rest.release(); segs.clear(); rest.clear(); ncu = -1; }
 };
 
 // workspaces of the Titsias sparse bound (config 5): two M x M SPD systems and three M x N panels

@@ -113,7 +113,7 @@ int mogp_oa_forward(mogp_model* m, const double* q_nu, const double* q_lambda, d
     ga.table = m->d_table.p; ga.T = m->T; ga.D = D; ga.C = C; ga.W = m->Wt;
     ga.out = o.K.p; ga.ldo = Npad; ga.noise = nullptr; ga.dvar = nullptr; ga.jitter_abs = 0.0; ga.mirror = 0;
     m->strip.attach(ga);
-    RC(launch_gram(ga, (int)m->tiles.size(), m->st));
+    RC(launch_gram(plan_cus(m->ctx), ga, (int)m->tiles.size(), m->st));
     RC(launch_pad_identity(o.K.p, Npad, N, Npad, m->st));          // padded rows / columns: zero off the diagonal (lambda = 0 there anyway)
     // mu = K nu
     double* dmu = o.vec.p + V_MU * Npad;
@@ -211,7 +211,7 @@ int mogp_oa_backward(mogp_model* m, const double* e, const double* f, double* mo
     ma.gzr = nullptr; ma.gzc = nullptr; ma.ldgz = Npad;
     ma.partial = m->d_partial.p;
     ma.phases_ready = 1;                                        // the forward pass's Gram filled ph_xx for these inputs and this table
-    RC(launch_moments(ma, m->st));
+    RC(launch_moments(plan_cus(m->ctx), ma, m->st));
     RC(launch_moment_reduce(m->d_partial.p, m->d_pair_start.p, P, T, W, D, m->d_moments.p, m->st, 1));
 
     std::vector<double> hb(Npad), hs(Npad), hr(Npad), hg(Npad);

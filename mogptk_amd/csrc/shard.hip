@@ -19,7 +19,7 @@ static int sweep_eval_begin(mogp_model* m, const double* noise_var, const double
     const bool own = m->sh_n > 1 && m->own_n == m->sh_n && m->own_rank == m->sh_rank;
     if (own) ga.tiles = m->d_tiles_own.p;
     (own ? m->strip_own : m->strip).attach(ga);
-    if ((rc = launch_gram(ga, (int)(own ? m->tiles_own.size() : m->tiles.size()), m->st))) return rc;
+    if ((rc = launch_gram(plan_cus(m->ctx), ga, (int)(own ? m->tiles_own.size() : m->tiles.size()), m->st))) return rc;
     // (owned-rows form: the padding rows lie in the last tile row -- its owner's business; everybody else gets them with the pivot block)
     if (!(m->sh_owned && m->sh_n > 1 && (m->nb - 1) % m->sh_n != m->sh_rank))
         if ((rc = launch_pad_identity(m->k.A.p, Npad, N, Npad, m->st))) return rc;
@@ -105,7 +105,7 @@ int mogp_shard_config(mogp_model* m, int rank, int nranks) {
         if ((rc = m->d_tiles_own.ensure(std::max<size_t>(m->tiles_own.size(), 1)))) return rc;
         if ((rc = m->d_pair_start_own.ensure(m->pair_start_own.size()))) return rc;
         HIP_TRY(dev_upload(m->d_tiles_own.p, m->tiles_own.data(), m->tiles_own.size() * sizeof(GTile)));
-        if ((rc = m->strip_own.build(m->tiles_own))) return rc;
+        if ((rc = m->strip_own.build(m->tiles_own, plan_cus(m->ctx)))) return rc;
         HIP_TRY(dev_upload(m->d_pair_start_own.p, m->pair_start_own.data(), m->pair_start_own.size() * sizeof(int)));
         m->own_rank = rank; m->own_n = nranks;
     }
@@ -354,7 +354,7 @@ int mogp_exact_predict_sharded(mogp_model* m, const double* noise_var, const dou
     if ((rc = m->d_pred_tasks.ensure(std::max<size_t>(tasks.size(), 1)))) return rc;
     if (!tasks.empty()) HIP_TRY(hipMemcpyAsync(m->d_pred_tasks.p, tasks.data(), tasks.size() * sizeof(GemmTask), hipMemcpyHostToDevice, m->st));
     HIP_TRY(hipMemsetAsync(m->d_var.p, 0, 2 * Spad * sizeof(double), m->st));
-    if ((rc = launch_gram(ga, ts.ntiles, m->st, m->radial ? m->gate_kinds : 0))) return rc;
+    if ((rc = launch_gram(plan_cus(m->ctx), ga, ts.ntiles, m->st, m->radial ? m->gate_kinds : 0))) return rc;
     if ((rc = launch_gemv_rows(m->d_Ksf.p, Npad, Spad, Npad, m->d_alpha.p, m->d_mu.p, m->st))) return rc;            // mu = K_sf alpha (alpha is complete on every rank)
     if (nown > 0) {
         GemmArgs g{};

@@ -182,6 +182,8 @@ int sparse_workspace(mogp_model* m, TitsiasWork& t, int64_t Mpad, int64_t M) {
 int sparse_tiles(mogp_model* m, TitsiasWork& t, const SortedX& sz, bool want_uf) {
     std::vector<int> key(sz.off);
     key.insert(key.end(), m->sx.off.begin(), m->sx.off.end());
+    const int ncu = plan_cus(m->ctx);
+    key.push_back(ncu);                                         // the CU count the strip runs of (Z, X) are cut for (mogp_ctx_plan_cus may change it)
     key.push_back(1);                                           // last entry: the (Z, X) lists are there
     if (key == t.tile_key) return 0;
     if (!want_uf) { key.back() = 0; if (key == t.tile_key) return 0; }
@@ -198,7 +200,7 @@ int sparse_tiles(mogp_model* m, TitsiasWork& t, const SortedX& sz, bool want_uf)
         RC(t.tiles_uf.ensure(tuf.size())); RC(t.ps_uf.ensure(psuf.size()));
         HIP_TRY(dev_upload(t.tiles_uf.p, tuf.data(), tuf.size() * sizeof(GTile)));
         HIP_TRY(dev_upload(t.ps_uf.p, psuf.data(), psuf.size() * sizeof(int)));
-        RC(t.strip_uf.build(tuf));
+        RC(t.strip_uf.build(tuf, ncu));
     }
     t.n_tuu = tuu.size(); t.n_tuf = tuf.size();
     t.tile_key = key;
@@ -228,7 +230,7 @@ int sparse_kuu(mogp_model* m, int64_t M, const double* Z, double jitter, bool wa
     RC(t.ph_zz.prepare(sz.off, sz.off, C, m->T, Mpad, Mpad, m->st, ga.ph));
     ga.table = m->d_table.p; ga.T = m->T; ga.D = D; ga.C = C; ga.W = W; ga.out = t.a.A.p; ga.ldo = Mpad;
     ga.noise = t.zero_noise.p; ga.dvar = nullptr; ga.jitter_abs = *jit; ga.mirror = 0;
-    RC(launch_gram(ga, (int)t.n_tuu, m->st));
+    RC(launch_gram(plan_cus(m->ctx), ga, (int)t.n_tuu, m->st));
     RC(launch_pad_identity(t.a.A.p, Mpad, M, Mpad, m->st));
     t.a.keep_L = true;                                                          // the solves need L itself, diagonal tiles included
     t.a.refine_panels = true;                                                   // K_uu + jitter is ill-conditioned: mogp_api.hip:spd_potrf
@@ -243,7 +245,7 @@ int sparse_kuf(mogp_model* m, TitsiasWork& t, const SortedX& sz, hipStream_t str
     ga.table = m->d_table.p; ga.T = m->T; ga.D = m->D; ga.C = m->C; ga.W = m->Wt; ga.out = t.B.p; ga.ldo = Npad; ga.mirror = 0;
     ga.out2 = out2;
     if (use_strips) t.strip_uf.attach(ga);                                      // full interior tiles in runs of four on the strip kernel
-    return launch_gram(ga, (int)t.n_tuf, stream);
+    return launch_gram(plan_cus(m->ctx), ga, (int)t.n_tuf, stream);
 }
 
 // out = P rhs with P = Q^-1 formed explicitly, plus ONE step of iterative refinement against Q (Titsias: t1 = Pq (v y) against Qs; Snelson:
@@ -324,7 +326,7 @@ int sparse_moments(mogp_model* m, TitsiasWork& t, const SortedX& sz, const Momen
         ma.G = uf->G; ma.ldg = uf->ldg; ma.ru = uf->ru; ma.rw = uf->rw; ma.rcoef = uf->rcoef; ma.sym = 0;
         ma.gzr = uf->dz ? t.gz.p : nullptr; ma.gzc = nullptr; ma.partial = t.partial_uf.p;
         gz_attach(t, ma, true);
-        RC(launch_moments(ma, m->st));
+        RC(launch_moments(plan_cus(m->ctx), ma, m->st));
         RC(launch_moment_reduce(t.partial_uf.p, t.ps_uf.p, C * C, T, W, D, t.mom_uf.p, m->st, 0));
         if (sharded) {                       // the (Z, X) moments and their share of d/dZ are sums over data points; the (Z, Z) pass below is not
             RC(comm_allreduce(m->ctx, t.mom_uf.p, (int64_t)C * C * T * W, m->st));
@@ -339,7 +341,7 @@ int sparse_moments(mogp_model* m, TitsiasWork& t, const SortedX& sz, const Momen
     ma.G = uu.G; ma.ldg = uu.ldg; ma.ru = uu.ru; ma.rw = uu.rw; ma.rcoef = uu.rcoef; ma.sym = 1;
     ma.gzr = ma.gzc = uu.dz ? t.gz.p : nullptr; ma.partial = t.partial_uu.p;
     gz_attach(t, ma, false);
-    RC(launch_moments(ma, m->st));
+    RC(launch_moments(plan_cus(m->ctx), ma, m->st));
     RC(launch_moment_reduce(t.partial_uu.p, t.ps_uu.p, P, T, W, D, t.mom_uu.p, m->st, 1));
     return 0;
 }
@@ -361,7 +363,7 @@ int sparse_predict_panels(mogp_model* m, TitsiasWork& t, const SortedX& sz, int6
     ga.tiles = m->d_ptiles.p; ga.xr = t.zx.p; ga.ldxr = Mpad; ga.xc = m->d_xs.p; ga.ldxc = Spad; ga.nrows = sz.M; ga.ncols = S;
     RC(t.ph_zs.prepare(sz.off, ss.off, C, m->T, Mpad, Spad, m->st, ga.ph));
     ga.table = m->d_table.p; ga.T = m->T; ga.D = D; ga.C = C; ga.W = m->Wt; ga.out = t.Kus.p; ga.ldo = Spad; ga.mirror = 0;
-    RC(launch_gram(ga, (int)tus.size(), m->st));
+    RC(launch_gram(plan_cus(m->ctx), ga, (int)tus.size(), m->st));
     HIP_TRY(hipMemcpyAsync(t.Aus.p, t.Kus.p, (size_t)Mpad * Spad * sizeof(double), hipMemcpyDeviceToDevice, m->st));
     return trsm_lower(m, t.a.A.p, Mpad, (int)(Mpad / MOGP_TILE), t.Aus.p, Spad, Spad, false);             // a = L^-1 Kus
 }

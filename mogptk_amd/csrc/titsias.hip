@@ -293,7 +293,7 @@ int mogp_sparse_predict_cov(mogp_model* m, int64_t S, double* cov) {
     ga.tiles = m->d_ptiles.p; ga.xr = m->d_xs.p; ga.ldxr = Spad; ga.xc = m->d_xs.p; ga.ldxc = Spad; ga.nrows = S; ga.ncols = S;
     RC(m->ph_ss.prepare(ss.off, ss.off, C, m->T, Spad, Spad, m->st, ga.ph));
     ga.table = m->d_table.p; ga.T = m->T; ga.D = D; ga.C = C; ga.W = m->Wt; ga.out = m->d_Kss.p; ga.ldo = Spad; ga.mirror = 1;
-    RC(launch_gram(ga, (int)st_tiles.size(), m->st));
+    RC(launch_gram(plan_cus(m->ctx), ga, (int)st_tiles.size(), m->st));
     const int st = (int)(Spad / MOGP_TILE);
     GemmArgs g = make_gemm(t.Aus.p, Spad, 1, t.Aus.p, Spad, 1, m->d_Kss.p, Spad, -1.0, GM_RECT, st, st, Mpad);
     g.beta = 1.0;
